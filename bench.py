@@ -8,6 +8,7 @@ cosine matrix -> top-10.  Inputs (bf16 NCHW frames, token ids) are resident in H
 timed region; weights are random-init of the real architecture (no checkpoints offline).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          N > 1: re-executes itself as N ranks (one per GPU)
+    python bench.py ... --dump-outputs DIR                       also writes the last timed step's results as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` is binding: run directly it starts N ranks under torch.distributed.run (hirest_amd/launch.py) and fails
@@ -334,6 +335,28 @@ def cpu_baseline(model, frames, cfg, n):
             "min_cosine_gpu_vs_cpu_on_sample": cos}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, rows, scores, val, idx):
+    """--dump-outputs: the last timed step's results as float32 / float64 .npy files, so two builds can be compared output
+    for output.  video_rows [V, E] and scores [Q, V] grow with the corpus: past DUMP_MAX_BYTES in all they are cut to a fixed,
+    seeded sample of videos, whose corpus indices go to video_index.npy."""
+    import numpy as np
+    V = rows.shape[0]
+    per_video = 4 * (rows.shape[1] + scores.shape[0]) + 8             # + its video_index entry when sampled
+    keep = max(1, (DUMP_MAX_BYTES - 4096 - 12 * val.numel()) // per_video)   # 4096: the .npy headers
+    out = {"topk_values": val.float(), "topk_indices": idx.double()}
+    if keep < V:
+        sel = torch.randperm(V, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        out["video_index"] = sel.double()
+        rows, scores = rows[sel.to(rows.device)], scores[:, sel.to(scores.device)]
+    out["video_rows"], out["scores"] = rows.float(), scores.float()
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -355,10 +378,14 @@ def main():
     ap.add_argument("--share-gpu", action="store_true", help="FUNCTIONAL TEST ONLY (needs --backend gloo): rank r runs on device r %% device_count, "
                     "so the N-rank code path — launcher, timing protocol, gather, rank-0 report — runs on a one-GPU box.  The line is marked INVALID")
     ap.add_argument("--gemm-dbg", type=int, default=0, help="hirest_gemm_debug_mode bits: TIMING EXPERIMENTS ONLY, the line is not a valid result")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned (gathered video rows, "
+                    "scores, top-k values and indices) as DIR/<name>.npy; same arguments, same inputs")
     args = ap.parse_args()
     if args.cpu_probe > 0:
         _cpu_probe_child(args.cpu_probe)
         return
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.frames % FRAMES_PER_VIDEO != 0:
         raise SystemExit(f"--frames must be a multiple of {FRAMES_PER_VIDEO} (whole videos): a remainder would be counted "
@@ -406,17 +433,19 @@ def main():
     def step():
         pooled = retrieval.encode_videos(model, frames)                     # [V_local, 1024]
         allv = gather(pooled, V_total)                                      # RCCL all-gather (no-op at N=1)
-        _, val, idx = retrieval.retrieve(text_n, allv, min(TOPK, V_total))
-        return idx
+        scores, val, idx = retrieval.retrieve(text_n, allv, min(TOPK, V_total))
+        return allv, scores, val, idx
 
     tinfo = {}
-    elapsed, idx = launch.timed_steps(step, args.warmup, args.steps, torch.cuda.synchronize,
-                                      on_timed_start=(None if args.no_profile else (lambda: lib.hirest_profile_enable(1))), reduce_device=dev,
-                                      info=tinfo)
+    elapsed, last = launch.timed_steps(step, args.warmup, args.steps, torch.cuda.synchronize,
+                                       on_timed_start=(None if args.no_profile else (lambda: lib.hirest_profile_enable(1))), reduce_device=dev,
+                                       info=tinfo)
     # per-launch records of the timed steps (this rank)
     recs = (_lib.ProfRecord * 200000)()
     nrec = lib.hirest_profile_collect(recs, len(recs))
     lib.hirest_profile_enable(0)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, *last)
 
     out = None
     if rank == 0:
