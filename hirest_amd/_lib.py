@@ -159,6 +159,27 @@ class TrainBlockGrads(C.Structure):
                 ("scratch_bytes", C.c_size_t)]
 
 
+class JpegImage(C.Structure):
+    """hirest_jpeg_image (include/hirest_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "ncomp", "hs", "vs", "restart_interval", "mcux", "mcuy", "supported",
+                                         "reason")] + \
+               [("scan_begin", C.c_int64), ("scan_end", C.c_int64), ("table_set", C.c_int32), ("reserved", C.c_int32),
+                ("data_offset", C.c_int64), ("out_offset", C.c_int64), ("ws_offset", C.c_int64),
+                ("plane_offset", C.c_int64)]
+
+
+class JpegTables(C.Structure):
+    """hirest_jpeg_tables (include/hirest_hip.h)."""
+    _fields_ = [("qt", (C.c_uint16 * 64) * 3), ("huff_bits", (C.c_uint8 * 16) * 6), ("huff_vals", (C.c_uint8 * 256) * 6)]
+
+
+JPEG_REASONS = {0: "ok", 1: "not a JPEG / malformed markers", 2: "progressive", 3: "arithmetic coding", 4: "lossless / hierarchical",
+                5: "not 8-bit", 6: "colour space (CMYK / YCCK / RGB / component count)", 7: "sampling factors", 8: "multi-scan",
+                9: "truncated (no EOI after the scan)", 10: "bad or missing tables", 11: "image size"}
+JPEG_STATUS = {1: "bad Huffman code", 2: "more than 64 coefficients in a block", 4: "out of data", 8: "RSTn out of sequence",
+               16: "unsupported"}
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("kind", C.c_int32), ("tag", C.c_int32), ("d0", C.c_int64), ("d1", C.c_int64), ("d2", C.c_int64),
                 ("ms", C.c_float)]
@@ -313,6 +334,11 @@ _SIGNATURES = {
     "hirest_preprocess_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "hirest_preprocess_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hirest_jpeg_parse": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(JpegImage), C.POINTER(JpegTables)]),
+    "hirest_jpeg_workspace_bytes": (C.c_int64, [C.POINTER(JpegImage), C.c_int32]),
+    "hirest_jpeg_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_void_p]),
+    "hirest_jpeg_decode_host": (C.c_int, [C.POINTER(JpegImage), C.POINTER(JpegTables), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "hirest_interval_iou_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "hirest_step_bound_pr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -244,3 +244,55 @@ class FeatureWriter:
     def __exit__(self, *exc):
         self.close()
         return False
+
+
+def _decoded_video(model, frames):
+    """jpeg.decode output of one video -> one uint8 tensor the tower path takes: a [T,H,W,3] tensor passes through; a video
+    whose frames differ in size (a list) is resized + cropped per frame size on the device into [T,S,S,3]."""
+    if isinstance(frames, torch.Tensor):
+        return frames
+    if not frames:
+        raise ValueError("empty frame list")
+    size = _model_input_size(model)
+    out = torch.empty((len(frames), size, size, 3), dtype=torch.uint8, device=frames[0].device)
+    by_shape = {}
+    for i, f in enumerate(frames):
+        by_shape.setdefault(tuple(f.shape), []).append(i)
+    for members in by_shape.values():
+        out[torch.tensor(members, device=out.device)] = _prepare_frames(model, torch.stack([frames[i] for i in members]))
+    return out
+
+
+@torch.no_grad()
+def extract_frame_dir(model, frame_path, save_path, slice_start: int = 0, slice_end: int = -1, min_call: int = 256,
+                      max_call: int = 1024, normalize: bool = True, device=None):
+    """extraction/video_features/extract_features.py:29-69 as one call: every ``<frame_path>/<video>/`` directory (in
+    ``glob`` order, sliced like ``--slice_start`` / ``--slice_end``) has its ``*.jpg`` frames decoded on the device in the
+    reference's integer order (``jpeg.read_frame_dir``), encoded (``frame_features_many``: short videos share a tower call)
+    and written as ``<save_path>/<video>.pt`` through ``FeatureWriter``.  The files are those ``frame_features`` writes for
+    the Pillow-decoded frames.  Returns the video names written."""
+    from glob import glob
+    from . import jpeg
+    videos = glob(f"{frame_path}/*/")
+    videos = videos[slice_start:slice_end] if slice_end != -1 else videos[slice_start:]
+    if device is None:
+        device = next(model.parameters()).device
+    names = []
+    with FeatureWriter(save_path) as writer:
+        i = 0
+        while i < len(videos):
+            # decode videos until the tower has at least max_call frames to work on, then encode and hand them to the writer
+            batch, count = [], 0
+            while i < len(videos) and (not batch or count < max_call):
+                files = jpeg.list_frame_dir(videos[i])
+                name = videos[i].rstrip("/").split("/")[-1]
+                frames = _decoded_video(model, jpeg.decode(files, device)) if files else \
+                    torch.zeros((0, 1, 1, 3), dtype=torch.uint8, device=device)
+                batch.append((name, frames))
+                count += int(frames.shape[0])
+                i += 1
+            feats = frame_features_many(model, [f for _, f in batch], min_call=min_call, max_call=max_call, normalize=normalize)
+            for (name, _), f in zip(batch, feats):
+                writer.submit(name, f)
+                names.append(name)
+    return names

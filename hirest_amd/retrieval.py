@@ -496,3 +496,65 @@ def corpus_digest(video_rows: torch.Tensor, topk_idx: torch.Tensor) -> Dict[str,
     import hashlib
     return {"pooled_sha256": hashlib.sha256(video_rows.detach().float().cpu().contiguous().numpy().tobytes()).hexdigest(),
             "top10_sha256": hashlib.sha256(topk_idx.detach().cpu().to(torch.int32).contiguous().numpy().tobytes()).hexdigest()}
+
+
+class JpegFrameSource(FrameSource):
+    """The ``--raw_frame`` corpus straight from JPEG frame directories (``VideoFramesDataset``, inference_video_retrieval.py:
+    13-60): video ``v`` is ``<frame_dir>/<video_ids[v]>/frame_{i:06d}.jpg`` for ``i < n_model_frames`` (every ``*.jpg`` in
+    integer order when ``n_model_frames`` is not positive), decoded on the device (``jpeg.decode``, Pillow-exact), resized /
+    cropped / normalised per frame size with ``FramePreprocessor(normalized=True)`` (the model's image size, mean and std)
+    and handed to ``FrameSource`` as ``[V, F, 3, S, S]`` blocks, so ``run_corpus`` takes it unchanged.  Videos may differ in
+    frame size; with ``n_model_frames <= 0`` every video of a call must hold the same number of frames."""
+
+    def __init__(self, frame_dir, video_ids: Sequence[str], videos_per_call: int = 32, min_frames_per_call: int = 256):
+        super().__init__(video_ids, self._decode_block, videos_per_call, min_frames_per_call)
+        self.frame_dir = str(frame_dir)
+        self._n = None
+        self._pre = None
+        self._device = None
+
+    def _bind(self, model, n_model_frames, device):
+        from .preprocess import FramePreprocessor
+        self._n = n_model_frames
+        self._device = device
+        if self._pre is None:
+            vis = getattr(model, "visual", None)
+            size = getattr(vis, "image_size", None) or getattr(vis, "input_resolution", None)
+            size = size[0] if isinstance(size, (tuple, list)) else size
+            self._pre = FramePreprocessor(int(size), getattr(vis, "image_mean", None), getattr(vis, "image_std", None))
+
+    def frame_paths(self, v: int) -> List[str]:
+        import os
+        from .jpeg import list_frame_dir
+        d = os.path.join(self.frame_dir, self.video_ids[v])
+        if self._n is not None and self._n > 0:
+            return [os.path.join(d, f"frame_{str(i).zfill(6)}.jpg") for i in range(self._n)]
+        return list_frame_dir(d)
+
+    def _decode_block(self, lo: int, hi: int) -> torch.Tensor:
+        from . import jpeg
+        paths = [self.frame_paths(v) for v in range(lo, hi)]
+        F = len(paths[0])
+        if any(len(p) != F for p in paths):
+            raise ValueError("JpegFrameSource: the videos of one call hold different frame counts; pass n_model_frames")
+        flat = [p for ps in paths for p in ps]
+        dec = jpeg.decode(flat, self._device)
+        S = self._pre.size
+        if isinstance(dec, torch.Tensor):
+            x = self._pre(dec, normalized=True)
+        else:
+            x = torch.empty((len(flat), 3, S, S), dtype=torch.float32, device=dec[0].device)
+            by_shape: Dict[Tuple[int, ...], List[int]] = {}
+            for i, f in enumerate(dec):
+                by_shape.setdefault(tuple(f.shape), []).append(i)
+            for members in by_shape.values():
+                x[torch.tensor(members, device=x.device)] = self._pre(torch.stack([dec[i] for i in members]), normalized=True)
+        return x.reshape(hi - lo, F, 3, S, S)
+
+    def pooled_rows(self, model, lo: int, hi: int, n_model_frames: Optional[int], device) -> torch.Tensor:
+        self._bind(model, n_model_frames, device)
+        return super().pooled_rows(model, lo, hi, n_model_frames, device)
+
+    def pooled_rows_of(self, model, ids: Sequence[int], n_model_frames: Optional[int], device) -> torch.Tensor:
+        self._bind(model, n_model_frames, device)
+        return _frame_source_rows_of(self, model, ids, n_model_frames, device)

@@ -764,6 +764,68 @@ int hirest_preprocess_u8(const uint8_t* frames, int32_t B, int32_t in_h, int32_t
                          void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Baseline-JPEG decode (the frames of extract_features.py:45-49 and inference_video_retrieval.py:35-46), bit-exact with
+ * Pillow's Image.open(f).convert("RGB") on libjpeg-turbo (JDCT_ISLOW, fancy upsampling).
+ * Supported on the device: SOF0 / SOF1, 8-bit, Huffman, one interleaved scan; grey or YCbCr; luma sampling 1x1, 2x1,
+ * 2x2 with chroma 1x1; any DQT / DHT; any restart interval; APPn / COM skipped.  Everything else is reported
+ * unsupported (supported = 0, reason = HIREST_JPEG_*) and is the caller's to decode on the host.
+ *   hirest_jpeg_parse           HOST: markers of one file (data, size) -> descriptor + its raw tables (per component:
+ *                               quantisation in natural order, DC / AC Huffman tables).  Returns 0 whether or not the
+ *                               file is supported.
+ *   hirest_jpeg_workspace_bytes HOST: lays out the workspace of exactly this imgs[0..n) for hirest_jpeg_decode (table_set
+ *                               filled in first): assigns ws_offset (coefficients) and plane_offset (component planes) of
+ *                               every image and returns the total bytes.  The coefficient blocks of the (up to) 16 images
+ *                               one entropy workgroup decodes are interleaved (block b of lane l at group + 128 l + 2048 b)
+ *                               so that the lanes' stores stay within one 2 KB span.
+ *   hirest_jpeg_decode          DEVICE: n images.  imgs_host / imgs_dev are the same descriptors (host copy for the launch
+ *                               geometry, device copy for the kernels) with table_set (index into tables_dev), data_offset
+ *                               (first byte of the file in data) and out_offset (byte offset of the [height, width, 3]
+ *                               uint8 frame in out) filled in by the caller.  Images sharing a table set should be
+ *                               adjacent (one entropy launch per run).  status[i] (device int32) = 0 on success, else
+ *                               HIREST_JPEG_ST_* bits: the frame is then not written and the caller decodes the file on
+ *                               the host.  workspace 256-B aligned, data 8-B aligned.
+ *   hirest_jpeg_decode_host     HOST: the same arithmetic on the CPU for one image (data = the file, out = H*W*3 bytes).
+ * ------------------------------------------------------------------------------------ */
+enum hirest_jpeg_reason {
+    HIREST_JPEG_OK = 0, HIREST_JPEG_NOT_JPEG = 1, HIREST_JPEG_PROGRESSIVE = 2, HIREST_JPEG_ARITHMETIC = 3,
+    HIREST_JPEG_LOSSLESS = 4,      /* lossless or hierarchical */
+    HIREST_JPEG_PRECISION = 5,     /* not 8-bit samples */
+    HIREST_JPEG_COLOR = 6,         /* CMYK, YCCK, RGB, or 2 / 4+ components */
+    HIREST_JPEG_SAMPLING = 7, HIREST_JPEG_MULTI_SCAN = 8,
+    HIREST_JPEG_TRUNCATED = 9,     /* no EOI after the scan */
+    HIREST_JPEG_BAD_TABLES = 10, HIREST_JPEG_SIZE = 11
+};
+#define HIREST_JPEG_ST_BAD_CODE 1
+#define HIREST_JPEG_ST_COEF_OVERRUN 2
+#define HIREST_JPEG_ST_OUT_OF_DATA 4
+#define HIREST_JPEG_ST_BAD_RESTART 8
+#define HIREST_JPEG_ST_UNSUPPORTED 16
+
+typedef struct {
+    int32_t width, height, ncomp, hs, vs;   /* hs x vs = luma sampling (chroma 1x1); 1 x 1 for grey */
+    int32_t restart_interval, mcux, mcuy;    /* MCUs per row / column */
+    int32_t supported, reason;
+    int64_t scan_begin, scan_end;            /* entropy-coded bytes [begin, end) of the file; end = the EOI marker */
+    int32_t table_set, reserved;             /* caller */
+    int64_t data_offset, out_offset;         /* caller; data_offset a multiple of 8 */
+    int64_t ws_offset, plane_offset;         /* hirest_jpeg_workspace_bytes */
+} hirest_jpeg_image;
+
+typedef struct {
+    uint16_t qt[3][64];                      /* per component, natural order */
+    uint8_t huff_bits[6][16];                /* [2c] DC, [2c + 1] AC table of component c: code counts of length 1..16 */
+    uint8_t huff_vals[6][256];
+} hirest_jpeg_tables;
+
+int hirest_jpeg_parse(const uint8_t* data, int64_t size, hirest_jpeg_image* img, hirest_jpeg_tables* tables);
+int64_t hirest_jpeg_workspace_bytes(hirest_jpeg_image* imgs, int32_t n);
+int hirest_jpeg_decode(const hirest_jpeg_image* imgs_host, const hirest_jpeg_image* imgs_dev, int32_t n,
+                       const hirest_jpeg_tables* tables_dev, const uint8_t* data, uint8_t* out, int32_t* status,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int hirest_jpeg_decode_host(const hirest_jpeg_image* img, const hirest_jpeg_tables* tables, const uint8_t* data,
+                            uint8_t* out, int32_t* status);
+
+/* ------------------------------------------------------------------------------------
  * Moment-task evaluation on device (evaluate.py), double precision with Python's operation order:
  *   hirest_interval_iou_f64     compute_iou (evaluate.py:24-31) of n interval pairs a[i] (= interval_1), b[i];
  *                               R@tIoU of evaluate_moment_retrieval (:83-121) is !(iou < tIoU).
