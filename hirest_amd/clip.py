@@ -270,7 +270,7 @@ def load(name: str, device: Union[str, torch.device] = "cuda", jit: bool = False
     ``'clip'`` retrieval branch imports (inference_video_retrieval.py:11,169; hirest_dataset.py:84): same weights, same tower, but
     ``encode_image`` returns the CLS embedding ``ln_post(x[:, 0]) @ proj`` -> [B, embed_dim] instead of the vendored copy's projected
     patch tokens.  That package is not part of the reference tree, so this head is checked against the oracle's restatement of its
-    published forward only (parity unpinned)."""
+    published forward and against transformers' CLIPModel on the same weights (tests/test_gpu_clip_score.py)."""
     if not os.path.isfile(name):
         raise RuntimeError(f"Model {name} not found; available models = {available_models()}")
     try:

@@ -1,6 +1,6 @@
 // Pooling + scoring: frame -> video mean pooling with L2 normalisation, the text x video cosine
-// matrix in fp32, and per-query top-k with the reference's tie rule
-// (inference_video_retrieval.py:283-285,323-334; evaluate.py:58-60).  All HBM-bound / tiny.
+// matrix in fp32, per-query top-k with the reference's tie rule, and the per-caption CLIPScore
+// (inference_video_retrieval.py:283-285,323-334; evaluate.py:58-60,250-262).  All HBM-bound / tiny.
 #include "common.h"
 
 namespace {
@@ -236,6 +236,53 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
     }
 }
 
+
+// CLIPScore (evaluate.py:250-262): one wavefront per caption c; out[c] = (1/K) sum_j <t, i_j> / (|t| |i_j|) with t = txt[c] and
+// i_j = img[sel[c][j]].  Each lane strides the E columns; the three sums of a row go through the xor butterfly, which leaves the
+// same bits in every lane (fp32 addition commutes), and the K terms are added in j order.  A caption's result therefore depends on
+// its own rows only, never on C or on its place in the batch.  A row id outside [0, U) gives NaN and reads nothing.
+template <typename T> __device__ __forceinline__ float load_elem(const T* p, int64_t i);
+template <> __device__ __forceinline__ float load_elem<float>(const float* p, int64_t i) { return p[i]; }
+template <> __device__ __forceinline__ float load_elem<uint16_t>(const uint16_t* p, int64_t i) {
+    return __uint_as_float((uint32_t)p[i] << 16);
+}
+
+template <typename TI, typename TT>
+__global__ __launch_bounds__(256) void clip_score_kernel(const TI* __restrict__ img, int U, const TT* __restrict__ txt,
+                                                        const int32_t* __restrict__ sel, int C, int K, int E, float* __restrict__ out) {
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= C) return;
+    const int64_t tb = (int64_t)c * E;
+    float tt = 0.f;
+    for (int e = lane; e < E; e += 64) {
+        const float t = load_elem(txt, tb + e);
+        tt = fmaf(t, t, tt);
+    }
+    const float tn = sqrtf(wave_sum(tt));
+    float acc = 0.f;
+    for (int j = 0; j < K; ++j) {
+        const int row = sel[(int64_t)c * K + j];
+        if (row < 0 || row >= U) { acc = __builtin_nanf(""); break; }
+        const int64_t ib = (int64_t)row * E;
+        float dot = 0.f, ii = 0.f;
+        for (int e = lane; e < E; e += 64) {
+            const float x = load_elem(img, ib + e);
+            dot = fmaf(x, load_elem(txt, tb + e), dot);
+            ii = fmaf(x, x, ii);
+        }
+        dot = wave_sum(dot);
+        ii = wave_sum(ii);
+        acc += dot / (tn * sqrtf(ii));
+    }
+    if (lane == 0) out[c] = acc / (float)K;
+}
+
+template <typename TI, typename TT>
+static void launch_clip_score(const void* img, int U, const void* txt, const int32_t* sel, int C, int K, int E, float* out, hipStream_t s) {
+    hipLaunchKernelGGL((clip_score_kernel<TI, TT>), dim3((C + 3) / 4), dim3(256), 0, s, reinterpret_cast<const TI*>(img), U,
+                       reinterpret_cast<const TT*>(txt), sel, C, K, E, out);
+}
+
 }  // namespace
 
 extern "C" int hirest_pool_l2norm(const float* frame_embeds, float* out, int32_t V, int32_t F, int32_t E,
@@ -294,5 +341,18 @@ extern "C" int hirest_topk_f32_ws(const float* scores, const int32_t* tie_rank, 
     int32_t* ci = ct + n;
     hipLaunchKernelGGL(topk_chunk_kernel, dim3(nchunk, Q), dim3(256), 0, s, scores, tie_rank, V, k, nchunk, cs, ct, ci);
     hipLaunchKernelGGL(topk_merge_kernel, dim3(Q), dim3(256), 0, s, cs, ct, ci, nchunk * k, k, out_index, out_score);
+    return hirest_launch_status();
+}
+
+extern "C" int hirest_clip_score(const void* img_rows, int32_t img_dtype, int32_t U, const void* txt_rows, int32_t txt_dtype,
+                                 const int32_t* sel, int32_t C, int32_t K, int32_t E, float* out, void* stream) {
+    if (!img_rows || !txt_rows || !sel || !out || C < 0 || K < 1 || E < 1 || U < 1) return HIREST_E_BADARG;
+    if ((img_dtype != 0 && img_dtype != 1) || (txt_dtype != 0 && txt_dtype != 1)) return HIREST_E_BADARG;   // fp32 | bf16
+    if (C == 0) return 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (img_dtype == 0 && txt_dtype == 0) launch_clip_score<float, float>(img_rows, U, txt_rows, sel, C, K, E, out, s);
+    else if (img_dtype == 0) launch_clip_score<float, uint16_t>(img_rows, U, txt_rows, sel, C, K, E, out, s);
+    else if (txt_dtype == 0) launch_clip_score<uint16_t, float>(img_rows, U, txt_rows, sel, C, K, E, out, s);
+    else launch_clip_score<uint16_t, uint16_t>(img_rows, U, txt_rows, sel, C, K, E, out, s);
     return hirest_launch_status();
 }

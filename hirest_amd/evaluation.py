@@ -6,19 +6,22 @@ names and dict layouts, so a driver holding predictions can score them without t
     evaluate_moment_retrieval(gt, pred, prompt_to_cat)      # evaluate.py:83-121   R@0.5 / R@0.7 per prompt category
     compute_step_bound_scores(gt, pred, video_to_cat)       # evaluate.py:123-188  step recall / precision at tIoU
     preprocess_moment_bounds(gt, pred)                      # evaluate.py:322-412  filter + NMS + gap filling
+    evaluate_clip_score(gt, pred, video_to_cat, model, dir) # evaluate.py:190-320  the CLIPScore leg of step captioning
 
 ``gt`` / ``pred`` are the reference's dicts (or JSON paths).  The category maps are arguments (the reference reads them
 into module globals in ``__main__``, :444-466).  Intervals are flattened to float64 tensors, the per-pair / per-video
 work runs in ``csrc/eval.hip`` in double precision with Python's operation order (identical decisions), and the final
 means are taken on the host in the reference's summation order, so results are equal to the last bit.
 Tensor-level entry points (`interval_iou`, `step_bound_pr`, `preprocess_bounds`) take device tensors directly.
-No CPU fallback.  Caption metrics (CLIPScore / BERTScore / entailment / COCO, :190-320) are out of scope.
+No CPU fallback.  CLIPScore runs as a batch: frames decoded and encoded once on the device, one scoring kernel
+(``csrc/score.hip``); the other caption metrics (BERTScore / entailment / COCO, :190-320) are out of scope.
 """
 from __future__ import annotations
 
 import json
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -215,3 +218,217 @@ def preprocess_moment_bounds(gt_data, pred_data, device=None) -> dict:
         res[v] = dict(pred[v])
         res[v]["bounds"] = out[i, : cnt[i]].tolist()
     return res
+
+
+# ------------------------------------------------------------------------------------------------ CLIPScore (step captioning)
+
+CLIP_SCORE_FRAMES = 4            # evaluate.py:241: np.linspace(start, end - 1, 4)
+CLIP_SCORE_CHUNK = 1024          # unique frames decoded and encoded per round (1024 frames at 360p: 0.7 GB decoded)
+TEXT_BATCH = 1024
+
+
+def _no_frames(frame_dir) -> bool:
+    return frame_dir is None or str(frame_dir) == "None"
+
+
+def _frame_files(frame_dir, video: str) -> List[str]:
+    """evaluate.py:236-237, verbatim: glob, then the integer after the last '_' of the whole path."""
+    from glob import glob
+    frames = glob(f"{frame_dir}/{video}/*.jpg")
+    frames.sort(key=lambda a: int(a.split("_")[-1].replace(".jpg", "")))
+    return frames
+
+
+class ClipScorePlan:
+    """Host-side selection of a CLIPScore run (see ``clip_score_plan``).
+
+    captions    every (video, caption index) of the selected GT videos, in evaluate.py's loop order
+    candidates  the candidate sentence of each caption, lower-cased
+    skip        per caption: True when it gets no score
+    scored      indices into ``captions`` of the scored ones, in order (C of them)
+    sel         int32 [C, 4]: rows of ``frames`` that feed each scored caption, in linspace order (repeats kept)
+    frames      the unique frame files (U), in order of first use
+    tokens      int64 [C, 77] CPU: clip.tokenize of the scored candidates (truncate=False)
+    categories  {category: {"Total": matching videos, "captions": indices into ``captions``}} for the categories evaluate.py
+                reports, in ``_categories`` order
+    """
+
+    def __init__(self, captions, candidates, skip, scored, sel, frames, tokens, categories):
+        self.captions, self.candidates, self.skip, self.scored = captions, candidates, skip, scored
+        self.sel, self.frames, self.tokens, self.categories = sel, frames, tokens, categories
+
+
+def clip_score_plan(gt_data, pred_data, frame_dir, video_to_cat: Optional[Dict[str, str]] = None, per_category: bool = False,
+                    videos: Optional[Sequence[str]] = None, context_length: int = 77) -> ClipScorePlan:
+    """Everything evaluate_moment_summarization (evaluate.py:190-320) decides about CLIPScore before the model runs; host only.
+
+    * categories: ``per_category`` false -> only "all" (evaluate.py:490-491), else those of ``video_to_cat`` plus "all"; a category
+      none of whose matching videos has a caption is left out (:290-291).  ``video_to_cat[video]`` is looked up for every GT video
+      (:219), so a missing video raises KeyError.  ``video_to_cat`` None: only "all", no lookups (the per-caption form).
+    * "Total" counts the matching videos (:222-223), not the captions.
+    * candidate: ``pred[video]["captions"][i]["sentence"].lower()`` (:228); the GT sentence plays no part.  It is tokenized with
+      truncate=False (:243), so a scored candidate of more than 77 tokens raises RuntimeError.
+    * frames: ``glob(f"{frame_dir}/{video}/*.jpg")`` sorted by ``int(path.split("_")[-1].replace(".jpg", ""))`` (:235-237); GT keys
+      carry ".mp4", so that is the directory name.  Listed once per video (the reference re-lists per caption: the same list).
+    * skip: ``start >= n_frames or end >= n_frames`` (:239-241); a missing directory has n_frames = 0 and skips every caption.
+    * frame indices: ``np.linspace(start, min(end, n) - 1, 4).astype(int)`` in float64 (:244), applied to the frame array as numpy
+      indexing does (a negative index counts from the end, as for a one-frame segment start == end); repeats stay.
+    * ``frame_dir`` None or "None": nothing is scored (the guard at :204,236), every category present reports CLIPScore 0.
+    """
+    from .tokenizer import tokenize
+    gt, pred = _load(gt_data), _load(pred_data)
+    no_frames = _no_frames(frame_dir)
+    if videos is None:
+        order = list(gt)
+    else:
+        wanted = set(videos)
+        missing = wanted - set(gt)
+        if missing:
+            raise KeyError(f"videos not in the GT data: {sorted(missing)[:5]}")
+        order = [v for v in gt if v in wanted]
+    cats = _categories(video_to_cat) if (per_category and video_to_cat is not None) else ["all"]
+    members = {c: [] for c in cats}
+    totals = {c: 0 for c in cats}
+    captions, candidates, skip, scored, sel_rows = [], [], [], [], []
+    frames, row_of = [], {}
+    for video in order:
+        video_cat = video_to_cat[video] if video_to_cat is not None else None     # evaluate.py:219, KeyError like VIDEOS_TO_CAT
+        mine = [c for c in cats if c == "all" or c == video_cat]
+        for c in mine:
+            totals[c] += 1
+        files = None
+        for i, d in enumerate(gt[video]["captions"]):
+            k = len(captions)
+            captions.append((video, i))
+            candidates.append(pred[video]["captions"][i]["sentence"].lower())
+            for c in mine:
+                members[c].append(k)
+            if no_frames:
+                skip.append(True)
+                continue
+            if files is None:
+                files = _frame_files(frame_dir, video)
+            n = len(files)
+            if d["start"] >= n or d["end"] >= n:
+                skip.append(True)
+                continue
+            skip.append(False)
+            idxes = np.linspace(d["start"], min(d["end"], n) - 1, CLIP_SCORE_FRAMES).astype(int)
+            row = []
+            for f in np.array(files)[idxes]:
+                f = str(f)
+                if f not in row_of:
+                    row_of[f] = len(frames)
+                    frames.append(f)
+                row.append(row_of[f])
+            scored.append(k)
+            sel_rows.append(row)
+    sel = np.array(sel_rows, dtype=np.int32).reshape(len(sel_rows), CLIP_SCORE_FRAMES)
+    tokens = tokenize([candidates[k] for k in scored], context_length=context_length, truncate=False)
+    categories = {c: {"Total": totals[c], "captions": members[c]} for c in cats if members[c]}
+    return ClipScorePlan(captions, candidates, skip, scored, sel, frames, tokens, categories)
+
+
+def _model_device(model, device):
+    if device is None:
+        device = next(model.parameters()).device
+    return _dev(device)
+
+
+@torch.no_grad()
+def _plan_scores(plan: ClipScorePlan, model, device, chunk: int = CLIP_SCORE_CHUNK, stats: Optional[dict] = None) -> np.ndarray:
+    """The device pipeline of a plan -> float32 [C] scores (host).  Unique frames go in chunks of at most ``chunk``: read, decoded
+    (jpeg.Decoder), resized + cropped per geometry (FramePreprocessor), encoded (CLS head) into one [U, E] buffer; the candidates are
+    encoded in batches of TEXT_BATCH; one hirest_clip_score launch scores every caption.  ``stats`` (a dict): filled with counts,
+    the host-decoded files, and per-stage seconds (each stage is then synchronised, which costs a little overlap)."""
+    import time
+    from . import jpeg
+    from .features import _prepare_frames
+    C, U = len(plan.scored), len(plan.frames)
+    if C == 0:
+        return np.zeros(0, np.float32)
+    timed = stats is not None
+    t = {k: 0.0 for k in ("read_s", "decode_s", "preprocess_s", "image_tower_s", "text_tower_s", "score_s")}
+    fallbacks = []
+
+    def mark(key, t0):
+        if timed:
+            torch.cuda.synchronize(device)
+            t[key] += time.perf_counter() - t0
+        return time.perf_counter()
+    decoder = jpeg.Decoder()
+    emb = None
+    with torch.cuda.device(device):
+        t0 = time.perf_counter()
+        for s in range(0, U, max(1, int(chunk))):
+            files = plan.frames[s:s + chunk]
+            blobs = jpeg._pool_map(jpeg._read, files)
+            t0 = mark("read_s", t0)
+            dec = decoder.decode(blobs, device)
+            fallbacks.extend((files[i], why) for i, why in decoder.last_fallbacks)
+            t0 = mark("decode_s", t0)
+            if isinstance(dec, torch.Tensor):
+                groups = [(None, dec)]
+            else:
+                by_shape = {}
+                for i, f in enumerate(dec):
+                    by_shape.setdefault(tuple(f.shape), []).append(i)
+                groups = [(ids, torch.stack([dec[i] for i in ids])) for ids in by_shape.values()]
+            for ids, frames in groups:
+                x = _prepare_frames(model, frames)
+                t0 = mark("preprocess_s", t0)
+                out = model.encode_image(x)
+                if out.dim() != 2:
+                    raise ValueError("CLIPScore needs the CLS embedding of the pip `clip` package: load the model with pip_head=True")
+                if emb is None:
+                    emb = torch.empty((U, out.shape[1]), dtype=torch.float32, device=device)
+                if ids is None:
+                    emb[s:s + out.shape[0]] = out
+                else:
+                    emb[torch.tensor(ids, device=device) + s] = out.float()
+                t0 = mark("image_tower_s", t0)
+            del dec, groups
+        tok = plan.tokens.to(device)
+        txt = torch.cat([model.encode_text(tok[b:b + TEXT_BATCH]).float() for b in range(0, C, TEXT_BATCH)])
+        t0 = mark("text_tower_s", t0)
+        scores = ops.clip_score(emb, txt, torch.from_numpy(plan.sel))
+        t0 = mark("score_s", t0)
+        host = scores.cpu().numpy()                      # the one device -> host read of the scores
+    if timed:
+        stats.update(t)
+        stats.update(captions=len(plan.captions), scored=C, unique_frames=U, fallbacks=fallbacks)
+    return host
+
+
+def caption_clip_scores(gt_data, pred_data, model, frame_dir, videos: Optional[Sequence[str]] = None, device=None,
+                        stats: Optional[dict] = None) -> List[Tuple[str, int, Optional[float]]]:
+    """Per-caption CLIPScore of evaluate.py:204-262: ``[(video, caption_index, score or None), ...]`` in the reference's loop
+    order; None marks a skipped caption (see ``clip_score_plan`` for the rules).  ``model``: ``clip.load(..., pip_head=True)``."""
+    plan = clip_score_plan(gt_data, pred_data, frame_dir, videos=videos)
+    vals = _plan_scores(plan, model, _model_device(model, device), stats=stats) if plan.scored else []
+    out: List[Tuple[str, int, Optional[float]]] = [(v, i, None) for v, i in plan.captions]
+    for k, s in zip(plan.scored, vals):
+        out[k] = (plan.captions[k][0], plan.captions[k][1], float(s))
+    return out
+
+
+def evaluate_clip_score(gt_data, pred_data, video_to_cat: Dict[str, str], model, frame_dir, per_category: bool = False,
+                        device=None, stats: Optional[dict] = None) -> dict:
+    """The CLIPScore leg of evaluate_moment_summarization (evaluate.py:190-320): ``{category: {"CLIPScore": float, "Total": int}}``.
+
+    The selection rules are ``clip_score_plan``'s.  Every unique frame is decoded and encoded once, every candidate once, and one
+    kernel launch scores all captions; ``CLIPScore`` is ``np.average`` of a category's per-caption Python floats in the reference's
+    order, 0 when it has none (:303-304).  ``model`` is ``hirest_amd.clip.load(..., pip_head=True)``, used at whatever precision the
+    caller set.  The reference runs the pip ``clip`` model in fp16 on CUDA (``clip.load`` applies ``convert_weights`` and casts back
+    to fp32 only on CPU); no precision here reproduces its numbers bit for bit, and ``precision='fp32'`` is the recommended setting
+    for reporting."""
+    plan = clip_score_plan(gt_data, pred_data, frame_dir, video_to_cat, per_category)
+    vals = _plan_scores(plan, model, _model_device(model, device), stats=stats) if plan.scored else []
+    score_of = {k: float(s) for k, s in zip(plan.scored, vals)}
+    results = {}
+    for c, m in plan.categories.items():
+        clip_scores = [score_of[k] for k in m["captions"] if k in score_of]
+        if len(clip_scores) == 0:
+            clip_scores = [0]
+        results[c] = {"CLIPScore": float(np.average(clip_scores)), "Total": m["Total"]}
+    return results

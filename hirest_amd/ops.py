@@ -17,7 +17,7 @@ from ._lib import (EPI_BIAS_BF16, EPI_BIAS_F32, EPI_BIAS_GELU_BF16, EPI_BIAS_QGE
                    EPI_PATCH_POS_F32)
 
 __all__ = ["gemm", "layernorm", "attention", "patchify", "write_cls_rows", "embed_tokens", "to_bf16",
-           "pool_l2norm", "similarity", "topk", "stream_ptr", "on_tensor_device"]
+           "pool_l2norm", "similarity", "topk", "clip_score", "stream_ptr", "on_tensor_device"]
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -263,6 +263,31 @@ def topk(scores: torch.Tensor, k: int, tie_rank: Optional[torch.Tensor] = None):
                                    Q, V, k, idx.data_ptr(), val.data_ptr(), stream_ptr()), "hirest_topk_f32")
     return val, idx
 
+
+
+@on_tensor_device
+def clip_score(img_rows: torch.Tensor, txt_rows: torch.Tensor, sel) -> torch.Tensor:
+    """[C] fp32 CLIPScore (hirest_clip_score): out[c] = mean_j cos(txt_rows[c], img_rows[sel[c, j]]).  img_rows [U, E] and
+    txt_rows [C, E] are fp32 or bf16 GPU tensors; sel is an int [C, K] table (CPU or GPU) whose ids are checked against U here."""
+    lib = _lib.load()
+    if img_rows.dim() != 2 or txt_rows.dim() != 2 or img_rows.shape[1] != txt_rows.shape[1]:
+        raise RuntimeError(f"clip_score: expected [U, E] and [C, E] rows, got {tuple(img_rows.shape)} and {tuple(txt_rows.shape)}")
+    sel = torch.as_tensor(sel)
+    U, E = img_rows.shape
+    C = txt_rows.shape[0]
+    if sel.dim() != 2 or sel.shape[0] != C or sel.shape[1] < 1:
+        raise RuntimeError(f"clip_score: sel must be [C={C}, K>=1], got {tuple(sel.shape)}")
+    if sel.numel() and (int(sel.min()) < 0 or int(sel.max()) >= U):
+        raise RuntimeError(f"clip_score: row ids must lie in [0, {U})")
+    for t, name in ((img_rows, "clip_score.img"), (txt_rows, "clip_score.txt")):
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise RuntimeError(f"{name}: expected fp32 or bf16 rows, got {t.dtype}")
+    out = torch.empty(C, dtype=torch.float32, device=img_rows.device)
+    sel = sel.to(device=img_rows.device, dtype=torch.int32).contiguous()
+    _lib.check(lib.hirest_clip_score(_dev(img_rows, img_rows.dtype, "clip_score.img"), _IN_DTYPES[img_rows.dtype], U,
+                                     _dev(txt_rows, txt_rows.dtype, "clip_score.txt"), _IN_DTYPES[txt_rows.dtype],
+                                     sel.data_ptr(), C, sel.shape[1], E, out.data_ptr(), stream_ptr()), "hirest_clip_score")
+    return out
 
 def to_device(t: torch.Tensor, device) -> torch.Tensor:
     """t.to(device) that does not stall the host when it need not: a pinned CPU tensor (what DataLoader(pin_memory=True) delivers:

@@ -265,6 +265,13 @@ int hirest_topk_f32(const float* scores, const int32_t* tie_rank, int32_t Q, int
 int64_t hirest_topk_workspace_bytes(int32_t Q, int32_t V, int32_t k);
 int hirest_topk_f32_ws(const float* scores, const int32_t* tie_rank, int32_t Q, int32_t V, int32_t k,
                        int32_t* out_index, float* out_score, void* workspace, int64_t workspace_bytes, void* stream);
+/* CLIPScore of C captions (evaluate.py:250-262): out[c] = (1/K) sum_j <t_c, i_j> / (|t_c| |i_j|), t_c = txt_rows[c] and
+ * i_j = img_rows[sel[c*K + j]], rows of E elements, dtype 0 = fp32 / 1 = bf16 (each operand its own).  fp32 accumulation, the
+ * K terms summed in j order: a caption's score depends on its own rows only (not on C or its place in the batch).
+ * sel: device int32 [C, K], every id in [0, U) (an id outside gives NaN for that caption, nothing is read).  HIREST_E_BADARG for a
+ * NULL pointer, another dtype, C < 0, K < 1, E < 1 or U < 1, before anything is enqueued; C == 0 does nothing. */
+int hirest_clip_score(const void* img_rows, int32_t img_dtype, int32_t U, const void* txt_rows, int32_t txt_dtype,
+                      const int32_t* sel, int32_t C, int32_t K, int32_t E, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Whole-tower runners: one call = one forward of a transformer tower over a batch, all
