@@ -9,17 +9,25 @@ timed region; weights are random-init of the real architecture (no checkpoints o
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          N > 1: re-executes itself as N ranks (one per GPU)
     python bench.py ... --dump-outputs DIR                       also writes the last timed step's results as DIR/<name>.npy
+    python bench.py ... --full                                   also runs the legs outside the headline (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` is binding: run directly it starts N ranks under torch.distributed.run (hirest_amd/launch.py) and fails
 loudly when fewer than N GPUs are visible; run under a launcher, WORLD_SIZE must equal N.  The JSON line carries
 `rccl_ranks` = the size of the process group the timed all-gather ran on.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps,
+writes --dump-outputs and prints the line, which carries one extra object:
   roofline      live per-launch timing (hipEvent pairs recorded by the library on the launch
                 stream during the timed steps) of the dominant kernel vs the dense bf16 MFMA peak
-  cpu_baseline  the fp32 CPU oracle (oracle/ref_cpu.py, kind "port") timed on this host on a
-                bounded sample of the same workload (rank 0, N=1 only)
+With --full the line also carries the figures that take runs of their own, after the timed steps:
+  matched_recall  R@k against the real reference's rankings on the pinned C3 sub-corpus, the fp32 and bf16x3
+                  towers on it, the margin-guarded re-rank and its throughput on a synthetic corpus (rank 0)
+  cpu_baseline    the fp32 CPU oracle (oracle/ref_cpu.py, kind "port") timed on this host on a
+                  bounded sample of the same workload (rank 0, N=1 only)
+  secondary       the joint model, captioning, training step and ASR encoder (tools/secondary_bench.py) and
+                  the tower at small call sizes (rank 0, N=1 only)
+--no-matched-recall / --no-cpu-baseline / --no-secondary leave single legs out of a --full run.
 """
 import argparse
 import ctypes
@@ -184,7 +192,7 @@ def matched_recall(model, dev):
 
 def rank_exact_throughput(model, dev, videos=1024, frames=32):
     """Reference-rank retrieval at close to the bf16 towers' speed (retrieval.run_corpus(rank_exact_k=...)): a synthetic
-    corpus of `videos` x `frames` frames (BASELINE configs[2]'s shape, a quarter of its size so the default bench stays short) goes through the
+    corpus of `videos` x `frames` frames (BASELINE configs[2]'s shape, a quarter of its size so the --full run stays short) goes through the
     bf16 tower once; the videos whose place in a query's top k is within twice the measured bf16 score error go through bf16x3 again.
     effective frames/s = corpus frames / (fast pass + measuring eps + re-encoding).  The 4096 x 32 figures (k = 1: 3.7 % re-encoded, 1948
     frames/s, top-1 lists equal to the whole corpus at bf16x3; k = 10: 13 %, 1581) are in profiles/r06/rank_exact_*.json."""
@@ -365,15 +373,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--frames", type=int, default=FRAMES_PER_STEP, help="frames per GPU per step")
     ap.add_argument("--chunk", type=int, default=1024, help="frames per tower call (micro-batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the matched-R@k, CPU-baseline and secondary legs "
+                    "(a plain run reports the headline and its roofline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-baseline leg")
     ap.add_argument("--cpu-frames", type=int, default=4, help="frames per timed pass of the CPU oracle (3 passes per thread count)")
-    ap.add_argument("--no-matched-recall", action="store_true", help="skip the matched-R@k leg (reference-pinned sub-corpus)")
+    ap.add_argument("--no-matched-recall", action="store_true", help="with --full: skip the matched-R@k leg (reference-pinned sub-corpus)")
     ap.add_argument("--gemm-kernel", type=int, default=0, help="0 auto, 1 force t128, 2 force t256 (A/B timing)")
     ap.add_argument("--no-ln-fold", action="store_true", help="A/B: run the LayerNorm passes instead of folding them into the GEMMs")
     ap.add_argument("--no-prune", action="store_true", help="A/B: run the last block on every token (results identical)")
     ap.add_argument("--no-profile", action="store_true", help="A/B: no per-launch hipEvent pairs inside the timed region (the line then "
                     "carries no roofline; profiles/r04/README.md holds the comparison)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the joint-model / captioning / training / ASR figures")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the joint-model / captioning / training / ASR figures")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"), help="nccl = RCCL over xGMI (the measured path); gloo: functional tests")
     ap.add_argument("--share-gpu", action="store_true", help="FUNCTIONAL TEST ONLY (needs --backend gloo): rank r runs on device r %% device_count, "
                     "so the N-rank code path — launcher, timing protocol, gather, rank-0 report — runs on a one-GPU box.  The line is marked INVALID")
@@ -536,11 +546,12 @@ def main():
         if args.gemm_dbg & ~512:                       # bit 9 only switches the kernels' walk direction off (A/B), results unchanged
             out["INVALID"] = f"timing experiment: hirest_gemm_debug_mode({args.gemm_dbg})"
 
-    # ---- matched R@k at EVA-CLIP-g/14 scale (BASELINE.json's "at matched R@1"), outside the timed region, rank 0:
+    # ---- everything below runs with --full only: a plain run ends with the headline line.
+    # matched R@k at EVA-CLIP-g/14 scale (BASELINE.json's "at matched R@1"), outside the timed region, rank 0:
     # the sub-corpus and the 546 real prompts whose rankings the REAL reference produced in the build container
     # (tests/golden/eva_g14_c3.npz, made by tests/golden/make_golden.py gen_c3) are re-encoded here by the same kernels
     # the timed step ran (one >= 64-frame tower call) and ranked; GT(q) = the reference's top-1.
-    if rank == 0 and not args.no_matched_recall:
+    if rank == 0 and args.full and not args.no_matched_recall:
         _log("matched R@k leg: synthetic checkpoint of the reference-pinned sub-corpus")
         out["matched_recall"] = matched_recall(model, dev)
         _log("rank-exact retrieval: margin-guarded re-rank on a synthetic corpus of 32-frame videos")
@@ -548,11 +559,11 @@ def main():
         _log("matched R@k leg done")
 
     # ---- CPU baseline: the fp32 oracle on this host's cores, bounded sample (rank 0, N=1 only)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(model, frames, cfg, args.cpu_frames)
     # ---- the other rows of SURVEY 8 (configs[3], configs[4], f4) at the reference's operating point, outside the timed
     # region, rank 0, N = 1: value + roofline fraction + CPU oracle each (tools/secondary_bench.py)
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         small = small_calls(model, frames)
         del frames
         model.visual._workspace = None

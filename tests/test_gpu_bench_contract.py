@@ -1,5 +1,6 @@
-"""bench.py's output contract (one JSON line with the metric, the live roofline of the dominant kernel and the CPU
-baseline) on a reduced batch, so that a kernel or profile-format change cannot silently break what the driver parses."""
+"""bench.py's output contract (one JSON line with the metric and the live roofline of the dominant kernel; with --full also
+the CPU baseline, matched R@k and the secondary figures) on a reduced batch, so that a kernel or profile-format change
+cannot silently break what the driver parses."""
 import json
 import os
 import subprocess
@@ -16,7 +17,7 @@ def test_bench_line_contract():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "1", "--warmup", "1", "--frames", "256",
-                        "--chunk", "256", "--cpu-frames", "1"], capture_output=True, text=True, timeout=600, cwd=REPO)
+                        "--chunk", "256", "--cpu-frames", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -100,6 +101,25 @@ def test_bench_line_contract():
     tx = sec["train_step_bf16x3"]          # the training step with the encoder blocks' forward / dX products on split operands (csrc/train_block.hip)
     # (no speed gate against train_step: both legs are paced by the host's enqueue rate, which moves by +- 10 % between two runs on one box)
     assert tx["unit"] == "ms/step" and 0 < tx["value"] < 2 * sec["train_step"]["value"] and tx["ms_per_step_with_fused_adamw"] > 0
+
+
+def test_plain_bench_line_is_the_headline_only(tmp_path):
+    """Without --full the run sets up, warms up, times the steps, writes --dump-outputs and prints the line: the headline and the
+    roofline of the timed steps, none of the legs that take runs of their own."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "256",
+                        "--chunk", "256", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("encoded frames/sec") and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] - 2 * 256 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+    assert d["roofline"]["kernel"].startswith("gemm<") and d["roofline"]["launches"] > 0
+    assert not {"cpu_baseline", "matched_recall", "secondary"} & set(d)
+    assert sorted(p.name for p in dump.iterdir()) == ["scores.npy", "topk_indices.npy", "topk_values.npy", "video_rows.npy"]
 
 
 def test_bench_gpus_flag_is_binding():

@@ -4,7 +4,7 @@
 out=gpurun_out/final; mkdir -p $out; export TMPDIR=/tmp
 ( time timeout 2400 python -m pytest tests -m gpu -q ) > $out/pytest_gpu.log 2>&1; tail -6 $out/pytest_gpu.log
 timeout 300 python __graft_entry__.py smoke > $out/smoke.log 2>&1; tail -1 $out/smoke.log
-( time timeout 1200 python bench.py > $out/bench_n1.json 2> $out/bench.err ) 2>&1 | grep real; cut -c1-300 $out/bench_n1.json
+( time timeout 1200 python bench.py --full > $out/bench_n1.json 2> $out/bench.err ) 2>&1 | grep real; cut -c1-300 $out/bench_n1.json
 ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$out/prof -o r -- \
     python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-matched-recall --no-secondary > $GRAFT_REPO_ROOT/$out/bench_under_rocprofv3.json 2> $GRAFT_REPO_ROOT/$out/prof.err )
 f=$(find $out/prof -name "*kernel_stats.csv" | head -1); cp "$f" $out/rocprofv3_kernel_stats_bench.csv; head -8 $out/rocprofv3_kernel_stats_bench.csv | cut -c1-150

@@ -4,7 +4,7 @@ the joint model's moment retrieval / moment segmentation / step captioning, its 
 each at the reference's own operating point (B = 5 = scripts/run.sh:14, T = 300 frames; beam 3 and 5, 48 words), each with
 its roofline fraction and with the CPU oracle timed beside it on this host.
 
-``bench.py`` calls ``measure()`` outside its timed region (rank 0, N = 1) and prints the result as the ``secondary`` object
+``bench.py --full`` calls ``measure()`` outside its timed region (rank 0, N = 1) and prints the result as the ``secondary`` object
 of its JSON line; ``python tools/secondary_bench.py`` prints the same object on its own (profiles/rNN/secondary.json).
 
 The reference's published speeds for these paths are val_inference_and_evaluation.ipynb:708,713,716 (T4): 38 videos/s
