@@ -578,8 +578,9 @@ __global__ void heads_bwd_kernel(const float* __restrict__ dl, int64_t rows, int
 }
 
 // cross-entropy over frames of masked logits (modeling.py:343-344: logits[mask == 0] = -finfo.max, then F.cross_entropy with
-// mean reduction): one wave per sample.  *loss += weight * (lse - logit[target]) / B;  dlogits = weight (softmax - onehot) / B on
-// the frames of the moment, 0 outside (the in-place fill cuts their gradient).
+// mean reduction): one wave per sample.  *loss += weight * ((mx - logit[target]) + log(sum)) / B;  dlogits = weight (softmax - onehot) / B
+// on the frames of the moment, 0 outside (the in-place fill cuts their gradient).  The loss is not formed as lse - logit[target]:
+// for a sample whose mask row is all zero mx = -finfo.max absorbs log(T) in lse, where torch's log_softmax returns log(T).
 __global__ __launch_bounds__(64) void ce_masked_kernel(const float* __restrict__ logits, const int32_t* __restrict__ mask,
                                                        const int32_t* __restrict__ target, int B, int T, float weight,
                                                        float* __restrict__ loss, float* __restrict__ dlogits) {
@@ -593,14 +594,15 @@ __global__ __launch_bounds__(64) void ce_masked_kernel(const float* __restrict__
     float sum = 0.f;
     for (int t = lane; t < T; t += 64) sum += __expf((mr[t] ? lr[t] : NEG) - mx);
     sum = wave_sum_x(sum);
-    const float lse = mx + __logf(sum);
+    const float lsum = __logf(sum);
+    const float lse = mx + lsum;
     const int tg = target[b];
     for (int t = lane; t < T; t += 64) {
         const float x = mr[t] ? lr[t] : NEG;
         const float p = __expf(x - lse);
         dlogits[(int64_t)b * T + t] = mr[t] ? weight * (p - (t == tg ? 1.f : 0.f)) / B : 0.f;
     }
-    if (lane == 0) atomicAdd(loss, weight * (lse - (mr[tg] ? lr[tg] : NEG)) / B);
+    if (lane == 0) atomicAdd(loss, weight * ((mx - (mr[tg] ? lr[tg] : NEG)) + lsum) / B);
 }
 
 inline dim3 grid1(int64_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }

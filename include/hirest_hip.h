@@ -731,7 +731,8 @@ int hirest_joint_base_bwd_f32(const float* dbase, const float* v, const float* t
 /* backward of tn = t / |t| (modeling.py:162) */
 int hirest_l2norm_bwd_f32(const float* t, const float* dtn, float* dt, int32_t B, int32_t E, void* stream);
 /* *loss_accum += weight * mean_b CE(softmax over the frames with mask[b,t] != 0, target[b]); dlogits = its gradient, 0 on masked
- * frames (modeling.py:343-344: logits[moment_mask == 0] = -finfo.max; F.cross_entropy) */
+ * frames (modeling.py:343-344: logits[moment_mask == 0] = -finfo.max; F.cross_entropy).  A sample whose mask row is all zero adds
+ * log(T), as torch does (every frame then holds -finfo.max). */
 int hirest_ce_masked_f32(const float* logits, const int32_t* mask, const int32_t* target, int32_t B, int32_t T, float weight,
                          float* loss_accum, float* dlogits, void* stream);
 /* dfeats[r] = sum_h dlogits[h*rows + r] * w_h   (backward of hirest_linear_heads with respect to its input) */

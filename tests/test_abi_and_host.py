@@ -112,6 +112,123 @@ def test_argument_errors_without_gpu(lib):
     assert lib.hirest_train_fusion_backward_scratch_bytes(ctypes.byref(tf)) == 0               # longer than the position table
 
 
+def test_train_entry_points_refuse_bad_arguments_without_gpu(lib):
+    """Every entry point of csrc/train.hip checks its arguments before any launch: NULL pointers and non-positive sizes give
+    HIREST_E_BADARG (-1), an unsupported head size or dropout rate HIREST_E_SHAPE (-2).  The placeholder pointers X are never
+    dereferenced: each call below is refused by its checks alone."""
+    X = 1 << 20
+    BAD, SHAPE = -1, -2
+    # transpose_pad(in, ld, R, C, out, Rp): Rp < R
+    assert lib.hirest_transpose_pad_f32(None, 8, 2, 2, X, 2, None) == BAD
+    assert lib.hirest_transpose_pad_f32(X, 8, 2, 2, None, 2, None) == BAD
+    assert lib.hirest_transpose_pad_f32(X, 8, 0, 2, X, 2, None) == BAD
+    assert lib.hirest_transpose_pad_f32(X, 8, 2, 0, X, 2, None) == BAD
+    assert lib.hirest_transpose_pad_f32(X, 8, 4, 2, X, 3, None) == BAD
+    # weighted_colsum(x, ldx, w, sel, value, R, C, out)
+    assert lib.hirest_weighted_colsum_f32(None, 8, None, None, 0, 2, 2, X, None) == BAD
+    assert lib.hirest_weighted_colsum_f32(X, 8, None, None, 0, 2, 2, None, None) == BAD
+    assert lib.hirest_weighted_colsum_f32(X, 8, None, None, 0, 0, 2, X, None) == BAD
+    assert lib.hirest_weighted_colsum_f32(X, 8, None, None, 0, 2, -1, X, None) == BAD
+    # scale_by_device_scalar(x, scalar, n)
+    assert lib.hirest_scale_by_device_scalar_f32(None, X, 4, None) == BAD
+    assert lib.hirest_scale_by_device_scalar_f32(X, None, 4, None) == BAD
+    assert lib.hirest_scale_by_device_scalar_f32(X, X, 0, None) == BAD
+    # act(pre, y, n, act): 0..2 forward; act_bwd(pre, dy, dx, n, act): 0..3
+    assert lib.hirest_act_f32(None, X, 4, 1, None) == BAD and lib.hirest_act_f32(X, None, 4, 1, None) == BAD
+    assert lib.hirest_act_f32(X, X, 0, 1, None) == BAD
+    assert lib.hirest_act_f32(X, X, 4, -1, None) == BAD and lib.hirest_act_f32(X, X, 4, 3, None) == BAD
+    assert lib.hirest_act_bwd_f32(None, X, X, 4, 1, None) == BAD and lib.hirest_act_bwd_f32(X, None, X, 4, 1, None) == BAD
+    assert lib.hirest_act_bwd_f32(X, X, None, 4, 1, None) == BAD and lib.hirest_act_bwd_f32(X, X, X, -3, 1, None) == BAD
+    assert lib.hirest_act_bwd_f32(X, X, X, 4, -1, None) == BAD and lib.hirest_act_bwd_f32(X, X, X, 4, 4, None) == BAD
+    # dropout_add(x, resid, y, n, p, seed): 0 <= p < 1
+    assert lib.hirest_dropout_add_f32(None, None, X, 4, 0.1, 0, None) == BAD
+    assert lib.hirest_dropout_add_f32(X, None, None, 4, 0.1, 0, None) == BAD
+    assert lib.hirest_dropout_add_f32(X, None, X, 0, 0.1, 0, None) == BAD
+    for p in (1.0, 1.5, -0.1, float("nan")):
+        assert lib.hirest_dropout_add_f32(X, None, X, 4, p, 0, None) == BAD, p
+    # layernorm_bwd(x, dy, gamma, eps, dx, dyxhat, R, D)
+    for i in range(5):
+        ptrs = [X] * 5
+        ptrs[i] = None
+        assert lib.hirest_layernorm_bwd_f32(ptrs[0], ptrs[1], ptrs[2], 1e-12, ptrs[3], ptrs[4], 4, 768, None) == BAD, i
+    assert lib.hirest_layernorm_bwd_f32(X, X, X, 1e-12, X, X, 0, 768, None) == BAD
+    assert lib.hirest_layernorm_bwd_f32(X, X, X, 1e-12, X, X, 4, 0, None) == BAD
+    # attention, general form: fwd(q, ldq, k, v, ldkv, mask, P, ctx, ldctx, B, Tq, Tk, H, dh, scale, add_const, drop, seed)
+    fwd = lambda q, k, v, P, c, B, Tq, Tk, H, dh, drop: lib.hirest_attention_train_fwd_qkv_f32(
+        q, 768, k, v, 1536, None, P, c, 768, B, Tq, Tk, H, dh, 0.125, 0.0, drop, 0, None)
+    for i in range(5):
+        ptrs = [X] * 5
+        ptrs[i] = None
+        assert fwd(*ptrs, 2, 3, 5, 12, 64, 0.1) == BAD, i
+    for dims in ((0, 3, 5, 12), (2, 0, 5, 12), (2, 3, 0, 12), (2, 3, 5, 0)):
+        assert fwd(X, X, X, X, X, *dims, 64, 0.1) == BAD, dims
+    assert fwd(X, X, X, X, X, 2, 3, 5, 12, 32, 0.1) == SHAPE and fwd(X, X, X, X, X, 2, 3, 5, 12, 128, 0.0) == SHAPE
+    assert fwd(X, X, X, X, X, 2, 3, 5, 12, 64, 1.0) == SHAPE and fwd(X, X, X, X, X, 2, 3, 5, 12, 64, -0.5) == SHAPE
+    # bwd(q, ldq, k, v, ldkv, P, dctx, ldctx, dS, dq, lddq, dk, dv, lddkv, B, Tq, Tk, H, dh, scale, drop, seed)
+    bwd = lambda ptrs, B, Tq, Tk, H, dh, drop: lib.hirest_attention_train_bwd_qkv_f32(
+        ptrs[0], 768, ptrs[1], ptrs[2], 1536, ptrs[3], ptrs[4], 768, ptrs[5], ptrs[6], 768, ptrs[7], ptrs[8], 1536, B, Tq, Tk, H, dh, 0.125,
+        drop, 0, None)
+    for i in range(9):
+        ptrs = [X] * 9
+        ptrs[i] = None
+        assert bwd(ptrs, 2, 3, 5, 12, 64, 0.1) == BAD, i
+    for dims in ((0, 3, 5, 12), (2, -1, 5, 12), (2, 3, 0, 12), (2, 3, 5, 0)):
+        assert bwd([X] * 9, *dims, 64, 0.1) == BAD, dims
+    assert bwd([X] * 9, 2, 3, 5, 12, 80, 0.1) == SHAPE and bwd([X] * 9, 2, 3, 5, 12, 64, 1.0) == SHAPE
+    # packed self-attention forms
+    assert lib.hirest_attention_train_fwd_f32(None, X, X, 2, 5, 12, 64, 0.125, 0.0, 0.1, 0, None) == BAD
+    assert lib.hirest_attention_train_fwd_f32(X, X, X, 2, 5, 12, 96, 0.125, 0.0, 0.1, 0, None) == SHAPE
+    assert lib.hirest_attention_train_fwd_f32(X, X, X, 2, 5, 12, 64, 0.125, 0.0, 1.0, 0, None) == SHAPE
+    assert lib.hirest_attention_train_bwd_f32(X, X, X, X, None, 2, 5, 12, 64, 0.125, 0.1, 0, None) == BAD
+    assert lib.hirest_attention_train_bwd_f32(None, X, X, X, X, 2, 5, 12, 64, 0.125, 0.1, 0, None) == BAD
+    assert lib.hirest_attention_train_bwd_f32(X, X, X, X, X, 2, 5, 12, 16, 0.125, 0.1, 0, None) == SHAPE
+    assert lib.hirest_attention_train_select(2) == BAD and lib.hirest_attention_train_select(-1) == BAD
+    # gemm_f32_strided(A, sam, sak, B, sbn, sbk, C, ldc, M, N, K, alpha): one stride of each pair must be 1
+    gs = lambda A, sam, sak, B, sbn, sbk, C, M, N, K: lib.hirest_gemm_f32_strided(A, sam, sak, B, sbn, sbk, C, 64, M, N, K, 1.0, None)
+    assert gs(None, 64, 1, X, 64, 1, X, 8, 8, 8) == BAD and gs(X, 64, 1, None, 64, 1, X, 8, 8, 8) == BAD
+    assert gs(X, 64, 1, X, 64, 1, None, 8, 8, 8) == BAD
+    for dims in ((0, 8, 8), (8, 0, 8), (8, 8, 0), (-8, 8, 8)):
+        assert gs(X, 64, 1, X, 64, 1, X, *dims) == BAD, dims
+    assert gs(X, 64, 2, X, 64, 1, X, 8, 8, 8) == SHAPE and gs(X, 64, 1, X, 3, 5, X, 8, 8, 8) == SHAPE
+    # embeddings
+    assert lib.hirest_embedding_fwd_f32(None, X, X, X, 4, 2, 8, None) == BAD and lib.hirest_embedding_fwd_f32(X, None, X, X, 4, 2, 8, None) == BAD
+    assert lib.hirest_embedding_fwd_f32(X, X, None, X, 4, 2, 8, None) == BAD and lib.hirest_embedding_fwd_f32(X, X, X, None, 4, 2, 8, None) == BAD
+    for dims in ((0, 2, 8), (4, 0, 8), (4, 2, 0)):
+        assert lib.hirest_embedding_fwd_f32(X, X, X, X, *dims, None) == BAD, dims
+    assert lib.hirest_embedding_pos_fwd_f32(X, None, X, X, X, 4, 8, None) == BAD
+    assert lib.hirest_embedding_pos_fwd_f32(X, X, X, X, X, 0, 8, None) == BAD and lib.hirest_embedding_pos_fwd_f32(X, X, X, X, X, 4, 0, None) == BAD
+    assert lib.hirest_embedding_bwd_f32(None, X, X, 4, 8, None) == BAD and lib.hirest_embedding_bwd_f32(X, X, None, 4, 8, None) == BAD
+    assert lib.hirest_embedding_bwd_f32(X, X, X, 0, 8, None) == BAD and lib.hirest_embedding_bwd_f32(X, X, X, 4, 0, None) == BAD
+    # ce_rows(logits, ld, target, R, V, weight, n_valid, loss, dlogits): ld >= V
+    ce = lambda lg, ld, tg, R, V, ls, dl: lib.hirest_ce_rows_f32(lg, ld, tg, R, V, 1.0, 2, ls, dl, None)
+    assert ce(X, 10, X, 2, 11, X, X) == BAD
+    assert ce(None, 16, X, 2, 11, X, X) == BAD and ce(X, 16, None, 2, 11, X, X) == BAD
+    assert ce(X, 16, X, 2, 11, None, X) == BAD and ce(X, 16, X, 2, 11, X, None) == BAD
+    assert ce(X, 16, X, 0, 11, X, X) == BAD and ce(X, 16, X, 2, 0, X, X) == BAD
+    # masked losses (logits, target|mask, mask|target, B, T, weight, loss, dlogits)
+    for fn in (lib.hirest_bce_masked_f32, lib.hirest_ce_masked_f32):
+        for i in range(5):
+            ptrs = [X] * 5
+            ptrs[i] = None
+            assert fn(ptrs[0], ptrs[1], ptrs[2], 2, 5, 1.0, ptrs[3], ptrs[4], None) == BAD, (fn, i)
+        assert fn(X, X, X, 0, 5, 1.0, X, X, None) == BAD and fn(X, X, X, 2, 0, 1.0, X, X, None) == BAD
+    # fusion backward pieces
+    for i in range(5):
+        ptrs = [X] * 5
+        ptrs[i] = None
+        assert lib.hirest_joint_base_bwd_f32(*ptrs, 2, 5, 8, None) == BAD, i
+    for dims in ((0, 5, 8), (2, 0, 8), (2, 5, 0)):
+        assert lib.hirest_joint_base_bwd_f32(X, X, X, X, X, *dims, None) == BAD, dims
+    assert lib.hirest_l2norm_bwd_f32(None, X, X, 2, 8, None) == BAD and lib.hirest_l2norm_bwd_f32(X, None, X, 2, 8, None) == BAD
+    assert lib.hirest_l2norm_bwd_f32(X, X, None, 2, 8, None) == BAD
+    assert lib.hirest_l2norm_bwd_f32(X, X, X, 0, 8, None) == BAD and lib.hirest_l2norm_bwd_f32(X, X, X, 2, 0, None) == BAD
+    # heads_bwd(dlogits, rows, D, nheads, w0, w1, w2, dfeats): 1 <= nheads <= 3
+    hb = lambda dl, rows, D, nh, w0, out: lib.hirest_heads_bwd_f32(dl, rows, D, nh, w0, X, X, out, None)
+    assert hb(X, 4, 8, 0, X, X) == BAD and hb(X, 4, 8, 4, X, X) == BAD
+    assert hb(None, 4, 8, 1, X, X) == BAD and hb(X, 4, 8, 1, None, X) == BAD and hb(X, 4, 8, 1, X, None) == BAD
+    assert hb(X, 0, 8, 1, X, X) == BAD and hb(X, 4, 0, 1, X, X) == BAD
+
+
 def test_workspace_size_formula(lib):
     from hirest_amd import _lib
     t = _lib.VisionTower()
