@@ -2024,7 +2024,7 @@ extern "C" int hirest_log_softmax_f32(const float* x, int64_t ldx, const float* 
 
 extern "C" int hirest_joint_time_features(const int32_t* n_valid, const float* w1, const float* b1, float* tin, int32_t B,
                                           int32_t T, int32_t E, void* stream) {
-    if (!n_valid || !w1 || !b1 || !tin || B <= 0 || T <= 0 || E % 4 != 0) return HIREST_E_BADARG;
+    if (!n_valid || !w1 || !b1 || !tin || B <= 0 || T <= 0 || E <= 0 || E % 4 != 0) return HIREST_E_BADARG;
     hipLaunchKernelGGL(joint_time_kernel, dim3(grid1d((int64_t)B * T * (E / 4))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        n_valid, w1, b1, tin, B, T, E);
     return hirest_launch_status();
@@ -2039,7 +2039,7 @@ extern "C" int hirest_joint_time_grid_f32(const int32_t* n_valid, int32_t B, int
 
 extern "C" int hirest_joint_base(const float* v, const float* text_proj, const float* asr, const float* temporal, float* base,
                                  int32_t B, int32_t T, int32_t E, void* stream) {
-    if (!v || !text_proj || !asr || !temporal || !base || B <= 0 || T <= 0 || E % 4 != 0) return HIREST_E_BADARG;
+    if (!v || !text_proj || !asr || !temporal || !base || B <= 0 || T <= 0 || E <= 0 || E % 4 != 0) return HIREST_E_BADARG;
     hipLaunchKernelGGL(joint_base_kernel, dim3((T + 15) / 16, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), v, text_proj,
                        asr, temporal, base, B, T, E);
     return hirest_launch_status();
@@ -2048,7 +2048,7 @@ extern "C" int hirest_joint_base(const float* v, const float* text_proj, const f
 extern "C" int hirest_joint_mask_add(const float* base, const int32_t* moment_mask, const int32_t* boundary_mask,
                                      const float* mask_embed, const float* boundary_embed, float* f, int64_t rows, int32_t E,
                                      void* stream) {
-    if (!base || !moment_mask || !mask_embed || !f || rows <= 0 || E % 4 != 0) return HIREST_E_BADARG;
+    if (!base || !moment_mask || !mask_embed || !f || rows <= 0 || E <= 0 || E % 4 != 0) return HIREST_E_BADARG;
     if (boundary_mask && !boundary_embed) return HIREST_E_BADARG;
     hipLaunchKernelGGL(joint_mask_add_kernel, dim3(grid1d(rows * (E / 4))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), base,
                        moment_mask, boundary_mask, mask_embed, boundary_embed, f, rows, E);
@@ -2057,7 +2057,8 @@ extern "C" int hirest_joint_mask_add(const float* base, const int32_t* moment_ma
 
 extern "C" int hirest_linear_heads(const float* x, int64_t rows, int32_t D, int32_t nheads, const float* w0, const float* w1,
                                    const float* w2, const float* bias3, float* logits, void* stream) {
-    if (!x || !w0 || !bias3 || !logits || rows <= 0 || nheads < 1 || nheads > 3 || D % 4 != 0) return HIREST_E_BADARG;
+    if (!x || !w0 || !bias3 || !logits || rows <= 0 || nheads < 1 || nheads > 3 || D <= 0 || D % 4 != 0) return HIREST_E_BADARG;
+    if ((nheads > 1 && !w1) || (nheads > 2 && !w2)) return HIREST_E_BADARG;     // (a missing weight is not head 0's)
     hipLaunchKernelGGL(heads_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, rows, D,
                        nheads, w0, w1 ? w1 : w0, w2 ? w2 : w0, bias3, logits);
     return hirest_launch_status();

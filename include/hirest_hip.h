@@ -540,20 +540,24 @@ int hirest_attention_f32_varlen(const float* qkv, float* out, const int32_t* seq
 /* out[r][:] = log_softmax(x[r][:]) + row_add[r]  (train.py:563-564 + the beam score add of beam.py:76); row_add may be NULL */
 int hirest_log_softmax_f32(const float* x, int64_t ldx, const float* row_add, float* out, int64_t ldo, int32_t rows,
                            int32_t V, void* stream);
-/* tin[b,t,:] = tanh(time(b,t)*w1 + b1), time = (linspace(0,1,n_valid[b])[t]-0.5)*2, 0 past n_valid (modeling.py:176-195) */
+/* tin[b,t,:] = tanh(time(b,t)*w1 + b1), time = (linspace(0,1,n_valid[b])[t]-0.5)*2, 0 past n_valid (modeling.py:176-195).
+ * B, T > 0, E > 0 and E % 4 == 0, else HIREST_E_BADARG. */
 int hirest_joint_time_features(const int32_t* n_valid, const float* w1, const float* b1, float* tin,
                                int32_t B, int32_t T, int32_t E, void* stream);
 /* grid[b][t] = that time(b,t) itself, [B, T] fp32: the per-row weight of temporal_embed.0.weight's gradient (a column sum of
  * d pre-activation * time), built on the device so that the training step never reads n_valid back (modeling.py:176-193) */
 int hirest_joint_time_grid_f32(const int32_t* n_valid, int32_t B, int32_t T, float* grid, void* stream);
-/* base = v * (text_proj/||text_proj||)[:,None,:] + asr + temporal   (modeling.py:163-195, loop invariant) */
+/* base = v * (text_proj/||text_proj||)[:,None,:] + asr + temporal   (modeling.py:163-195, loop invariant).
+ * B, T > 0, E > 0 and E % 4 == 0, else HIREST_E_BADARG. */
 int hirest_joint_base(const float* v, const float* text_proj, const float* asr, const float* temporal, float* base,
                       int32_t B, int32_t T, int32_t E, void* stream);
-/* f = base (+ boundary_embed[boundary_mask]) + mask_embed[moment_mask]   (modeling.py:171-173,197-198) */
+/* f = base (+ boundary_embed[boundary_mask]) + mask_embed[moment_mask]   (modeling.py:171-173,197-198), added in that order.
+ * boundary_mask may be NULL (then boundary_embed is unused); rows > 0, E > 0 and E % 4 == 0, else HIREST_E_BADARG. */
 int hirest_joint_mask_add(const float* base, const int32_t* moment_mask, const int32_t* boundary_mask,
                           const float* mask_embed, const float* boundary_embed, float* f, int64_t rows, int32_t E,
                           void* stream);
-/* up to three Linear(D,1) heads: logits[h*rows + r] = <x[r], w_h> + bias3[h] */
+/* up to three Linear(D,1) heads: logits[h*rows + r] = <x[r], w_h> + bias3[h], h < nheads.  1 <= nheads <= 3, w1 (w2) required
+ * from 2 (3) heads on and unused below, rows > 0, D > 0 and D % 4 == 0, else HIREST_E_BADARG. */
 int hirest_linear_heads(const float* x, int64_t rows, int32_t D, int32_t nheads, const float* w0, const float* w1,
                         const float* w2, const float* bias3, float* logits, void* stream);
 /* ------------------------------------------------------------------------------------
@@ -742,7 +746,9 @@ int hirest_heads_bwd_f32(const float* dlogits, int64_t rows, int32_t D, int32_t 
 /* out[b] = argmax_t (mask[b,t] ? logits[b,t] : fill), first maximum (modeling.py:294-298) */
 int hirest_masked_argmax(const float* logits, const int32_t* mask, float fill, int32_t B, int32_t T, int32_t* out,
                          void* stream);
-/* one iteration of test_moment_segmentation's loop body for all samples, on device (modeling.py:393-433) */
+/* one iteration of test_moment_segmentation's loop body for all samples, on device (modeling.py:393-433).  A sample whose
+ * nsteps[b] has reached max_steps still has its masks updated; nothing is appended to its steps [B, max_steps, 2].
+ * 1 <= T <= 16384 (the row's probabilities are staged in 64 KiB of LDS), else HIREST_E_BADARG. */
 int hirest_segmentation_step(const float* logits, int32_t* moment_mask, int32_t* boundary_mask, int32_t B, int32_t T,
                              double threshold, int32_t* steps, int32_t* nsteps, int32_t max_steps, float* probs_out,
                              void* stream);

@@ -375,3 +375,113 @@ def test_profiled_kernels_are_the_dispatched_ones(lib):
     for retired in (10, 17, 18, 20):                                      # the 4-wave kernel (round 2) and gemm_d2 (round 3)
         assert lib.hirest_gemm_select_kernel(retired) != 0
     lib.hirest_gemm_select_kernel(0)
+
+
+def test_joint_inference_entry_points_refuse_bad_arguments_without_gpu(lib):
+    """The inference entry points of the joint model (csrc/joint.hip, csrc/caption.hip) check their arguments before any launch:
+    NULL pointers, non-positive sizes, E or D not a positive multiple of 4, nheads outside 1..3 or a missing weight of a used head,
+    T > 16384 for segmentation_step, a beam wider than 16 for the tail and a decode step without any key give HIREST_E_BADARG (-1);
+    an attention head width that is not a multiple of 4 up to 96 and row strides that are not multiples of 4 HIREST_E_SHAPE (-2).
+    The placeholder pointers X are never dereferenced: each call below is refused by its checks alone."""
+    X = 1 << 20
+    BAD, SHAPE, WS = -1, -2, -3
+    # joint_time_grid(n_valid, B, T, grid)
+    assert lib.hirest_joint_time_grid_f32(X, 5, 300, None, None) == BAD
+    assert lib.hirest_joint_time_grid_f32(X, 0, 300, X, None) == BAD and lib.hirest_joint_time_grid_f32(X, 5, 0, X, None) == BAD
+    # joint_time_features(n_valid, w1, b1, tin, B, T, E)
+    for i in range(4):
+        ptrs = [X] * 4
+        ptrs[i] = None
+        assert lib.hirest_joint_time_features(*ptrs, 2, 300, 512, None) == BAD, i
+    for dims in ((0, 300, 512), (2, 0, 512), (2, 300, 0), (2, 300, 514), (2, 300, -4)):
+        assert lib.hirest_joint_time_features(X, X, X, X, *dims, None) == BAD, dims
+    # joint_base(v, text_proj, asr, temporal, base, B, T, E)
+    for i in range(5):
+        ptrs = [X] * 5
+        ptrs[i] = None
+        assert lib.hirest_joint_base(*ptrs, 2, 300, 512, None) == BAD, i
+    for dims in ((0, 300, 512), (2, 0, 512), (2, 300, 0), (2, 300, 6), (2, 300, -8)):
+        assert lib.hirest_joint_base(X, X, X, X, X, *dims, None) == BAD, dims
+    # joint_mask_add(base, moment_mask, boundary_mask, mask_embed, boundary_embed, f, rows, E): a boundary mask needs its table
+    for i in (0, 1, 3, 5):
+        ptrs = [X] * 6
+        ptrs[i] = None
+        assert lib.hirest_joint_mask_add(*ptrs, 600, 512, None) == BAD, i
+    assert lib.hirest_joint_mask_add(X, X, X, X, None, X, 600, 512, None) == BAD
+    for rows, E in ((0, 512), (600, 0), (600, 510), (600, -4)):
+        assert lib.hirest_joint_mask_add(X, X, None, X, None, X, rows, E, None) == BAD, (rows, E)
+    # linear_heads(x, rows, D, nheads, w0, w1, w2, bias3, logits)
+    lh = lambda x, rows, D, nh, w0, w1, w2, b, out: lib.hirest_linear_heads(x, rows, D, nh, w0, w1, w2, b, out, None)
+    assert lh(None, 4, 8, 1, X, None, None, X, X) == BAD and lh(X, 4, 8, 1, None, None, None, X, X) == BAD
+    assert lh(X, 4, 8, 1, X, None, None, None, X) == BAD and lh(X, 4, 8, 1, X, None, None, X, None) == BAD
+    assert lh(X, 4, 8, 0, X, X, X, X, X) == BAD and lh(X, 4, 8, 4, X, X, X, X, X) == BAD
+    assert lh(X, 4, 8, 2, X, None, X, X, X) == BAD and lh(X, 4, 8, 3, X, X, None, X, X) == BAD
+    assert lh(X, 0, 8, 1, X, None, None, X, X) == BAD and lh(X, 4, 0, 1, X, None, None, X, X) == BAD
+    assert lh(X, 4, 6, 1, X, None, None, X, X) == BAD and lh(X, 4, -4, 1, X, None, None, X, X) == BAD
+    # masked_argmax(logits, mask, fill, B, T, out)
+    assert lib.hirest_masked_argmax(None, X, -1e10, 2, 300, X, None) == BAD and lib.hirest_masked_argmax(X, None, -1e10, 2, 300, X, None) == BAD
+    assert lib.hirest_masked_argmax(X, X, -1e10, 2, 300, None, None) == BAD
+    assert lib.hirest_masked_argmax(X, X, -1e10, 0, 300, X, None) == BAD and lib.hirest_masked_argmax(X, X, -1e10, 2, 0, X, None) == BAD
+    # segmentation_step(logits, moment_mask, boundary_mask, B, T, threshold, steps, nsteps, max_steps, probs_out)
+    seg = lambda lg, mm, bm, B, T, st, ns: lib.hirest_segmentation_step(lg, mm, bm, B, T, 0.5, st, ns, 20, None, None)
+    for i in range(5):
+        ptrs = [X] * 5
+        ptrs[i] = None
+        assert seg(ptrs[0], ptrs[1], ptrs[2], 2, 300, ptrs[3], ptrs[4]) == BAD, i
+    assert seg(X, X, X, 0, 300, X, X) == BAD and seg(X, X, X, 2, 0, X, X) == BAD
+    assert seg(X, X, X, 2, 16385, X, X) == BAD
+    # attention_f32(qkv, out, B, T, H, dh) / attention_f32_varlen(qkv, out, seq_off, B, max_len, H, dh)
+    af = lambda q, o, B, T, H, dh: lib.hirest_attention_f32(q, o, B, T, H, dh, 0.125, 0.0, None)
+    assert af(None, X, 1, 64, 2, 64) == BAD and af(X, None, 1, 64, 2, 64) == BAD
+    assert af(X, X, 0, 64, 2, 64) == BAD and af(X, X, 1, 0, 2, 64) == BAD and af(X, X, 1, 64, 0, 64) == BAD
+    for dh in (0, -4, 6, 100):
+        assert af(X, X, 1, 64, 2, dh) == SHAPE, dh
+    av = lambda q, o, so, B, L, dh: lib.hirest_attention_f32_varlen(q, o, so, B, L, 12, dh, 0.125, 0.0, None)
+    assert av(X, X, None, 3, 40, 32) == BAD and av(X, None, X, 3, 40, 32) == BAD
+    assert av(X, X, X, 0, 40, 32) == BAD and av(X, X, X, 3, 0, 32) == BAD
+    assert av(X, X, X, 3, 40, 30) == SHAPE and av(X, X, X, 3, 40, 128) == SHAPE
+    # attention_f32_qkv(q, ldq, k, v, ldkv, out, B, Tq, Tk, H, dh, scale, add_const, causal_penalty)
+    aq = lambda q, ldq, k, v, ldkv, o, B, Tq, Tk, H, dh: lib.hirest_attention_f32_qkv(q, ldq, k, v, ldkv, o, B, Tq, Tk, H, dh, 0.125, 0.0,
+                                                                                      -1e30, None)
+    for i in range(4):
+        ptrs = [X] * 4
+        ptrs[i] = None
+        assert aq(ptrs[0], 128, ptrs[1], ptrs[2], 256, ptrs[3], 1, 17, 300, 2, 64) == BAD, i
+    for dims in ((0, 17, 300, 2), (1, 0, 300, 2), (1, 17, 0, 2), (1, 17, 300, 0)):
+        assert aq(X, 128, X, X, 256, X, *dims, 64) == BAD, dims
+    assert aq(X, 130, X, X, 256, X, 1, 17, 300, 2, 64) == SHAPE and aq(X, 128, X, X, 258, X, 1, 17, 300, 2, 64) == SHAPE
+    assert aq(X, 128, X, X, 256, X, 1, 17, 300, 2, 66) == SHAPE and aq(X, 256, X, X, 512, X, 1, 17, 300, 2, 100) == SHAPE
+    # attention_f32_decode(q, ldq, k_hist, v_hist, ld_hist, parent, t_hist, k_new, v_new, ld_new, k_out, v_out, out, R, H)
+    ad = lambda q, ldq, kh, vh, ldh, th, kn, vn, ldn, ko, vo, o, R, H: lib.hirest_attention_f32_decode(
+        q, ldq, kh, vh, ldh, None, th, kn, vn, ldn, ko, vo, o, R, H, 0.125, 0.0, 0.0, None)
+    assert ad(X, 384, None, None, 128, 0, None, None, 384, None, None, X, 6, 2) == BAD          # no history and no new key
+    assert ad(None, 384, X, X, 128, 5, X, X, 384, X, X, X, 6, 2) == BAD and ad(X, 384, X, X, 128, 5, X, X, 384, X, X, None, 6, 2) == BAD
+    assert ad(X, 384, X, X, 128, 5, X, X, 384, X, X, X, 0, 2) == BAD and ad(X, 384, X, X, 128, 5, X, X, 384, X, X, X, 6, 0) == BAD
+    assert ad(X, 384, X, X, 128, -1, X, X, 384, X, X, X, 6, 2) == BAD
+    assert ad(X, 384, None, X, 128, 5, X, X, 384, X, X, X, 6, 2) == BAD and ad(X, 384, X, None, 128, 5, X, X, 384, X, X, X, 6, 2) == BAD
+    assert ad(X, 384, X, X, 128, 5, X, None, 384, X, X, X, 6, 2) == BAD and ad(X, 384, X, X, 128, 5, X, X, 384, X, None, X, 6, 2) == BAD
+    assert ad(X, 386, X, X, 128, 5, X, X, 384, X, X, X, 6, 2) == SHAPE and ad(X, 384, X, X, 130, 5, X, X, 384, X, X, X, 6, 2) == SHAPE
+    assert ad(X, 384, X, X, 128, 5, X, X, 386, X, X, X, 6, 2) == SHAPE
+    # caption_beam_tail(logits, ldx, row_add, B, beam, vocab, step, max_steps, eos, scores, tokens, backptr, n_steps, done, next_ids,
+    #                   next_parents, next_add, done_host, workspace, workspace_bytes)
+    big = 1 << 30
+    bt = lambda ldx, B, beam, V, step, wsb=big, logits=X: lib.hirest_caption_beam_tail(logits, ldx, X, B, beam, V, step, 48, 102, X, X, X, X, X, X,
+                                                                                        X, X, None, X, wsb, None)
+    assert bt(30528, 5, 17, 30528, 0) == BAD and bt(30528, 5, 0, 30528, 0) == BAD and bt(30528, 0, 5, 30528, 0) == BAD
+    assert bt(30528, 5, 5, 30528, 48) == BAD and bt(30528, 5, 5, 30528, -1) == BAD and bt(30528, 5, 5, 0, 0) == BAD
+    assert bt(30528, 5, 5, 30528, 0, logits=None) == BAD
+    assert bt(30522, 5, 5, 30522, 0) == SHAPE and bt(30530, 5, 5, 30528, 0) == SHAPE and bt(30528, 5, 5, 30528, 0, logits=X + 4) == SHAPE
+    assert bt(8, 5, 12, 8, 0) == SHAPE and bt(32772, 5, 5, 32772, 0) == SHAPE                   # beam > vocab, vocab > 32768
+    assert bt(30528, 5, 5, 30528, 0, wsb=lib.hirest_caption_beam_tail_workspace_bytes(5, 5, 30528) - 1) == WS
+    # beam_advance(val, idx, B, beam, vocab, step, max_steps, eos, ...) / beam_backtrack(scores, tokens, backptr, n_steps, B, beam, max_steps, out)
+    ba = lambda B, beam, step: lib.hirest_beam_advance(X, X, B, beam, 30528, step, 48, 102, X, X, X, X, X, X, X, X, None)
+    assert ba(5, 65, 0) == BAD and ba(5, 0, 0) == BAD and ba(0, 5, 0) == BAD and ba(5, 5, 48) == BAD and ba(5, 5, -1) == BAD
+    bb = lambda s, t, bp, n, B, beam, ms, o: lib.hirest_beam_backtrack(s, t, bp, n, B, beam, ms, o, None)
+    for i in range(5):
+        ptrs = [X] * 5
+        ptrs[i] = None
+        assert bb(ptrs[0], ptrs[1], ptrs[2], ptrs[3], 5, 5, 48, ptrs[4]) == BAD, i
+    assert bb(X, X, X, X, 0, 5, 48, X) == BAD and bb(X, X, X, X, 5, 0, 48, X) == BAD and bb(X, X, X, X, 5, 5, 0, X) == BAD
+    # log_softmax(x, ldx, row_add, out, ldo, rows, V)
+    assert lib.hirest_log_softmax_f32(None, 8, None, X, 8, 2, 8, None) == BAD and lib.hirest_log_softmax_f32(X, 8, None, None, 8, 2, 8, None) == BAD
+    assert lib.hirest_log_softmax_f32(X, 8, None, X, 8, 0, 8, None) == BAD and lib.hirest_log_softmax_f32(X, 8, None, X, 8, 2, 0, None) == BAD
