@@ -1523,109 +1523,60 @@ __global__ __launch_bounds__(512) void gemm_pp256(GemmP p) { pp256_body<EPI, RD,
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_pp256x3(GemmP p) { pp256_body<EPI, 1, true>(p); }
 template <int EPI>
-__global__ __launch_bounds__(512) void gemm_pq256(GemmP p) { pp256_body<EPI, (EPI == HIREST_EPI_BIAS_RESID2_LNSTATS ? HIREST_S2_RD : 1), false, 1>(p); }      // two-phase schedule (PH2); the two-array residual epilogue decodes its loads a pass late: look-ahead 2 (1.258 -> 1.206 ms on proj; 3: 1.27-1.30)      // two-phase schedule (PH2)
+__global__ __launch_bounds__(512) void gemm_pq256(GemmP p) { pp256_body<EPI, (EPI == HIREST_EPI_BIAS_RESID2_LNSTATS ? HIREST_S2_RD : 1), false, 1>(p); }      // two-phase schedule (PH2); the two-array residual epilogue decodes its loads a pass late: look-ahead 2 (1.258 -> 1.206 ms on proj; 3: 1.27-1.30)
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_pq256x3(GemmP p) { pp256_body<EPI, 1, true, 1>(p); }
 template <int EPI>      // the measurement variant of gemm_pq256: same schedule and arithmetic, with the hirest_gemm_debug_mode switches live
 __global__ __launch_bounds__(512) void gemm_pq256_dbg(GemmP p) { pp256_body<EPI, (EPI == HIREST_EPI_BIAS_RESID2_LNSTATS ? HIREST_S2_RD : 1), false, 1, true>(p); }
 
 
-template <int EPI, int RD = 1, bool X3 = false, int PH2 = 0, bool DBG = false>
-int launch_pp256(GemmP p, hipStream_t s) {
-    static_assert(!DBG || (PH2 && !X3), "the switch-carrying instantiation exists for gemm_pq256 only");
-    static HirestDevCfg cfg;
-    int cus = 0;
-    auto kern = [] {
-        if constexpr (DBG) return gemm_pq256_dbg<EPI>;
-        else if constexpr (X3 && PH2) return gemm_pq256x3<EPI>;
-        else if constexpr (X3) return gemm_pp256x3<EPI>;
-        else if constexpr (PH2) return gemm_pq256<EPI>;
-        else return gemm_pp256<EPI, RD>;
-    }();
-    constexpr int LDS = 2 * Q_STEP + 8 * p_stg_bytes(EPI);
-    if (int e = hirest_configure(kern, LDS, cfg, &cus)) return e;
+// ---- host side: gemm_choose() decides which kernel a call takes, gemm_kernel() maps that choice to the instantiation and to its name as
+// rocprofv3 prints it; hirest_gemm_bf16 launches the result and hirest_gemm_dispatch_name prints it, so the two cannot disagree
+
+// 256 x 256 tile counts of the t256* / p256 / pp256 / pq256 kernels
+static inline void tiles256(GemmP& p) {
     p.nbm = (p.M + T_BM - 1) / T_BM; p.nbn = (p.N + T_BN - 1) / T_BN;
     p.ppx = (p.nbm + 7) / 8;
+}
+
+// One launcher per launch geometry.  `cfg` is one static per kernel instantiation: it records that the dynamic-LDS limit of KERN was raised
+// on a device (hirest_configure).
+// Tile-grid kernels: one workgroup of 512 threads per 256 x 256 tile, 8 * ppx * nbn of them.
+template <auto KERN, int LDS>
+int launch_tiles(GemmP p, hipStream_t s) {
+    static HirestDevCfg cfg;
+    if (int e = hirest_configure(KERN, LDS, cfg)) return e;
+    tiles256(p);
+    hipLaunchKernelGGL(KERN, dim3(8 * p.ppx * p.nbn), dim3(512), LDS, s, p);
+    return hirest_launch_status();
+}
+// Persistent kernels: NW waves per workgroup, one workgroup per CU (cus / 8 per XCD) or per tile of an XCD's share, whichever is fewer
+template <auto KERN, int NW, int LDS>
+int launch_persistent(GemmP p, hipStream_t s) {
+    static HirestDevCfg cfg;
+    int cus = 0;
+    if (int e = hirest_configure(KERN, LDS, cfg, &cus)) return e;
+    tiles256(p);
     int nslot = cus / 8; nslot = nslot < 1 ? 1 : nslot;
     const int per_xcd = p.ppx * p.nbn;
     if (nslot > per_xcd) nslot = per_xcd;
-    hipLaunchKernelGGL(kern, dim3(8 * nslot), dim3(512), LDS, s, p);
+    hipLaunchKernelGGL(KERN, dim3(8 * nslot), dim3(64 * NW), LDS, s, p);
     return hirest_launch_status();
 }
-
-template <int EPI, int WN, bool DBG, int RD = 1>
-int launch_p256_impl(GemmP p, hipStream_t s) {
-    static HirestDevCfg cfg;
-    int cus = 0;
-    auto kern = gemm_p256<EPI, WN, DBG, RD>;
-    constexpr int NW = 512 / WN;
-    constexpr int LDS = 2 * Q_STEP + NW * p_stg_bytes(EPI);
-    if (int e = hirest_configure(kern, LDS, cfg, &cus)) return e;
-    p.nbm = (p.M + T_BM - 1) / T_BM; p.nbn = (p.N + T_BN - 1) / T_BN;
-    p.ppx = (p.nbm + 7) / 8;
-    int nslot = cus / 8; nslot = nslot < 1 ? 1 : nslot;
-    const int per_xcd = p.ppx * p.nbn;
-    if (nslot > per_xcd) nslot = per_xcd;
-    hipLaunchKernelGGL(kern, dim3(8 * nslot), dim3(64 * NW), LDS, s, p);
-    return hirest_launch_status();
-}
-
-template <int EPI, int WN>
-int launch_p256(GemmP p, hipStream_t s) {
-    if constexpr (WN == 64 && (EPI == HIREST_EPI_BIAS_BF16 || EPI == HIREST_EPI_BIAS_GELU_BF16 || EPI == HIREST_EPI_BIAS_RESID_F32)) {
-        if (p.dbg) return launch_p256_impl<EPI, WN, true>(p, s);       // experiment kernel: the three tower epilogues only
-    }
-    p.dbg = 0;
-    return launch_p256_impl<EPI, WN, false>(p, s);
-}
+constexpr int p_lds(int epi, int nw) { return 2 * Q_STEP + nw * p_stg_bytes(epi); }   // 2-slot ring + one epilogue staging area per wave
 
 template <int EPI>
-int launch256q(GemmP p, hipStream_t s) {
-    static HirestDevCfg cfg;
-    auto kern = gemm_t256q<EPI>;
-    if (int e = hirest_configure(kern, 2 * Q_STEP, cfg)) return e;
-    p.nbm = (p.M + T_BM - 1) / T_BM; p.nbn = (p.N + T_BN - 1) / T_BN;
-    p.ppx = (p.nbm + 7) / 8;
-    const int grid = 8 * p.ppx * p.nbn;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 2 * Q_STEP, s, p);
+int launch_t128(GemmP p, hipStream_t s) {                         // (tile counts of 128 x 128: hirest_gemm_bf16 has set them)
+    hipLaunchKernelGGL(gemm_t128<EPI>, dim3(8 * p.ppx * p.nbn), dim3(256), 2 * STAGE_BYTES, s, p);
     return hirest_launch_status();
 }
-
-template <int EPI>
-int launch256p(GemmP p, hipStream_t s) {
-    static HirestDevCfg cfg;
-    auto kern = gemm_t256p<EPI>;
-    if (int e = hirest_configure(kern, 4 * T_SLAB, cfg)) return e;
-    p.nbm = (p.M + T_BM - 1) / T_BM; p.nbn = (p.N + T_BN - 1) / T_BN;
-    p.ppx = (p.nbm + 7) / 8;
-    const int grid = 8 * p.ppx * p.nbn;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 4 * T_SLAB, s, p);
-    return hirest_launch_status();
-}
-
-template <int EPI, int T_NST>
-int launch256(GemmP p, hipStream_t s) {
-    static HirestDevCfg cfg;
-    auto kern = gemm_t256<EPI, T_NST>;
-    if (int e = hirest_configure(kern, T_NST * T_SLAB, cfg)) return e;
-    p.nbm = (p.M + T_BM - 1) / T_BM; p.nbn = (p.N + T_BN - 1) / T_BN;
-    p.ppx = (p.nbm + 7) / 8;
-    const int grid = 8 * p.ppx * p.nbn;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), T_NST * T_SLAB, s, p);
-    return hirest_launch_status();
-}
-
-}  // namespace
-std::atomic<int> g_gemm_dbg{0};
-namespace {
 
 template <int EPI, int WM>
-int launch_t128x3_impl(const GemmP& p0, hipStream_t s) {
+int launch_t128x3(GemmP p, hipStream_t s) {
     static HirestDevCfg cfg;
     auto kern = gemm_t128x3<EPI, WM>;
     constexpr int LDS = 4 * (64 * WM + BN) * BK * 2;
     if (int e = hirest_configure(kern, LDS, cfg)) return e;
-    GemmP p = p0;
     p.nbm = (p.M + 64 * WM - 1) / (64 * WM);
     p.ppx = (p.nbm + 7) / 8;
     p.flat = p.nbm < 32 ? 1 : 0;                                  // (same tiles, same arithmetic per tile: the mapping does not change a bit of the result)
@@ -1647,60 +1598,156 @@ int launch_t128x3_impl(const GemmP& p0, hipStream_t s) {
     }
     return hirest_launch_status();
 }
+
+}  // namespace
+// hirest_gemm_select_kernel: 0 automatic, 1 t128, 2 / 3 t256 with a 4- / 5-slot ring, 4 t256p, 5 t256q, 6 / 7 p256 with 8 / 4 waves, 8 pp256,
+// 9 pq256 (and pq256x3).  Read by gemm_choose() only.
+std::atomic<int> g_force_kernel{0};
+std::atomic<int> g_gemm_dbg{0};       // hirest_gemm_debug_mode word (layout: gemm_shared.h); read by gemm_choose() and the decode in hirest_gemm_bf16
+namespace {
+
+// Which epilogues a kernel family is instantiated for (gemm_kernel) and may therefore be chosen for (gemm_choose)
+constexpr bool epi_is_plain(int e) { return e >= HIREST_EPI_BIAS_BF16 && e <= HIREST_EPI_PATCH_POS_F32; }   // every non-X3 family
+// LN-fold producers and consumers exist in the persistent kernels only: p256 with 8 waves, pp256, pq256, pq256_dbg
+constexpr bool epi_is_fused(int e) { return e == HIREST_EPI_BIAS_RESID_LNSTATS_F32 || e == HIREST_EPI_BIAS_RESID2_LNSTATS || epi_is_lnfold(e); }
+constexpr bool epi_is_x3(int e) { return e == HIREST_EPI_BIAS_F32 || e == HIREST_EPI_BIAS_RESID_F32 || e == HIREST_EPI_BIAS_GELU_SPLIT2; }
+// the timing-experiment instantiation gemm_p256<EPI, 64, true>: the three tower epilogues only
+constexpr bool epi_has_p256_dbg(int e) { return e == HIREST_EPI_BIAS_BF16 || e == HIREST_EPI_BIAS_GELU_BF16 || e == HIREST_EPI_BIAS_RESID_F32; }
+
+enum class GemmFamily { t128, t256, t256p, t256q, p256, pp256, pq256, pq256_dbg, pp256x3, pq256x3, t128x3 };
+struct GemmChoice {
+    int status = 0;                        // HIREST_E_* : no kernel takes these arguments (the other members mean nothing then)
+    GemmFamily family = GemmFamily::t128;
+    int epi = 0;
+    int ring = 0;                          // t256: LDS ring slots (4 / 5)
+    int wn = 64;                           // p256: columns per wave (64: 8 waves, 128: 4 waves)
+    bool dbg = false;                      // p256: the instantiation that reads p.dbg
+    int wm = 2;                            // t128x3: wave rows per K group (2: 128-row tiles, 3: 192-row tiles)
+    bool drop_dbg = false;                 // p.dbg is zeroed for the launch (p256 without `dbg` and every LN-fold call; none of their kernels reads it)
+};
+
 // 192-row tiles (WM = 3) when they save rounds over the 256 CUs: cost of a tiling = rounds x tile height.  Taken only under HIREST_GEMM_X3_T128
 // (the joint model's calls): the towers' small split-operand calls keep the 128 x 128 tiles they have always had.
-static inline bool t128x3_tall(const GemmP& p, bool allow) {
-    if (!allow) return false;
-    const int64_t n2 = (int64_t)((p.M + 127) / 128) * p.nbn, n3 = (int64_t)((p.M + 191) / 192) * p.nbn;
+static inline bool t128x3_tall(int M, int N) {
+    const int nbn = (N + BN - 1) / BN;
+    const int64_t n2 = (int64_t)((M + 127) / 128) * nbn, n3 = (int64_t)((M + 191) / 192) * nbn;
     const int64_t c2 = ((n2 + 255) / 256) * 2, c3 = ((n3 + 255) / 256) * 3;
     return 4 * c3 <= 3 * c2;                                      // (a 6 % saving on paper measured 2 % slower at B = 32: take it from a quarter on)
 }
-template <int EPI>
-int launch_t128x3(const GemmP& p, hipStream_t s, bool allow_tall = false) {
-    return t128x3_tall(p, allow_tall) ? launch_t128x3_impl<EPI, 3>(p, s) : launch_t128x3_impl<EPI, 2>(p, s);
+static inline bool x3_small(int64_t M, int64_t N) { return ((M + 255) / 256) * ((N + 255) / 256) < 256; }   // fewer 256 x 256 tiles than CUs
+
+// The dispatch decision: pure host logic over the epilogue, the flags and M, N of the call and the two process-wide states.  It does not look at
+// K, the strides or the pointers (hirest_gemm_bf16 checks those around it), so hirest_gemm_dispatch_name can ask it without operands.
+GemmChoice gemm_choose(const hirest_gemm_args& a) {
+    const int f = g_force_kernel, word = g_gemm_dbg;
+    GemmChoice c;
+    c.epi = a.epilogue;
+    auto reject = [&c](int status) { c.status = status; return c; };
+    auto take = [&c](GemmFamily family) { c.family = family; return c; };
+    if (a.flags & HIREST_GEMM_X3) {                   // split-operand products, fp32 accumulators out: no selection but 9, no debug switches
+        if (!epi_is_x3(c.epi)) return reject(HIREST_E_BADARG);
+        // the 128 x 128 kernel (2 workgroups per CU) below 256 tiles of 256 x 256 — the towers keep the 256 x 256 kernel for
+        // HIREST_EPI_BIAS_GELU_SPLIT2 at every size — or wherever the joint model asks for it
+        const bool t128 = (a.flags & HIREST_GEMM_X3_T128) != 0;
+        if (t128 || (x3_small(a.M, a.N) && c.epi != HIREST_EPI_BIAS_GELU_SPLIT2)) {
+            c.wm = (t128 && t128x3_tall(a.M, a.N)) ? 3 : 2;
+            return take(GemmFamily::t128x3);
+        }
+        return take(f == 9 ? GemmFamily::pq256x3 : GemmFamily::pp256x3);
+    }
+    if (!epi_is_plain(c.epi) && !epi_is_fused(c.epi)) return reject(HIREST_E_BADARG);     // (HIREST_EPI_BIAS_GELU_SPLIT2 exists in the X3 form only)
+    // the measurement variant of pq256 wherever one of the switches only it reads is set
+    const GemmFamily pq = (word & GEMM_DBG_PQ_SWITCHES) ? GemmFamily::pq256_dbg : GemmFamily::pq256;
+    if (epi_is_fused(c.epi)) {
+        // (the persistent kernels take any M, N: a small problem just leaves CUs idle — the CLS-row GEMMs of a tower's last block)
+        if (a.M < 64 || a.N < 256) return reject(HIREST_E_SHAPE);
+        c.drop_dbg = true;
+        // pq256 on every shape: 1-3.3 % faster than p256 (K = 1408) / pp256 (K = 6144), same bits; 6 / 8 select those for A/B
+        return take(f == 6 ? GemmFamily::p256 : f == 8 ? GemmFamily::pp256 : pq);
+    }
+    const bool big = (int64_t)a.M * a.N >= (int64_t)2048 * 1024 && a.M >= 512 && a.N >= 256;
+    const bool p256_dbg = (word & GEMM_DBG_KERNEL_BITS) && epi_has_p256_dbg(c.epi);       // (the timing-experiment bits exist in p256 only)
+    switch (f) {
+        case 0: if (!big) return take(GemmFamily::t128);
+                if (!p256_dbg) return take(pq);                   // large problems: the two-phase ping-pong kernel
+                [[fallthrough]];                                  // ... unless a timing-experiment bit asks for the kernel that has them
+        case 6: c.dbg = p256_dbg; c.drop_dbg = !p256_dbg; return take(GemmFamily::p256);
+        case 7: c.wn = 128; c.drop_dbg = true; return take(GemmFamily::p256);
+        case 8: return take(GemmFamily::pp256);
+        case 9: return take(pq);
+        case 5: return take(GemmFamily::t256q);
+        case 4: return take(GemmFamily::t256p);
+        case 2: c.ring = 4; return take(GemmFamily::t256);
+        case 3: c.ring = 5; return take(GemmFamily::t256);
+        default: return take(GemmFamily::t128);
+    }
 }
-static inline bool x3_small(int64_t M, int64_t N) { return ((M + 255) / 256) * ((N + 255) / 256) < 256; }
-std::atomic<int> g_force_kernel{0};   // 0 auto, 1 t128, 2 t256 with a 4-slot ring, 3 t256 with a 5-slot ring (tests / A-B timing)
 
-// walk / knock-out switches of hirest_gemm_debug_mode that only gemm_pq256_dbg reads (bits 10-19)
-static inline bool pq_switches(const GemmP& p) { return p.sched || p.stagger || p.epi_dbg; }
-
-// LN-fold epilogues exist in the persistent kernels only
+// A kernel instantiation: its name as rocprofv3 prints it (a printf format that takes the epilogue number) and its launcher
+struct GemmKernel {
+    const char* name;
+    int (*launch)(GemmP, hipStream_t);
+};
+// Every instantiation of this file, next to its name.  The `if constexpr` lines say which families exist for which epilogues (gemm_choose asks
+// for nothing else); {nullptr, nullptr} would be a choice without a kernel.
 template <int EPI>
-int launch_fused(const GemmP& p, hipStream_t s) {
-    // (the persistent kernels take any M, N: a small problem just leaves CUs idle — the CLS-row GEMMs of a tower's last block)
-    const bool big = p.M >= 64 && p.N >= 256;
-    if (!big || !p.aux0 || !p.aux1) return !big ? HIREST_E_SHAPE : HIREST_E_BADARG;
-    if ((EPI == HIREST_EPI_BIAS_RESID_LNSTATS_F32 || EPI == HIREST_EPI_BIAS_RESID2_LNSTATS) && p.N % 8 != 0) return HIREST_E_SHAPE;   // 16-B stores of the bf16 copy
-    if (EPI == HIREST_EPI_BIAS_RESID2_LNSTATS && p.ldo % 8 != 0) return HIREST_E_SHAPE;
-    GemmP q = p; q.dbg = 0;
-    // default since round 4: the two-phase ping-pong kernel (pq256) on every shape — 1-3.3 % faster than p256 (K = 1408) / pp256 (K = 6144),
-    // same bits; 6 / 8 select those for A/B
-    if (g_force_kernel == 6) return launch_p256_impl<EPI, 64, false>(q, s);
-    if (g_force_kernel == 8) return launch_pp256<EPI>(q, s);
-    if (pq_switches(q)) return launch_pp256<EPI, 1, false, 1, true>(q, s);      // measurement variant (gemm_pq256_dbg)
-    return launch_pp256<EPI, 1, false, 1>(q, s);
+GemmKernel gemm_kernel(const GemmChoice& c) {
+    constexpr int LDS8 = p_lds(EPI, 8);
+    if constexpr (epi_is_x3(EPI)) switch (c.family) {
+        case GemmFamily::pp256x3: return {"gemm_pp256x3<%d>", launch_persistent<gemm_pp256x3<EPI>, 8, LDS8>};
+        case GemmFamily::pq256x3: return {"gemm_pq256x3<%d>", launch_persistent<gemm_pq256x3<EPI>, 8, LDS8>};
+        case GemmFamily::t128x3:
+            if (c.wm == 3) return {"gemm_t128x3<%d, 3>", launch_t128x3<EPI, 3>};
+            return {"gemm_t128x3<%d, 2>", launch_t128x3<EPI, 2>};
+        default: break;
+    }
+    if constexpr (epi_is_plain(EPI) || epi_is_fused(EPI)) switch (c.family) {
+        case GemmFamily::p256:
+            if constexpr (epi_has_p256_dbg(EPI)) if (c.dbg) return {"gemm_p256<%d, 64, true, 1>", launch_persistent<gemm_p256<EPI, 64, true, 1>, 8, LDS8>};
+            if constexpr (epi_is_plain(EPI)) if (c.wn == 128) return {"gemm_p256<%d, 128, false, 1>", launch_persistent<gemm_p256<EPI, 128, false, 1>, 4, p_lds(EPI, 4)>};
+            return {"gemm_p256<%d, 64, false, 1>", launch_persistent<gemm_p256<EPI, 64, false, 1>, 8, LDS8>};
+        case GemmFamily::pp256: return {"gemm_pp256<%d, 1>", launch_persistent<gemm_pp256<EPI, 1>, 8, LDS8>};
+        case GemmFamily::pq256: return {"gemm_pq256<%d>", launch_persistent<gemm_pq256<EPI>, 8, LDS8>};
+        case GemmFamily::pq256_dbg: return {"gemm_pq256_dbg<%d>", launch_persistent<gemm_pq256_dbg<EPI>, 8, LDS8>};
+        default: break;
+    }
+    if constexpr (epi_is_plain(EPI)) switch (c.family) {
+        case GemmFamily::t128: return {"gemm_t128<%d>", launch_t128<EPI>};
+        case GemmFamily::t256:
+            if (c.ring == 5) return {"gemm_t256<%d, 5>", launch_tiles<gemm_t256<EPI, 5>, 5 * T_SLAB>};
+            return {"gemm_t256<%d, 4>", launch_tiles<gemm_t256<EPI, 4>, 4 * T_SLAB>};
+        case GemmFamily::t256p: return {"gemm_t256p<%d>", launch_tiles<gemm_t256p<EPI>, 4 * T_SLAB>};
+        case GemmFamily::t256q: return {"gemm_t256q<%d>", launch_tiles<gemm_t256q<EPI>, 2 * Q_STEP>};
+        default: break;
+    }
+    return {nullptr, nullptr};
+}
+GemmKernel gemm_kernel(const GemmChoice& c) {
+    switch (c.epi) {
+        case HIREST_EPI_BIAS_BF16: return gemm_kernel<HIREST_EPI_BIAS_BF16>(c);
+        case HIREST_EPI_BIAS_GELU_BF16: return gemm_kernel<HIREST_EPI_BIAS_GELU_BF16>(c);
+        case HIREST_EPI_BIAS_QGELU_BF16: return gemm_kernel<HIREST_EPI_BIAS_QGELU_BF16>(c);
+        case HIREST_EPI_BIAS_RESID_F32: return gemm_kernel<HIREST_EPI_BIAS_RESID_F32>(c);
+        case HIREST_EPI_BIAS_F32: return gemm_kernel<HIREST_EPI_BIAS_F32>(c);
+        case HIREST_EPI_PATCH_POS_F32: return gemm_kernel<HIREST_EPI_PATCH_POS_F32>(c);
+        case HIREST_EPI_BIAS_RESID_LNSTATS_F32: return gemm_kernel<HIREST_EPI_BIAS_RESID_LNSTATS_F32>(c);
+        case HIREST_EPI_LNFOLD_BF16: return gemm_kernel<HIREST_EPI_LNFOLD_BF16>(c);
+        case HIREST_EPI_LNFOLD_GELU_BF16: return gemm_kernel<HIREST_EPI_LNFOLD_GELU_BF16>(c);
+        case HIREST_EPI_BIAS_GELU_SPLIT2: return gemm_kernel<HIREST_EPI_BIAS_GELU_SPLIT2>(c);
+        case HIREST_EPI_BIAS_RESID2_LNSTATS: return gemm_kernel<HIREST_EPI_BIAS_RESID2_LNSTATS>(c);
+        default: return {nullptr, nullptr};
+    }
 }
 
-
-template <int EPI>
-int launch(const GemmP& p, hipStream_t s) {
-    const bool big = (int64_t)p.M * p.N >= (int64_t)2048 * 1024 && p.M >= 512 && p.N >= 256;
-    // large problems: the two-phase ping-pong kernel (round 4; p256 / pp256 stay selectable: 6 / 8)
-    constexpr bool has_dbg_inst = EPI == HIREST_EPI_BIAS_BF16 || EPI == HIREST_EPI_BIAS_GELU_BF16 || EPI == HIREST_EPI_BIAS_RESID_F32;
-    if (g_force_kernel == 0 && big && !(p.dbg && has_dbg_inst))
-        return pq_switches(p) ? launch_pp256<EPI, 1, false, 1, true>(p, s) : launch_pp256<EPI, 1, false, 1>(p, s);
-    if (g_force_kernel == 6 || (g_force_kernel == 0 && big)) return launch_p256<EPI, 64>(p, s);      // (timing-experiment bits exist in p256 only)
-    if (g_force_kernel == 7) return launch_p256<EPI, 128>(p, s);
-    if (g_force_kernel == 8) return launch_pp256<EPI>(p, s);
-    if (g_force_kernel == 9) return pq_switches(p) ? launch_pp256<EPI, 1, false, 1, true>(p, s) : launch_pp256<EPI, 1, false, 1>(p, s);
-    if (g_force_kernel == 5) return launch256q<EPI>(p, s);
-    if (g_force_kernel == 4) return launch256p<EPI>(p, s);
-    if (g_force_kernel == 2) return launch256<EPI, 4>(p, s);
-    if (g_force_kernel == 3) return launch256<EPI, 5>(p, s);
-    const int grid = 8 * p.ppx * p.nbn;
-    hipLaunchKernelGGL(gemm_t128<EPI>, dim3(grid), dim3(256), 2 * STAGE_BYTES, s, p);
-    return hirest_launch_status();
+// What the epilogue needs of the operands gemm_choose() does not look at
+int epilogue_operand_status(const hirest_gemm_args& a) {
+    const int e = a.epilogue;
+    if (e == HIREST_EPI_PATCH_POS_F32 && (!a.pos || a.patches_per_frame <= 0)) return HIREST_E_BADARG;
+    if (e == HIREST_EPI_BIAS_GELU_SPLIT2 && (a.N % 32 != 0 || a.ldo < 2 * (int64_t)a.N || a.ldo % 8 != 0)) return HIREST_E_SHAPE;
+    if (epi_is_fused(e) && (!a.aux0 || !a.aux1)) return HIREST_E_BADARG;
+    if ((e == HIREST_EPI_BIAS_RESID_LNSTATS_F32 || e == HIREST_EPI_BIAS_RESID2_LNSTATS) && a.N % 8 != 0) return HIREST_E_SHAPE;   // 16-B stores of the bf16 copy
+    if (e == HIREST_EPI_BIAS_RESID2_LNSTATS && a.ldo % 8 != 0) return HIREST_E_SHAPE;
+    return 0;
 }
 
 }  // namespace
@@ -1716,41 +1763,14 @@ extern "C" int hirest_gemm_select_kernel(int32_t which) {
 }
 
 // Which kernel instantiation hirest_gemm_bf16 launches for these arguments under the current hirest_gemm_select_kernel /
-// hirest_gemm_debug_mode state, spelled the way rocprofv3 prints kernel names (template arguments included).  Mirrors
-// launch() / launch_fused() above; pure host logic (no launch, usable without a GPU).  Profiles committed under profiles/
+// hirest_gemm_debug_mode state, spelled the way rocprofv3 prints kernel names (template arguments included): the same gemm_choose() /
+// gemm_kernel() answer that hirest_gemm_bf16 launches; no launch, usable without a GPU.  Profiles committed under profiles/
 // are checked against it (tests/test_abi_and_host.py), so a profile of kernels the tower no longer runs cannot be quoted.
 extern "C" int hirest_gemm_dispatch_name(const hirest_gemm_args* a, char* out, int32_t out_len) {
     if (!a || a->struct_size != sizeof(hirest_gemm_args) || !out || out_len < 48) return HIREST_E_BADARG;
-    const int epi = a->epilogue, f = g_force_kernel;
-    if (epi < 0 || epi > HIREST_EPI_BIAS_RESID2_LNSTATS) return HIREST_E_BADARG;
-    if (a->flags & HIREST_GEMM_X3) {
-        if (epi != HIREST_EPI_BIAS_F32 && epi != HIREST_EPI_BIAS_RESID_F32 && epi != HIREST_EPI_BIAS_GELU_SPLIT2) return HIREST_E_BADARG;
-        if (((a->flags & HIREST_GEMM_X3_T128) || x3_small(a->M, a->N)) && (epi != HIREST_EPI_BIAS_GELU_SPLIT2 || (a->flags & HIREST_GEMM_X3_T128))) {
-            GemmP q; q.M = a->M; q.nbn = (a->N + BN - 1) / BN;
-            snprintf(out, out_len, t128x3_tall(q, (a->flags & HIREST_GEMM_X3_T128) != 0) ? "gemm_t128x3<%d, 3>" : "gemm_t128x3<%d, 2>", epi);
-            return 0;
-        }
-        snprintf(out, out_len, g_force_kernel == 9 ? "gemm_pq256x3<%d>" : "gemm_pp256x3<%d>", epi);
-        return 0;
-    }
-    if (epi == HIREST_EPI_BIAS_GELU_SPLIT2) return HIREST_E_BADARG;      // exists in the X3 form only
-    const bool fused = (epi >= HIREST_EPI_BIAS_RESID_LNSTATS_F32 && epi <= HIREST_EPI_LNFOLD_GELU_BF16) || epi == HIREST_EPI_BIAS_RESID2_LNSTATS;
-    const bool big = fused ? (a->M >= 64 && a->N >= 256) : ((int64_t)a->M * a->N >= (int64_t)2048 * 1024 && a->M >= 512 && a->N >= 256);
-    const bool dbg_inst = !fused && (g_gemm_dbg & ~(512 | 3072 | 0xF000 | 0xF0000)) && (epi == HIREST_EPI_BIAS_BF16 || epi == HIREST_EPI_BIAS_GELU_BF16 || epi == HIREST_EPI_BIAS_RESID_F32);
-    if (fused && !big) return HIREST_E_SHAPE;
-    const bool sw = (g_gemm_dbg & (3072 | 0xF000 | 0xF0000)) != 0;      // stagger / epilogue knock-outs / walk switches: the measurement variant
-    if (f == 9 || (fused && f != 6 && f != 8) || (!fused && f == 0 && big && !dbg_inst)) snprintf(out, out_len, sw ? "gemm_pq256_dbg<%d>" : "gemm_pq256<%d>", epi);
-    else if (fused) {
-        if (f == 8) snprintf(out, out_len, "gemm_pp256<%d, 1>", epi);
-        else snprintf(out, out_len, "gemm_p256<%d, 64, false, 1>", epi);
-    } else if (f == 6 || (f == 0 && big)) snprintf(out, out_len, "gemm_p256<%d, 64, %s, 1>", epi, dbg_inst ? "true" : "false");
-    else if (f == 7) snprintf(out, out_len, "gemm_p256<%d, 128, false, 1>", epi);
-    else if (f == 8) snprintf(out, out_len, "gemm_pp256<%d, 1>", epi);
-    else if (f == 5) snprintf(out, out_len, "gemm_t256q<%d>", epi);
-    else if (f == 4) snprintf(out, out_len, "gemm_t256p<%d>", epi);
-    else if (f == 2) snprintf(out, out_len, "gemm_t256<%d, 4>", epi);
-    else if (f == 3) snprintf(out, out_len, "gemm_t256<%d, 5>", epi);
-    else snprintf(out, out_len, "gemm_t128<%d>", epi);
+    const GemmChoice c = gemm_choose(*a);
+    if (c.status) return c.status;
+    snprintf(out, out_len, gemm_kernel(c).name, c.epi);
     return 0;
 }
 
@@ -1760,6 +1780,8 @@ extern "C" int hirest_gemm_bf16(const hirest_gemm_args* a, void* stream) {
     if (a->flags & ~(HIREST_GEMM_REVERSE | HIREST_GEMM_X3 | HIREST_GEMM_X3_T128)) return HIREST_E_BADARG;
     if ((a->flags & HIREST_GEMM_X3_T128) && !(a->flags & HIREST_GEMM_X3)) return HIREST_E_BADARG;      // (a retired flag, e.g. round 4's K-blocked operands, must not be read as row-major)
     if (a->K % BK != 0 || a->K % T_BK != 0 || a->N % 4 != 0 || a->lda % 8 != 0 || a->ldw % 8 != 0) return HIREST_E_SHAPE;
+    const GemmChoice c = gemm_choose(*a);
+    const int word = g_gemm_dbg;
     GemmP p;
     p.A = reinterpret_cast<const bf16_t*>(a->A); p.lda = a->lda;
     p.W = reinterpret_cast<const bf16_t*>(a->W); p.ldw = a->ldw;
@@ -1767,51 +1789,16 @@ extern "C" int hirest_gemm_bf16(const hirest_gemm_args* a, void* stream) {
     p.M = a->M; p.N = a->N; p.K = a->K;
     p.pos = a->pos; p.P = a->patches_per_frame;
     p.aux0 = a->aux0; p.aux1 = a->aux1;
-    p.rev = ((a->flags & HIREST_GEMM_REVERSE) && !(g_gemm_dbg & 512)) ? 1 : 0;   // debug bit 9: ignore the direction flags (A/B)
-    p.dbg = g_gemm_dbg & ~(512 | 3072 | 0xF000 | 0xF0000);
-    p.sched = (g_gemm_dbg >> 16) & 15;     // bit 18: team walk of the persistent ping-pong kernels (few column tiles); bit 16: uneven XCD split; bit 17: the two-array residual epilogue loads hi / lo cached instead of streaming (A/B)
-    p.stagger = (g_gemm_dbg >> 10) & 3;
-    p.epi_dbg = (g_gemm_dbg >> 12) & 15;   // A/B experiment: start the CUs of an XCD 0..3 quarter tiles apart (bits 10-11 = mode)
+    p.rev = ((a->flags & HIREST_GEMM_REVERSE) && !(word & GEMM_DBG_IGNORE_REVERSE)) ? 1 : 0;
+    p.dbg = c.drop_dbg ? 0 : word & GEMM_DBG_KERNEL_BITS;
+    p.stagger = (word >> GEMM_DBG_STAGGER_SHIFT) & GEMM_DBG_STAGGER_MASK;
+    p.epi_dbg = (word >> GEMM_DBG_EPI_SHIFT) & GEMM_DBG_EPI_MASK;
+    p.sched = (word >> GEMM_DBG_SCHED_SHIFT) & GEMM_DBG_SCHED_MASK;
     p.nbm = (a->M + BM - 1) / BM; p.nbn = (a->N + BN - 1) / BN;
     p.ppx = (p.nbm + 7) / 8;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     HirestProfScope prof(HIREST_PROF_GEMM, a->epilogue, a->M, a->N, a->K, s);
-    if (a->flags & HIREST_GEMM_X3) {                  // split-operand products: the ping-pong kernel's X3 form, fp32 outputs only
-        // fewer 256 x 256 tiles than CUs: the 128 x 128 kernel (2 workgroups per CU)
-        const bool small = x3_small(a->M, a->N) || (a->flags & HIREST_GEMM_X3_T128);
-        const bool tall = (a->flags & HIREST_GEMM_X3_T128) != 0;
-        if (small && a->epilogue == HIREST_EPI_BIAS_F32) return launch_t128x3<HIREST_EPI_BIAS_F32>(p, s, tall);
-        if (small && a->epilogue == HIREST_EPI_BIAS_RESID_F32) return launch_t128x3<HIREST_EPI_BIAS_RESID_F32>(p, s, tall);
-        if ((a->flags & HIREST_GEMM_X3_T128) && a->epilogue == HIREST_EPI_BIAS_GELU_SPLIT2) {      // (the towers keep the 256 x 256 kernel for this epilogue at every size)
-            if (a->N % 32 != 0 || a->ldo < 2 * (int64_t)a->N || a->ldo % 8 != 0) return HIREST_E_SHAPE;
-            return launch_t128x3<HIREST_EPI_BIAS_GELU_SPLIT2>(p, s, true);
-        }
-        switch (a->epilogue) {
-            case HIREST_EPI_BIAS_F32:
-                return g_force_kernel == 9 ? launch_pp256<HIREST_EPI_BIAS_F32, 1, true, 1>(p, s) : launch_pp256<HIREST_EPI_BIAS_F32, 1, true>(p, s);
-            case HIREST_EPI_BIAS_RESID_F32:
-                return g_force_kernel == 9 ? launch_pp256<HIREST_EPI_BIAS_RESID_F32, 1, true, 1>(p, s)
-                                           : launch_pp256<HIREST_EPI_BIAS_RESID_F32, 1, true>(p, s);
-            case HIREST_EPI_BIAS_GELU_SPLIT2:
-                if (a->N % 32 != 0 || a->ldo < 2 * (int64_t)a->N || a->ldo % 8 != 0) return HIREST_E_SHAPE;
-                return g_force_kernel == 9 ? launch_pp256<HIREST_EPI_BIAS_GELU_SPLIT2, 1, true, 1>(p, s)
-                                           : launch_pp256<HIREST_EPI_BIAS_GELU_SPLIT2, 1, true>(p, s);
-            default: return HIREST_E_BADARG;
-        }
-    }
-    switch (a->epilogue) {
-        case HIREST_EPI_BIAS_BF16: return launch<HIREST_EPI_BIAS_BF16>(p, s);
-        case HIREST_EPI_BIAS_GELU_BF16: return launch<HIREST_EPI_BIAS_GELU_BF16>(p, s);
-        case HIREST_EPI_BIAS_QGELU_BF16: return launch<HIREST_EPI_BIAS_QGELU_BF16>(p, s);
-        case HIREST_EPI_BIAS_RESID_F32: return launch<HIREST_EPI_BIAS_RESID_F32>(p, s);
-        case HIREST_EPI_BIAS_F32: return launch<HIREST_EPI_BIAS_F32>(p, s);
-        case HIREST_EPI_PATCH_POS_F32:
-            if (!a->pos || a->patches_per_frame <= 0) return HIREST_E_BADARG;
-            return launch<HIREST_EPI_PATCH_POS_F32>(p, s);
-        case HIREST_EPI_BIAS_RESID_LNSTATS_F32: return launch_fused<HIREST_EPI_BIAS_RESID_LNSTATS_F32>(p, s);
-        case HIREST_EPI_BIAS_RESID2_LNSTATS: return launch_fused<HIREST_EPI_BIAS_RESID2_LNSTATS>(p, s);
-        case HIREST_EPI_LNFOLD_BF16: return launch_fused<HIREST_EPI_LNFOLD_BF16>(p, s);
-        case HIREST_EPI_LNFOLD_GELU_BF16: return launch_fused<HIREST_EPI_LNFOLD_GELU_BF16>(p, s);
-        default: return HIREST_E_BADARG;     // (HIREST_EPI_BIAS_GELU_SPLIT2 without HIREST_GEMM_X3 included)
-    }
+    if (c.status) return c.status;
+    if (int e = epilogue_operand_status(*a)) return e;
+    return gemm_kernel(c).launch(p, s);
 }

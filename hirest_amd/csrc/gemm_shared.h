@@ -24,6 +24,15 @@ struct GemmP {
     int ksplit = 1;      // gemm_t128x3: K slices per tile (flat mapping only); > 1: raw partial tiles to `part`, splitk_reduce_kernel finishes
     float* part = nullptr;
 };
+// Layout of the hirest_gemm_debug_mode word: where hirest_gemm_bf16 puts its bits in GemmP
+constexpr int GEMM_DBG_IGNORE_REVERSE = 1 << 9;                               // bit 9: p.rev stays 0 whatever HIREST_GEMM_REVERSE says (A/B)
+constexpr int GEMM_DBG_STAGGER_SHIFT = 10, GEMM_DBG_STAGGER_MASK = 3;         // bits 10-11 -> p.stagger: start the CUs of an XCD 0..3 quarter tiles apart
+constexpr int GEMM_DBG_EPI_SHIFT = 12, GEMM_DBG_EPI_MASK = 15;                // bits 12-15 -> p.epi_dbg: knock-outs of the LN-statistics epilogue
+constexpr int GEMM_DBG_SCHED_SHIFT = 16, GEMM_DBG_SCHED_MASK = 15;            // bits 16-19 -> p.sched: 16 uneven XCD split, 17 cached hi / lo loads of the
+                                                                              // two-array residual epilogue, 18 team walk of the ping-pong kernels
+// the walk / knock-out switches that only gemm_pq256_dbg reads, and everything else, which goes to p.dbg (gemm_p256's DBG instantiation, gemm_t128x3)
+constexpr int GEMM_DBG_PQ_SWITCHES = GEMM_DBG_STAGGER_MASK << GEMM_DBG_STAGGER_SHIFT | GEMM_DBG_EPI_MASK << GEMM_DBG_EPI_SHIFT | GEMM_DBG_SCHED_MASK << GEMM_DBG_SCHED_SHIFT;
+constexpr int GEMM_DBG_KERNEL_BITS = ~(GEMM_DBG_IGNORE_REVERSE | GEMM_DBG_PQ_SWITCHES);
 
 constexpr int GROUP_M = 8;                        // M-panels walked together inside one XCD
 // M panels of XCD x: an even split, [x nbm / 8, (x + 1) nbm / 8) (1028 panels = 4 x 129 + 4 x 128, not 7 x 129 + 125)

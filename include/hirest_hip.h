@@ -58,8 +58,8 @@ enum hirest_epilogue {
     HIREST_EPI_BIAS_F32 = 4,         /* out f32           = acc + bias                        */
     HIREST_EPI_PATCH_POS_F32 = 5,    /* patch-embed: row m=b*P+p -> out row b*(P+1)+1+p;
                                         out f32 = acc + bias + pos[(1+p)*ldo' ...]; see below */
-    /* LayerNorm folded into the neighbouring GEMMs (large problems only: M*N >= 2^21, M >= 512, N >= 256;
-     * HIREST_E_SHAPE otherwise).  LN(x) W^T + b = rstd * (x W'^T - mean * s) + b' with W' = W * gamma (per input
+    /* LayerNorm folded into the neighbouring GEMMs (M >= 64 and N >= 256; HIREST_E_SHAPE otherwise, before the aux
+     * pointers are looked at).  LN(x) W^T + b = rstd * (x W'^T - mean * s) + b' with W' = W * gamma (per input
      * column), s[n] = sum_k W'[n][k], b' = b + W beta, so the GEMM reads the un-normalised stream and the LayerNorm
      * pass (vit_model.py:177-178) disappears: */
     HIREST_EPI_BIAS_RESID_LNSTATS_F32 = 6, /* producer: as BIAS_RESID_F32, plus aux0 = bf16 copy [M,N] of the new rows
@@ -117,11 +117,13 @@ enum { HIREST_GEMM_REVERSE = 1,
      };
 
 int hirest_gemm_bf16(const hirest_gemm_args* args, void* stream);
-/* Kernel selection for tests / A-B timing: 0 = automatic (default), 1 = force the 128x128 kernel,
- * 2 / 3 = the 256x256 ping-pong kernel with a 4- / 5-slot LDS ring, 4 = t256p (32-deep slabs), 5 = t256q
- * (64-deep steps), 6 / 7 = the persistent 256x256 kernel with 8 / 4 waves, 8 = the persistent ping-pong kernel (default for
- * K >= 4096), 9 = that kernel with two phases of 32 MFMAs per 64-deep step instead of four of 16 (pq256; also selects the two-phase form of the
- * HIREST_GEMM_X3 kernel).  10..17 (the 4-wave kernel of round 2) and 18..20 (the two-workgroup kernel gemm_d2 of round 3) are retired and rejected.
+/* Kernel selection for tests / A-B timing: 0 = automatic (default): pq256 (see 9) for M * N >= 2^21 with M >= 512 and N >= 256 and for
+ * every LN-fold epilogue, the 128x128 kernel below that; 1 = force the 128x128 kernel, 2 / 3 = the 256x256 ping-pong kernel with a
+ * 4- / 5-slot LDS ring, 4 = t256p (32-deep slabs), 5 = t256q (64-deep steps), 6 / 7 = the persistent 256x256 kernel with 8 / 4 waves (p256),
+ * 8 = the persistent ping-pong kernel (pp256), 9 = that kernel with two phases of 32 MFMAs per 64-deep step instead of four of 16 (pq256)
+ * at every size.  The LN-fold epilogues exist in the persistent kernels only: 6 and 8 select p256 (8 waves) and pp256 for them, every other
+ * value leaves them on pq256.  Of the HIREST_GEMM_X3 kernels only the choice between pp256x3 and its two-phase form (9) is open.
+ * 10..17 (the 4-wave kernel of round 2) and 18..20 (the two-workgroup kernel gemm_d2 of round 3) are retired and rejected.
  * Results are identical for every valid selection (same k order per output element). */
 int hirest_gemm_select_kernel(int32_t which);
 /* TIMING EXPERIMENTS ONLY (results become wrong): bit0 = skip the main-loop LDS-DMA, bit1 = skip the
@@ -133,8 +135,9 @@ int hirest_gemm_select_kernel(int32_t which);
  * ignore HIREST_GEMM_REVERSE.  0 restores normal operation. */
 int hirest_gemm_debug_mode(int32_t bits);
 /* Name of the kernel instantiation hirest_gemm_bf16 would launch for `args` under the current selection state, as rocprofv3
- * prints it (e.g. "gemm_p256<8, 64, false>", "gemm_pp256<6>").  Host logic only; out_len >= 48.  Lets a committed profile be
- * checked against what the library dispatches today. */
+ * prints it (e.g. "gemm_pq256<7>", "gemm_p256<8, 64, false, 1>", "gemm_t128x3<3, 2>").  It is the launch's own decision, asked without
+ * a launch: host logic only, and it looks at the epilogue, the flags, M and N alone (not at K, the strides or the pointers, which
+ * hirest_gemm_bf16 may still reject).  out_len >= 48.  Lets a committed profile be checked against what the library dispatches today. */
 int hirest_gemm_dispatch_name(const hirest_gemm_args* args, char* out, int32_t out_len);
 
 /* ------------------------------------------------------------------------------------

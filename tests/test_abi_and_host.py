@@ -377,6 +377,64 @@ def test_profiled_kernels_are_the_dispatched_ones(lib):
     lib.hirest_gemm_select_kernel(0)
 
 
+# (selection, debug word, flags, M, N, K, epilogue) -> (status, name) of hirest_gemm_dispatch_name, recorded from the library of the commit
+# before the launch code and the name function were given one decision function (csrc/gemm.hip: gemm_choose / gemm_kernel).  Every kernel
+# family, every kind of rejection and both sides of every threshold of the decision; flags: 1 REVERSE, 2 X3, 4 X3_T128.
+GEMM_DISPATCH_PIN = [
+    # plain epilogues, automatic selection: t128 below M * N = 2048 * 1024, M = 512 or N = 256, pq256 from there on
+    (0, 0, 0, 511, 8192, 64, 0, 0, 'gemm_t128<0>'), (0, 0, 0, 512, 4096, 64, 0, 0, 'gemm_pq256<0>'), (0, 0, 0, 512, 4092, 64, 0, 0, 'gemm_t128<0>'),
+    (0, 0, 0, 8192, 252, 64, 2, 0, 'gemm_t128<2>'), (0, 0, 0, 8192, 256, 64, 2, 0, 'gemm_pq256<2>'), (0, 0, 1, 39424, 2304, 768, 0, 0, 'gemm_pq256<0>'),
+    (0, 0, 4, 512, 4096, 64, 0, 0, 'gemm_pq256<0>'),                 # (X3_T128 without X3: the launch rejects it, the name does not look)
+    (0, 0, 0, 262144, 1408, 640, 5, 0, 'gemm_pq256<5>'),
+    # debug word: bit 9 alone changes nothing, bits 10-19 take the measurement variant, the others p256's DBG instantiation where it exists
+    (0, 512, 0, 512, 4096, 64, 1, 0, 'gemm_pq256<1>'), (0, 1024, 0, 512, 4096, 64, 0, 0, 'gemm_pq256_dbg<0>'),
+    (0, 262144, 0, 263168, 1408, 6144, 10, 0, 'gemm_pq256_dbg<10>'), (9, 4096, 0, 128, 128, 64, 4, 0, 'gemm_pq256_dbg<4>'),
+    (0, 4, 0, 512, 4096, 64, 3, 0, 'gemm_p256<3, 64, true, 1>'), (0, 4, 0, 512, 4096, 64, 4, 0, 'gemm_pq256<4>'), (0, 4, 0, 511, 8192, 64, 3, 0, 'gemm_t128<3>'),
+    (0, 1025, 0, 512, 4096, 64, 0, 0, 'gemm_p256<0, 64, true, 1>'),
+    # forced selections
+    (1, 0, 0, 4096, 4096, 64, 4, 0, 'gemm_t128<4>'), (2, 0, 0, 4096, 4096, 64, 3, 0, 'gemm_t256<3, 4>'), (3, 0, 0, 128, 128, 64, 5, 0, 'gemm_t256<5, 5>'),
+    (4, 0, 0, 4096, 4096, 64, 0, 0, 'gemm_t256p<0>'), (5, 0, 0, 4096, 4096, 64, 1, 0, 'gemm_t256q<1>'), (6, 0, 0, 4096, 4096, 64, 1, 0, 'gemm_p256<1, 64, false, 1>'),
+    (6, 1, 0, 4096, 4096, 64, 1, 0, 'gemm_p256<1, 64, true, 1>'), (6, 1, 0, 4096, 4096, 64, 2, 0, 'gemm_p256<2, 64, false, 1>'),
+    (7, 1, 0, 4096, 4096, 64, 0, 0, 'gemm_p256<0, 128, false, 1>'), (8, 0, 0, 128, 128, 64, 2, 0, 'gemm_pp256<2, 1>'), (9, 0, 0, 128, 128, 64, 3, 0, 'gemm_pq256<3>'),
+    # LN-fold epilogues: persistent kernels only, from M = 64, N = 256 on; selections other than 6 / 8 and the p256 debug bits do not apply
+    (0, 0, 0, 64, 256, 64, 7, 0, 'gemm_pq256<7>'), (0, 0, 0, 63, 256, 64, 7, -2, ''), (0, 0, 0, 64, 252, 64, 8, -2, ''),
+    (1, 0, 0, 263168, 1408, 1408, 10, 0, 'gemm_pq256<10>'), (0, 1, 0, 263168, 1408, 6144, 6, 0, 'gemm_pq256<6>'),
+    (6, 1, 0, 263168, 1408, 6144, 6, 0, 'gemm_p256<6, 64, false, 1>'), (8, 0, 0, 263168, 4224, 1408, 7, 0, 'gemm_pp256<7, 1>'),
+    (0, 65536, 0, 263168, 6144, 1408, 8, 0, 'gemm_pq256_dbg<8>'),
+    # split operands: t128x3 below 256 tiles of 256 x 256 (not for GELU_SPLIT2) or under X3_T128, which also allows 192-row tiles (4 * c3 <= 3 * c2)
+    (0, 0, 2, 65280, 256, 128, 4, 0, 'gemm_t128x3<4, 2>'), (0, 0, 2, 65536, 256, 128, 4, 0, 'gemm_pp256x3<4>'), (9, 0, 2, 65536, 256, 128, 3, 0, 'gemm_pq256x3<3>'),
+    (0, 0, 2, 1500, 768, 1536, 9, 0, 'gemm_pp256x3<9>'), (9, 1, 2, 1500, 768, 1536, 9, 0, 'gemm_pq256x3<9>'), (0, 0, 6, 1500, 3072, 1536, 9, 0, 'gemm_t128x3<9, 3>'),
+    (0, 0, 6, 1500, 768, 1536, 3, 0, 'gemm_t128x3<3, 2>'), (0, 0, 6, 192, 32768, 64, 4, 0, 'gemm_t128x3<4, 3>'), (0, 0, 6, 193, 32768, 64, 4, 0, 'gemm_t128x3<4, 2>'),
+    (0, 0, 2, 192, 32768, 64, 4, 0, 'gemm_t128x3<4, 2>'), (0, 0, 6, 65536, 256, 128, 3, 0, 'gemm_t128x3<3, 2>'),
+    # rejected: unknown epilogue, GELU_SPLIT2 without X3, X3 with an epilogue it has no kernel for
+    (0, 0, 0, 512, 4096, 64, 11, -1, ''), (0, 0, 0, 512, 4096, 64, -1, -1, ''), (0, 0, 0, 512, 4096, 64, 9, -1, ''), (0, 0, 2, 512, 4096, 64, 0, -1, ''),
+    (0, 0, 6, 512, 4096, 64, 7, -1, ''), (9, 0, 2, 512, 4096, 64, 10, -1, ''),
+]
+
+
+def test_gemm_dispatch_names_are_pinned(lib):
+    """hirest_gemm_dispatch_name over GEMM_DISPATCH_PIN: status and string equal the recorded ones (a rejected call leaves the buffer alone)."""
+    from hirest_amd import _lib
+    try:
+        for sel, dbg, flags, M, N, K, epi, status, name in GEMM_DISPATCH_PIN:
+            assert lib.hirest_gemm_select_kernel(sel) == 0 and lib.hirest_gemm_debug_mode(dbg) == 0
+            a = _lib.GemmArgs.make(1, K, 1, K, None, 1, N, M, N, K, epi)
+            a.flags = flags
+            buf = ctypes.create_string_buffer(64)
+            got = lib.hirest_gemm_dispatch_name(ctypes.byref(a), buf, 64)
+            assert (got, buf.value.decode()) == (status, name), (sel, dbg, flags, M, N, K, epi)
+        # the entry point's own arguments: NULL, a buffer under 48 bytes, another struct layout
+        a = _lib.GemmArgs.make(1, 64, 1, 64, None, 1, 4096, 512, 4096, 64, 0)
+        assert lib.hirest_gemm_dispatch_name(ctypes.byref(a), buf, 48) == 0
+        assert lib.hirest_gemm_dispatch_name(None, buf, 64) == -1 and lib.hirest_gemm_dispatch_name(ctypes.byref(a), None, 64) == -1
+        assert lib.hirest_gemm_dispatch_name(ctypes.byref(a), buf, 47) == -1
+        a.struct_size -= 8
+        assert lib.hirest_gemm_dispatch_name(ctypes.byref(a), buf, 64) == -1
+    finally:
+        lib.hirest_gemm_select_kernel(0)
+        lib.hirest_gemm_debug_mode(0)
+
+
 def test_joint_inference_entry_points_refuse_bad_arguments_without_gpu(lib):
     """The inference entry points of the joint model (csrc/joint.hip, csrc/caption.hip) check their arguments before any launch:
     NULL pointers, non-positive sizes, E or D not a positive multiple of 4, nheads outside 1..3 or a missing weight of a used head,
