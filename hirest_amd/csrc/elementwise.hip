@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const int64_t* __rest
         *reinterpret_cast<f32x4*>(o + 4 * c) = *reinterpret_cast<const f32x4*>(e + 4 * c) + *reinterpret_cast<const f32x4*>(p + 4 * c);
     if (t == 0 && eot_row) {
         // argmax over the L token ids, first maximum (torch.argmax semantics on distinct maxima)
-        int64_t best = -1; int bi = 0;
+        int64_t best = INT64_MIN; int bi = 0;       // below every id: a row of negative ids has its argmax too (idle lanes keep position 0)
         for (int i = lane; i < L; i += 64) {
             const int64_t v = tokens[(int64_t)b * L + i];
             if (v > best) { best = v; bi = i; }
@@ -437,7 +437,7 @@ extern "C" int hirest_fold_layernorm(const float* W, const float* gamma, const f
 
 extern "C" int hirest_write_cls_rows(float* x, int64_t ldx, const float* cls, const float* pos0, int32_t B,
                                      int32_t tokens_per_frame, int32_t D, void* stream) {
-    if (!x || !cls || !pos0 || B <= 0) return HIREST_E_BADARG;
+    if (!x || !cls || !pos0 || B <= 0 || tokens_per_frame <= 0 || D <= 0) return HIREST_E_BADARG;
     if (D % 4 != 0 || ldx % 4 != 0) return HIREST_E_SHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(cls_rows_kernel, dim3(grid_for((int64_t)B * (D / 4))), dim3(256), 0, s, x, ldx, cls, pos0, B,
@@ -447,8 +447,8 @@ extern "C" int hirest_write_cls_rows(float* x, int64_t ldx, const float* cls, co
 
 extern "C" int hirest_embed_tokens(const int64_t* tokens, const float* tok_emb, const float* pos, float* x,
                                    int32_t* eot_row, int32_t B, int32_t L, int32_t D, int32_t vocab, void* stream) {
-    if (!tokens || !tok_emb || !pos || !x || B <= 0 || L <= 0) return HIREST_E_BADARG;
-    if (D % 4 != 0) return HIREST_E_SHAPE;
+    if (!tokens || !tok_emb || !pos || !x || B <= 0 || L <= 0 || D <= 0 || vocab <= 0) return HIREST_E_BADARG;   // vocab <= 0: the id clamp would read in front of the table
+    if (D % 4 != 0 || (int64_t)B * L > INT32_MAX) return HIREST_E_SHAPE;                                       // the kernel indexes rows in int32
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(embed_tokens_kernel, dim3((B * L + 3) / 4), dim3(256), 0, s, tokens, tok_emb, pos, x, eot_row, B, L, D, vocab);
     return hirest_launch_status();

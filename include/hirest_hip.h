@@ -214,7 +214,9 @@ int hirest_patchify(const void* frames, int32_t in_dtype, int32_t B, int32_t S, 
  * Wf = bf16(W * gamma) [N, K], colsum_out[n] = sum_k Wf[n][k] (of the rounded values), bias_out = bias + W beta (bias NULL = 0). */
 int hirest_fold_layernorm(const float* W, const float* gamma, const float* beta, const float* bias, hirest_bf16* Wf,
                           float* bias_out, float* colsum_out, int32_t N, int32_t K, void* stream);
-/* x[b*(P+1)] = cls + pos[0]  for every frame (vit_model.py:330-333, the CLS row). */
+/* x[b*(P+1)] = cls + pos[0]  for every frame (vit_model.py:330-333, the CLS row): row b * tokens_per_frame of x (row stride ldx)
+ * for b < B, no other row is touched.  HIREST_E_BADARG for a NULL pointer, B <= 0, tokens_per_frame <= 0 or D <= 0; D % 4 == 0 and
+ * ldx % 4 == 0 (HIREST_E_SHAPE). */
 int hirest_write_cls_rows(float* x, int64_t ldx, const float* cls, const float* pos0,
                           int32_t B, int32_t tokens_per_frame, int32_t D, void* stream);
 
@@ -237,7 +239,10 @@ int hirest_ln_stats_finalize(const float* partials, int32_t groups, float* stats
                              float* guard, void* stream);
 
 /* Text prologue: x[b,t,:] = tok_emb[tok[b,t]] + pos[t]  (eva_model.py:233-235); also writes
- * eot_row[b] = b*L + argmax_t tok[b,t] (first maximum) for the EOT gather (eva_model.py:243). */
+ * eot_row[b] = b*L + argmax_t tok[b,t] (first maximum) for the EOT gather (eva_model.py:243); eot_row NULL skips that.
+ * An id outside the table is clamped, not refused: id < 0 reads row 0, id >= vocab reads row vocab - 1 (the argmax is taken over
+ * the ids as given).  HIREST_E_BADARG for a NULL pointer (other than eot_row), B <= 0, L <= 0, D <= 0 or vocab <= 0;
+ * HIREST_E_SHAPE for D % 4 != 0 or B * L > INT32_MAX. */
 int hirest_embed_tokens(const int64_t* tokens, const float* tok_emb, const float* pos,
                         float* x, int32_t* eot_row, int32_t B, int32_t L, int32_t D,
                         int32_t vocab, void* stream);
@@ -248,11 +253,13 @@ int hirest_f32_to_bf16(const float* in, hirest_bf16* out, int64_t n, void* strea
 /* ------------------------------------------------------------------------------------
  * Pooling + scoring (inference_video_retrieval.py:283-285, 323-334; evaluate.py:58-60)
  * ------------------------------------------------------------------------------------ */
-/* [V,F,E] f32 -> [V,E] f32: (optional per-frame L2) -> mean over F -> L2.  F==1 is plain L2. */
+/* [V,F,E] f32 -> [V,E] f32: (optional per-frame L2) -> mean over F -> L2.  F==1 is plain L2.
+ * E % 4 == 0 and F <= 8192 (the per-frame norms live in LDS), else HIREST_E_SHAPE. */
 int hirest_pool_l2norm(const float* frame_embeds, float* out, int32_t V, int32_t F, int32_t E,
                        int32_t normalize_frames_first, void* stream);
 /* ragged form: out[v] = L2-normalised mean of rows seg_off[v] .. seg_off[v+1] of a packed [rows, E] matrix (seg_off: V + 1 device
- * ints; an empty segment gives zeros).  sentence-transformers' Pooling(mean over the attention mask) + Normalize. */
+ * ints; an empty segment gives zeros).  sentence-transformers' Pooling(mean over the attention mask) + Normalize.  E % 4 == 0; a segment
+ * may have any length. */
 int hirest_pool_l2norm_varlen(const float* rows, const int32_t* seg_off, float* out, int32_t V, int32_t E, void* stream);
 
 /* scores[q][v] = <T[q], Vn[v]> in fp32 FMA arithmetic. */
@@ -260,7 +267,8 @@ int hirest_similarity_f32(const float* text_n, const float* video_n, float* scor
                           int32_t Q, int32_t V, int32_t E, void* stream);
 
 /* Per-query top-k by (score desc, tie_rank desc); tie_rank NULL -> ties by higher index first
- * = the reference's sorted(zip(scores, names))[::-1] when tie_rank[v] = rank of names[v]. */
+ * = the reference's sorted(zip(scores, names))[::-1] when tie_rank[v] = rank of names[v].  1 <= k <= V.  Scores may be +-inf
+ * (they order like any other value) but must not be NaN: a NaN compares with nothing and the selection is then unspecified. */
 int hirest_topk_f32(const float* scores, const int32_t* tie_rank, int32_t Q, int32_t V, int32_t k,
                     int32_t* out_index, float* out_score, void* stream);
 /* The same selection for long rows (beam search over beams*vocab scores): per-chunk candidates in parallel, then a merge.

@@ -229,6 +229,115 @@ def test_train_entry_points_refuse_bad_arguments_without_gpu(lib):
     assert hb(X, 0, 8, 1, X, X) == BAD and hb(X, 4, 0, 1, X, X) == BAD
 
 
+def test_tower_row_and_scoring_entry_points_refuse_bad_arguments_without_gpu(lib):
+    """Every entry point of csrc/elementwise.hip and csrc/score.hip checks its arguments before any launch: each required pointer
+    NULL in turn and each size zero or negative give HIREST_E_BADARG (-1), each documented shape rule broken once HIREST_E_SHAPE
+    (-2), a two-pass top-k workspace one byte short HIREST_E_WORKSPACE (-3).  The placeholder pointers X are never dereferenced:
+    each call below is refused by its checks alone.  The GPU tests of these kernels (test_gpu_tower_kernels.py) pass valid
+    arguments only."""
+    X = 1 << 20
+    BAD, SHAPE, WS = -1, -2, -3
+
+    def each_null(n, call, code=BAD):
+        for i in range(n):
+            ptrs = [X] * n
+            ptrs[i] = None
+            assert call(*ptrs) == code, i
+
+    # layernorm(x, ldx, row_index, gamma, beta, eps, out, ldo, out_is_f32, rows, D): D % 4 == 0, D <= 8192, ldx % 4 == ldo % 4 == 0
+    ln = lambda x, g, b, o, rows=4, D=768, ldx=768, ldo=768, f32=1: lib.hirest_layernorm(x, ldx, None, g, b, 1e-5, o, ldo, f32, rows, D, None)
+    each_null(4, ln)
+    assert ln(X, X, X, X, rows=0) == BAD and ln(X, X, X, X, rows=-3) == BAD
+    for D in (0, -4, 6, 8196):
+        assert ln(X, X, X, X, D=D, ldx=8200, ldo=8200) == SHAPE, D
+        assert ln(X, X, X, X, D=D, ldx=8200, ldo=8200, f32=0, rows=9000) == SHAPE, D
+    assert ln(X, X, X, X, ldx=770) == SHAPE and ln(X, X, X, X, ldo=770) == SHAPE
+    # combine_hi_lo(hi, lo, ld_in, out, ldo, rows, D)
+    ch = lambda hi, lo, o, rows=4, D=768, ld_in=768, ldo=768: lib.hirest_combine_hi_lo_f32(hi, lo, ld_in, o, ldo, rows, D, None)
+    each_null(3, ch)
+    assert ch(X, X, X, rows=0) == BAD and ch(X, X, X, rows=-1) == BAD and ch(X, X, X, D=0) == BAD and ch(X, X, X, D=-4) == BAD
+    assert ch(X, X, X, D=6) == SHAPE and ch(X, X, X, ld_in=770) == SHAPE and ch(X, X, X, ldo=770) == SHAPE
+    # rowstats(x, ldx, xb, stats, eps, rows, D, guard) / rowstats_split(x, ldx, xb, xlo, stats, ...): D % 4 == 0, D <= 1536; xlo, guard optional
+    rs = lambda x, xb, st, rows=4, D=768, ldx=768: lib.hirest_rowstats_bf16(x, ldx, xb, st, 1e-6, rows, D, None, None)
+    rs2 = lambda x, xb, st, rows=4, D=768, ldx=768: lib.hirest_rowstats_split_bf16(x, ldx, xb, X, st, 1e-6, rows, D, X, None)
+    for fn in (rs, rs2):
+        each_null(3, fn)
+        assert fn(X, X, X, rows=0) == BAD and fn(X, X, X, rows=-1) == BAD
+        for D in (0, -4, 6, 1540):
+            assert fn(X, X, X, D=D, ldx=1544) == SHAPE, D
+        assert fn(X, X, X, ldx=770) == SHAPE
+    # ln_stats_finalize(partials, groups, stats, eps, rows, D, guard)
+    fz = lambda p, st, groups=44, rows=4, D=1408: lib.hirest_ln_stats_finalize(p, groups, st, 1e-6, rows, D, None, None)
+    each_null(2, fz)
+    for kw in ({"groups": 0}, {"groups": -1}, {"rows": 0}, {"rows": -1}, {"D": 0}, {"D": -4}):
+        assert fz(X, X, **kw) == BAD, kw
+    # patchify(frames, in_dtype, B, S, P, mean3, std3, patches, Kpad): S % P == 0, Kpad % 8 == 0, Kpad >= 3 P P; dtype 2 needs mean / std
+    pf = lambda fr, out, dt=0, B=2, S=224, P=14, Kpad=640, m=X, s=X: lib.hirest_patchify(fr, dt, B, S, P, m, s, out, Kpad, None)
+    each_null(2, pf)
+    for kw in ({"B": 0}, {"B": -1}, {"S": 0}, {"S": -224}, {"P": 0}, {"P": -14}, {"dt": 3}, {"dt": -1}, {"dt": 2, "m": None}, {"dt": 2, "s": None}):
+        assert pf(X, X, **kw) == BAD, kw
+    for kw in ({"S": 225}, {"Kpad": 636}, {"Kpad": 584}, {"P": 16, "Kpad": 760}):
+        assert pf(X, X, **kw) == SHAPE, kw
+    # fold_layernorm(W, gamma, beta, bias, Wf, bias_out, colsum_out, N, K): bias optional
+    fl = lambda W, g, b, Wf, bo, so, N=8, K=768: lib.hirest_fold_layernorm(W, g, b, None, Wf, bo, so, N, K, None)
+    each_null(6, fl)
+    for kw in ({"N": 0}, {"N": -1}, {"K": 0}, {"K": -1}):
+        assert fl(X, X, X, X, X, X, **kw) == BAD, kw
+    # write_cls_rows(x, ldx, cls, pos0, B, tokens_per_frame, D)
+    wc = lambda x, c, p, B=2, T=257, D=768, ldx=768: lib.hirest_write_cls_rows(x, ldx, c, p, B, T, D, None)
+    each_null(3, wc)
+    for kw in ({"B": 0}, {"B": -1}, {"T": 0}, {"T": -1}, {"D": 0}, {"D": -4}):
+        assert wc(X, X, X, **kw) == BAD, kw
+    assert wc(X, X, X, D=6) == SHAPE and wc(X, X, X, ldx=770) == SHAPE
+    # embed_tokens(tokens, tok_emb, pos, x, eot_row, B, L, D, vocab): eot_row optional; vocab <= 0 would clamp ids in front of the table
+    et = lambda t, e, p, x, B=2, L=77, D=512, vocab=49408: lib.hirest_embed_tokens(t, e, p, x, None, B, L, D, vocab, None)
+    each_null(4, et)
+    for kw in ({"B": 0}, {"B": -1}, {"L": 0}, {"L": -1}, {"D": 0}, {"D": -4}, {"vocab": 0}, {"vocab": -1}):
+        assert et(X, X, X, X, **kw) == BAD, kw
+    assert et(X, X, X, X, D=6) == SHAPE
+    assert et(X, X, X, X, B=65536, L=32768) == SHAPE and et(X, X, X, X, B=2 ** 31 - 1, L=2 ** 31 - 1) == SHAPE    # B * L > INT32_MAX
+    # f32_to_bf16(in, out, n): n % 4 == 0
+    each_null(2, lambda a, b: lib.hirest_f32_to_bf16(a, b, 8, None))
+    assert lib.hirest_f32_to_bf16(X, X, 0, None) == BAD and lib.hirest_f32_to_bf16(X, X, -4, None) == BAD
+    assert lib.hirest_f32_to_bf16(X, X, 6, None) == SHAPE
+    # pool_l2norm(frame_embeds, out, V, F, E, normalize_frames_first): E % 4 == 0, F <= 8192
+    pl = lambda fe, o, V=3, F=32, E=1024: lib.hirest_pool_l2norm(fe, o, V, F, E, 0, None)
+    each_null(2, pl)
+    for kw in ({"V": 0}, {"V": -1}, {"F": 0}, {"F": -1}, {"E": 0}, {"E": -4}):
+        assert pl(X, X, **kw) == BAD, kw
+    assert pl(X, X, E=6) == SHAPE and pl(X, X, F=8193) == SHAPE
+    # pool_l2norm_varlen(rows, seg_off, out, V, E)
+    pv = lambda r, s, o, V=3, E=384: lib.hirest_pool_l2norm_varlen(r, s, o, V, E, None)
+    each_null(3, pv)
+    for kw in ({"V": 0}, {"V": -1}, {"E": 0}, {"E": -4}):
+        assert pv(X, X, X, **kw) == BAD, kw
+    assert pv(X, X, X, E=6) == SHAPE
+    # similarity(text_n, video_n, scores, Q, V, E)
+    sm = lambda t, v, s, Q=3, V=5, E=1024: lib.hirest_similarity_f32(t, v, s, Q, V, E, None)
+    each_null(3, sm)
+    for kw in ({"Q": 0}, {"Q": -1}, {"V": 0}, {"V": -1}, {"E": 0}, {"E": -1}):
+        assert sm(X, X, X, **kw) == BAD, kw
+    # topk(scores, tie_rank, Q, V, k, out_index, out_score): tie_rank, out_score optional; 1 <= k <= V
+    tk = lambda s, oi, Q=3, V=100, k=10: lib.hirest_topk_f32(s, None, Q, V, k, oi, None, None)
+    tw = lambda s, oi, Q=3, V=100, k=10, ws=X, nb=1 << 30: lib.hirest_topk_f32_ws(s, None, Q, V, k, oi, None, ws, nb, None)
+    for fn in (tk, tw):
+        each_null(2, fn)
+        for kw in ({"Q": 0}, {"Q": -1}, {"V": 0}, {"V": -1}, {"k": 0}, {"k": -1}, {"k": 101}):
+            assert fn(X, X, **kw) == BAD, kw
+    for dims in ((0, 100, 10), (3, 0, 10), (3, 100, 0), (-1, 100, 10)):
+        assert lib.hirest_topk_workspace_bytes(*dims) == BAD, dims
+    assert lib.hirest_topk_workspace_bytes(5, 152620, 5) == 5 * 38 * 5 * 12          # (score, tie key, index) per chunk candidate
+    need = lib.hirest_topk_workspace_bytes(3, 16387, 10)                              # five chunks: the two-pass form
+    assert need == 3 * 5 * 10 * 12
+    assert tw(X, X, V=16387, nb=need - 1) == WS and tw(X, X, V=16387, ws=None, nb=need) == WS and tw(X, X, V=16387, nb=0) == WS
+    assert tw(X, X, V=12289, nb=3 * 4 * 10 * 12 - 1) == WS                            # four chunks: the first length that needs it
+    # clip_score(img_rows, img_dtype, U, txt_rows, txt_dtype, sel, C, K, E, out)
+    cs = lambda img, txt, sel, out, idt=0, tdt=1, U=8, C=4, K=3, E=512: lib.hirest_clip_score(img, idt, U, txt, tdt, sel, C, K, E, out, None)
+    each_null(4, cs)
+    for kw in ({"idt": 2}, {"idt": -1}, {"tdt": 2}, {"U": 0}, {"C": -1}, {"K": 0}, {"E": 0}):
+        assert cs(X, X, X, X, **kw) == BAD, kw
+
+
 def test_workspace_size_formula(lib):
     from hirest_amd import _lib
     t = _lib.VisionTower()

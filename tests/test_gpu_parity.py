@@ -158,8 +158,9 @@ def test_patchify_uint8_fused_normalize(dev, ops):
     want = img.reshape(B, 3, 16, P, 16, P).permute(0, 2, 4, 1, 3, 5).reshape(B * 256, 588).to(torch.bfloat16)
     patches = torch.empty((B * 256, kpad), dtype=torch.bfloat16, device=dev)
     ops.patchify(torch.from_numpy(u).to(dev), P, kpad, patches, mean.to(dev), std.to(dev))
-    d = (patches[:, :588].float().cpu() - want.float()).abs().max().item()
-    assert d <= 2 ** -6  # at most one bf16 ulp at |x| < 2.7 (fp32 op-order differences before rounding)
+    # bit equality: with CLIP's mean / std every one of the 256 x 3 values lies more than ten fp32 error bounds away from a bf16 rounding
+    # midpoint, so no fp32 evaluation order changes the bf16 result (derived in test_gpu_tower_kernels.py::test_patchify_uint8_exhaustive_bit_exact)
+    assert torch.equal(patches[:, :588].cpu().view(torch.int16), want.view(torch.int16))
 
 
 @pytest.mark.parametrize("rows,D,eps", [(257 * 2, 1408, 1e-6), (77, 768, 1e-5), (10, 512, 1e-12), (5, 384, 1e-5), (9, 6144, 1e-5),
