@@ -126,6 +126,15 @@ class SplitItem(C.Structure):
                 ("transposed", C.c_int32), ("reserved", C.c_int32)]
 
 
+class OptimItem(C.Structure):
+    """hirest_optim_item (include/hirest_hip.h)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
+
+
+OPTIM_GROUP_MAX = 64     # HIREST_OPTIM_GROUP_MAX
+OPTIM_CHUNK = 8192       # HIREST_OPTIM_CHUNK
+
+
 class TrainBlock(C.Structure):
     """hirest_train_block (include/hirest_hip.h): one post-LN encoder block in train mode, forward + what its backward needs."""
     _fields_ = [("struct_size", C.c_uint64)] + [(n, C.c_int32) for n in ("B", "T", "heads", "width", "mlp", "precision")] + \
@@ -298,6 +307,11 @@ _SIGNATURES = {
     "hirest_train_block_forward": (C.c_int, [C.POINTER(TrainBlock), C.c_void_p, C.c_size_t, C.c_void_p]),
     "hirest_train_block_backward_scratch_bytes": (C.c_size_t, [C.POINTER(TrainBlock)]),
     "hirest_train_block_backward": (C.c_int, [C.POINTER(TrainBlock), C.POINTER(TrainBlockGrads), C.c_void_p]),
+    "hirest_optim_partials_count": (C.c_int64, [C.c_void_p, C.c_int32]),
+    "hirest_grad_sqnorm_grouped_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "hirest_clip_coef_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    "hirest_adamw_grouped_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                           C.c_float, C.c_float, C.c_void_p]),
     "hirest_weighted_colsum_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "hirest_scale_by_device_scalar_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "hirest_act_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),

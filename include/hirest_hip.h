@@ -1006,6 +1006,46 @@ int hirest_train_block_forward(const hirest_train_block* b, void* scratch, size_
 size_t hirest_train_block_backward_scratch_bytes(const hirest_train_block* b);
 int hirest_train_block_backward(const hirest_train_block* b, const hirest_train_block_grads* g, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Optimizer step of the training loop (run.py:264-295, trainer_base.py:55-61): torch.nn.utils.clip_grad_norm_ followed by
+ * torch.optim.AdamW.step(), fp32, for a table of parameter tensors per launch.  The update reads p, g, exp_avg, exp_avg_sq and
+ * writes p, exp_avg, exp_avg_sq once each (28 B per element); the clip adds one read of g (4 B).  Nothing is read back to the host.
+ *
+ * `items` is a HOST array of at most HIREST_OPTIM_GROUP_MAX tensors, copied into the kernel arguments (no device copy of the table:
+ * gradient pointers change every step); the tensors must stay alive until the call has executed on `stream`.  Item i is cut into
+ * ceil(n_i / HIREST_OPTIM_CHUNK) chunks of HIREST_OPTIM_CHUNK elements (the last one shorter); chunk c of item i is workgroup
+ * (chunks of items 0 .. i-1) + c of the launch.  A chunk never spans two tensors.  Tensors may start at any 4-byte boundary and have
+ * any length: each chunk is a scalar head up to the first 16-byte boundary, a body of 16-byte accesses and a scalar tail.
+ * Every entry returns HIREST_E_BADARG for a NULL table or pointer, count <= 0, count > HIREST_OPTIM_GROUP_MAX or n <= 0, and
+ * HIREST_E_SHAPE for more than 2^31 - 1 chunks, before any launch.
+ * ------------------------------------------------------------------------------------ */
+#define HIREST_OPTIM_GROUP_MAX 64
+#define HIREST_OPTIM_CHUNK 8192
+typedef struct hirest_optim_item {
+    float*       p;    /* parameter [n], updated in place            (unused by hirest_grad_sqnorm_grouped_f32, may be NULL there) */
+    const float* g;    /* gradient [n], never written                                                                            */
+    float*       m;    /* exp_avg [n], updated in place              (unused by the norm, may be NULL there)                      */
+    float*       v;    /* exp_avg_sq [n], updated in place           (unused by the norm, may be NULL there)                      */
+    int64_t      n;    /* elements                                                                                               */
+} hirest_optim_item;
+/* number of chunks (= workgroups of either grouped launch = partial sums the norm writes) of a table; < 0: the errors above */
+int64_t hirest_optim_partials_count(const hirest_optim_item* items, int32_t count);
+/* partials[w] = sum of g^2 over chunk w, for w < hirest_optim_partials_count(items, count).  Fixed summation order, no atomics: the
+ * same gradients at the same addresses give the same bits. */
+int hirest_grad_sqnorm_grouped_f32(const hirest_optim_item* items, int32_t count, float* partials, void* stream);
+/* norm_coef[0] = total_norm = sqrt(sum of partials[0 .. count-1]) (added in index order per thread, then a fixed tree, in double);
+ * norm_coef[1] = min(1, max_norm / (total_norm + 1e-6)) in fp32: clip_grad_norm_'s coefficient (error_if_nonfinite = False).
+ * One workgroup; both results are device floats. */
+int hirest_clip_coef_f32(const float* partials, int64_t count, float max_norm, float* norm_coef, void* stream);
+/* torch.optim.AdamW's update (the arithmetic of its default, non-capturable path, in its order) with g' = coef[0] * g
+ * (coef: one device float, e.g. norm_coef + 1 above; NULL = 1):
+ *     p *= decay;  m += one_minus_beta1 * (g' - m);  v = beta2 * v + one_minus_beta2 * g'^2;
+ *     p -= step_size * (m / (sqrt(v) / bc2_sqrt + eps))
+ * The caller derives the scalars in double from the step count t, as torch does: decay = 1 - lr * weight_decay,
+ * step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t) (> 0, else HIREST_E_BADARG). */
+int hirest_adamw_grouped_f32(const hirest_optim_item* items, int32_t count, const float* coef, float decay, float one_minus_beta1,
+                             float beta2, float one_minus_beta2, float step_size, float bc2_sqrt, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
