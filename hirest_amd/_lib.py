@@ -355,6 +355,11 @@ _SIGNATURES = {
     "hirest_jpeg_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int64, C.c_void_p]),
     "hirest_jpeg_decode_host": (C.c_int, [C.POINTER(JpegImage), C.POINTER(JpegTables), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "hirest_jpeg_chunked_workspace_bytes": (C.c_int64, [C.c_int32]),
+    "hirest_jpeg_decode_chunked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hirest_jpeg_decode_host_chunked": (C.c_int, [C.POINTER(JpegImage), C.POINTER(JpegTables), C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hirest_interval_iou_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "hirest_step_bound_pr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -9,6 +9,9 @@
 //   jpeg_entropy_kernel   one lane per image, 16 per workgroup: Huffman decode of the whole scan (tables in LDS) -> int16
 //                         coefficient blocks in component-plane block order; per-image status word.  Bounds the decoder
 //                         (99.8 % of its GPU time).
+//   jpeg_entropy_chunked_kernel  (hirest_jpeg_decode_chunked) the same coefficients from one workgroup of up to 1024 lanes per
+//                         image, one lane per chunk of the scan, synchronised by re-entering from the neighbour's exit; images
+//                         with a restart interval go to jpeg_entropy_restart_kernel, the one-lane code.
 //   jpeg_idct_kernel      32 blocks per workgroup, one thread per block column (pass 1) and row (pass 2) ->
 //                         uint8 component planes (MCU-padded).
 //   jpeg_color_kernel     16 output pixels per thread: fancy upsampling + YCbCr -> RGB, 16-byte stores into the
@@ -85,6 +88,94 @@ JPG_HD int decode_scan(const hirest_jpeg_image& d, const uint8_t* file, const jp
         }
     }
     return br.status;
+}
+
+// ---- chunked entropy decode (restart_interval == 0): many lanes per image ----
+// The scan is cut into chunks of `cb` bytes, one lane each.  A lane owns the blocks whose first bit lies in its chunk and
+// decodes each of them to its end.  Sync pass: lane 0 enters at scan_begin, every other lane guesses that a block (the first
+// of an MCU) starts at its first bit; each records where it leaves (the first block start at or past its chunk's end), how
+// many blocks it owns and the sums of their DC differences.  Then lane i + 1 re-enters from lane i's exit until no exit
+// changes: lane 0 is exact, so after r rounds lanes 0 .. r - 1 are, and the fixed point is the serial decode.  An exclusive
+// scan of (blocks, DC sums) gives each lane its first block and predictors, and the write pass decodes the owned blocks again,
+// this time with output.  Blocks past the image's last one (the padding bits can look like one) are nobody's.
+constexpr int CHUNK_MAX_LANES = 1024;   // lanes of one image = threads of its workgroup
+constexpr int CHUNK_MIN_BYTES = 256;    // chosen chunk size: not below this (a lane runs on into the next chunk to the end of
+                                        // its last block, and a wrong guess costs a round)
+
+// chunk size for a scan of `len` bytes: the caller's, else the smallest >= CHUNK_MIN_BYTES that fits max_lanes; a caller's
+// size that needs more than max_lanes is raised to fit
+JPG_HD int64_t chunk_size(int64_t len, int64_t want, int64_t max_lanes) {
+    const int64_t fit = (len + max_lanes - 1) / max_lanes;
+    const int64_t cb = want > 0 ? want : CHUNK_MIN_BYTES;
+    return cb > fit ? cb : fit;
+}
+
+// a lane's entry or exit: bit position (jpg::BitReader::bit_position) * 8 + index of the block inside its MCU
+JPG_HD int64_t chunk_state(int64_t bitpos, int b) { return bitpos * 8 + b; }
+
+// the first guess of lane `lane`: its chunk's first byte, or the next one if that is the stuffed 0x00 of an 0xFF
+JPG_HD int64_t chunk_guess(const hirest_jpeg_image& d, const uint8_t* file, int64_t cb, int64_t lane) {
+    int64_t s = d.scan_begin + lane * cb;
+    if (lane > 0 && file[s] == 0 && file[s - 1] == 0xFF) ++s;
+    return chunk_state(s * 8, 0);
+}
+
+struct ChunkOut {
+    int64_t exit;        // chunk_state where the lane stopped
+    int32_t nown;        // blocks decoded
+    int32_t dc[3];       // predictors after the last block (sync pass: from 0, i.e. the sums of the DC differences)
+    int32_t status;
+};
+
+// One lane: enters at `entry`, decodes blocks while they start before bit `end_bits`.  WRITE: `first` is the scan-order
+// index of its first block and o->dc its predictors; blocks go through blk / done as in decode_scan and the lane stops at
+// the image's last block.  Without WRITE nothing is stored and anomalies are not reported.
+template <bool WRITE, class Block, class Done>
+JPG_HD void decode_chunk(const hirest_jpeg_image& d, const Geo& g, const uint8_t* file, const jpg::DTable* dt, const uint8_t* nat,
+                         int64_t entry, int64_t end_bits, int64_t first, ChunkOut* o, Block&& blk, Done&& done) {
+    const int ny = d.hs * d.vs, per_mcu = ny + (d.ncomp == 3 ? 2 : 0);
+    jpg::BitReader br;
+    br.enter(file, d.scan_begin, d.scan_end, entry >> 3);
+    int b = (int)(entry & 7), n = 0;
+    int mx = 0, my = 0;
+    if (WRITE) {
+        const int64_t mcu = first / per_mcu;
+        b = (int)(first - mcu * per_mcu);      // equal to the entry's once the sync pass has converged; this one bounds the stores
+        my = (int)(mcu / d.mcux);
+        mx = (int)(mcu - (int64_t)my * d.mcux);
+    }
+    int p0 = o->dc[0], p1 = o->dc[1], p2 = o->dc[2];      // scalars, not o->dc[c]: an indexed array would live in scratch
+    int64_t at = entry >> 3;
+    for (;;) {
+        if (br.marker && br.nbits <= br.fake) at = d.scan_end * 8;
+        else if (br.pos * 8 >= end_bits) at = br.bit_position();      // near the end of the chunk: the exact position
+        else at = 0;                                                  // before it: position <= 8 * pos < end_bits
+        if (at >= end_bits || (WRITE && first + n >= g.nblocks)) break;
+        const int c = b < ny ? 0 : b - ny + 1;
+        int pred = c == 0 ? p0 : (c == 1 ? p1 : p2);
+        if (WRITE) {
+            int64_t bi;
+            if (c == 0) bi = (int64_t)(my * d.vs + (b >> (d.hs - 1))) * g.bw0 + mx * d.hs + (b & (d.hs - 1));
+            else bi = (c == 1 ? g.off1 : g.off2) + (int64_t)my * d.mcux + mx;
+            int16_t* out = blk(bi);
+            jpg::decode_block(br, dt + 2 * c, dt + 2 * c + 1, pred, [&](int k, int v) { out[nat[k]] = (int16_t)v; });
+            done(bi);
+        } else {
+            jpg::decode_block(br, dt + 2 * c, dt + 2 * c + 1, pred, [](int, int) {});
+        }
+        if (c == 0) p0 = pred; else if (c == 1) p1 = pred; else p2 = pred;
+        ++n;
+        if (++b == per_mcu) {
+            b = 0;
+            if (++mx == d.mcux) { mx = 0; ++my; }
+        }
+    }
+    o->exit = chunk_state(at, b);
+    o->nown = n;
+    o->dc[0] = p0;
+    o->dc[1] = p1;
+    o->dc[2] = p2;
+    o->status = br.status;
 }
 
 // IDCT of block `bi` of an image: coef (dequantised by q, natural order) -> 8x8 samples of its plane
@@ -297,10 +388,13 @@ void host_dtables(const hirest_jpeg_tables* t, jpg::DTable* dt) {
 }
 
 // ------------------------------------------------------------------ kernels
-__global__ void __launch_bounds__(ENT_LANES) jpeg_entropy_kernel(const hirest_jpeg_image* __restrict__ imgs, int32_t first, int32_t count,
-                                                                 const hirest_jpeg_tables* __restrict__ tables, int32_t set,
-                                                                 const uint8_t* __restrict__ data, uint8_t* __restrict__ ws,
-                                                                 int32_t* __restrict__ status) {
+// One lane per image.  RESTART_ONLY (the chunked entry's launch for what its own kernel leaves alone): images without a restart
+// interval are skipped.
+template <bool RESTART_ONLY>
+__device__ __forceinline__ void entropy_lanes(const hirest_jpeg_image* __restrict__ imgs, int32_t first, int32_t count,
+                                              const hirest_jpeg_tables* __restrict__ tables, int32_t set,
+                                              const uint8_t* __restrict__ data, uint8_t* __restrict__ ws,
+                                              int32_t* __restrict__ status) {
     __shared__ jpg::DTable dt[6];
     __shared__ uint8_t nat[64];
     // each lane assembles its current block here and stores it with 8 x 16 B: scattered 2-byte global stores would make
@@ -320,6 +414,7 @@ __global__ void __launch_bounds__(ENT_LANES) jpeg_entropy_kernel(const hirest_jp
         status[first + i] = JPG_ST_UNSUPPORTED;
         return;
     }
+    if (RESTART_ONLY && d.restart_interval == 0) return;
     int16_t* coef = (int16_t*)(ws + d.ws_offset);
     uint4* mine = (uint4*)bb[t];
     const int st = decode_scan(
@@ -336,6 +431,129 @@ __global__ void __launch_bounds__(ENT_LANES) jpeg_entropy_kernel(const hirest_jp
             for (int j = 0; j < 8; ++j) g[j] = mine[j];
         });
     status[first + i] = st;
+}
+
+__global__ void __launch_bounds__(ENT_LANES) jpeg_entropy_kernel(const hirest_jpeg_image* __restrict__ imgs, int32_t first, int32_t count,
+                                                                 const hirest_jpeg_tables* __restrict__ tables, int32_t set,
+                                                                 const uint8_t* __restrict__ data, uint8_t* __restrict__ ws,
+                                                                 int32_t* __restrict__ status) {
+    entropy_lanes<false>(imgs, first, count, tables, set, data, ws, status);
+}
+
+__global__ void __launch_bounds__(ENT_LANES) jpeg_entropy_restart_kernel(const hirest_jpeg_image* __restrict__ imgs, int32_t first, int32_t count,
+                                                                         const hirest_jpeg_tables* __restrict__ tables, int32_t set,
+                                                                         const uint8_t* __restrict__ data, uint8_t* __restrict__ ws,
+                                                                         int32_t* __restrict__ status) {
+    entropy_lanes<true>(imgs, first, count, tables, set, data, ws, status);
+}
+
+// One workgroup per image of the run [first, first + gridDim.x), one lane per chunk (blockDim.x = the most lanes any image of
+// the run needs).  Exits and the scan go through LDS behind barriers; every lane stages its current block in LDS and stores it
+// whole, as jpeg_entropy_kernel does.  Images with a restart interval and unsupported ones are jpeg_entropy_restart_kernel's.
+// info[4 i ..]: chunk bytes, lanes, sync rounds, blocks found (capped) of image i.
+__global__ void __launch_bounds__(CHUNK_MAX_LANES) jpeg_entropy_chunked_kernel(const hirest_jpeg_image* __restrict__ imgs, int32_t first,
+                                                                               const hirest_jpeg_tables* __restrict__ tables, int32_t set,
+                                                                               const uint8_t* __restrict__ data, uint8_t* __restrict__ ws,
+                                                                               int32_t* __restrict__ status, int64_t chunk_bytes,
+                                                                               int32_t* __restrict__ info) {
+    __shared__ jpg::DTable dt[6];
+    __shared__ uint8_t nat[64];
+    __shared__ int32_t st_or;
+    // blockDim.x * 128 B: first the lanes' exits (8 B each) and the two scan buffers (16 B each), then the staged blocks
+    extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
+    const int t = threadIdx.x, T = blockDim.x;
+    const int i = first + blockIdx.x;
+    const hirest_jpeg_image d = imgs[i];
+    if (!d.supported || d.restart_interval != 0) return;          // uniform
+    const hirest_jpeg_tables* tb = tables + set;
+    if (t < 6) jpg::build_dtable(tb->huff_bits[t], tb->huff_vals[t], dt + t);
+    if (t < 64) nat[t] = kNatural[t];
+    if (t == 0) st_or = 0;
+    __syncthreads();
+    for (int e = t; e < 6 * 256; e += T) dt[e >> 8].look[e & 255] = jpg::look_entry(dt + (e >> 8), e & 255);
+    __syncthreads();
+    const Geo g = geo_of(d);
+    const uint8_t* file = data + d.data_offset;
+    const int64_t len = d.scan_end - d.scan_begin;
+    const int64_t cb = chunk_size(len, chunk_bytes, CHUNK_MAX_LANES);
+    const int lanes = (int)((len + cb - 1) / cb);                 // <= blockDim.x: the host sized the launch with the same rule
+    const int64_t end_bits = (t + 1 >= lanes ? d.scan_end : d.scan_begin + (int64_t)(t + 1) * cb) * 8;
+    int64_t* exits = (int64_t*)dyn;
+    auto none = [](int64_t) { return (int16_t*)nullptr; };
+    auto nop = [](int64_t) {};
+    // sync pass
+    int64_t entry = 0;
+    if (t < lanes) entry = t == 0 ? chunk_state(d.scan_begin * 8, 0) : chunk_guess(d, file, cb, t);
+    ChunkOut rec{};
+    bool need = t < lanes;
+    int rounds = 0;
+    for (int r = 0; r < lanes; ++r) {
+        if (!__syncthreads_or(need)) break;
+        ++rounds;
+        if (need) {
+            rec = ChunkOut{};
+            decode_chunk<false>(d, g, file, dt, nat, entry, end_bits, 0, &rec, none, nop);
+            exits[t] = rec.exit;
+        }
+        __syncthreads();
+        need = false;
+        if (t > 0 && t < lanes && exits[t - 1] != entry) {
+            entry = exits[t - 1];
+            need = true;
+        }
+    }
+    // exclusive scan over the lanes: first block and predictors of each
+    int4* sc = (int4*)(dyn + 8 * (size_t)T);
+    int4 own = t < lanes ? make_int4(rec.nown, rec.dc[0], rec.dc[1], rec.dc[2]) : make_int4(0, 0, 0, 0);
+    int4 acc = own;
+    int cur = 0;
+    sc[t] = acc;
+    __syncthreads();
+    for (int o = 1; o < T; o <<= 1) {
+        if (t >= o) {
+            const int4 v = sc[cur * T + t - o];
+            // unsigned: garbage can make the sums wrap, and the wrapped value is what the serial predictor holds too
+            acc = make_int4((int)((unsigned)acc.x + (unsigned)v.x), (int)((unsigned)acc.y + (unsigned)v.y),
+                            (int)((unsigned)acc.z + (unsigned)v.z), (int)((unsigned)acc.w + (unsigned)v.w));
+        }
+        cur ^= 1;
+        sc[cur * T + t] = acc;
+        __syncthreads();
+    }
+    const int found = sc[cur * T + T - 1].x;
+    __syncthreads();                                              // the staged blocks reuse this LDS
+    // write pass
+    if (t < lanes) {
+        int16_t* bb = (int16_t*)(dyn + 128 * (size_t)t);
+        uint4* mine = (uint4*)bb;
+        int16_t* coef = (int16_t*)(ws + d.ws_offset);
+        ChunkOut w{};
+        w.dc[0] = (int)((unsigned)acc.y - (unsigned)own.y);
+        w.dc[1] = (int)((unsigned)acc.z - (unsigned)own.z);
+        w.dc[2] = (int)((unsigned)acc.w - (unsigned)own.w);
+        decode_chunk<true>(
+            d, g, file, dt, nat, entry, end_bits, (int64_t)(acc.x - own.x), &w,
+            [&](int64_t) {
+                const uint4 z = make_uint4(0, 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) mine[j] = z;
+                return bb;
+            },
+            [&](int64_t bi) {
+                uint4* go = (uint4*)(coef + bi * COEF_STRIDE);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) go[j] = mine[j];
+            });
+        if (w.status) atomicOr(&st_or, w.status);
+    }
+    __syncthreads();
+    if (t == 0) {
+        status[i] = st_or | (found < g.nblocks ? JPG_ST_OUT_OF_DATA : 0);      // fewer blocks than the image has: the data ran out
+        info[4 * i] = (int32_t)cb;
+        info[4 * i + 1] = lanes;
+        info[4 * i + 2] = rounds;
+        info[4 * i + 3] = found;
+    }
 }
 
 __global__ void __launch_bounds__(IDCT_BLOCKS * 8) jpeg_idct_kernel(const hirest_jpeg_image* __restrict__ imgs,
@@ -453,29 +671,9 @@ extern "C" int64_t hirest_jpeg_workspace_bytes(hirest_jpeg_image* imgs, int32_t 
     return total;
 }
 
-extern "C" int hirest_jpeg_decode_host(const hirest_jpeg_image* img, const hirest_jpeg_tables* tables, const uint8_t* data,
-                                       uint8_t* out, int32_t* status) {
-    if (!img || !tables || !data || !out || !status) return HIREST_E_BADARG;
-    const hirest_jpeg_image& d = *img;
-    if (!d.supported) {
-        *status = JPG_ST_UNSUPPORTED;
-        return 0;
-    }
+// IDCT, upsampling and colour of one image on the CPU: coef = nblocks x 64 int16 in component-plane block order
+static void host_pixels(const hirest_jpeg_image& d, const hirest_jpeg_tables* tables, const std::vector<int16_t>& coef, uint8_t* out) {
     const Geo g = geo_of(d);
-    jpg::DTable dt[6];
-    host_dtables(tables, dt);
-    const uint8_t nat[64] = JPG_NATURAL_ORDER;
-    std::vector<int16_t> coef((size_t)g.nblocks * 64);
-    const int st = decode_scan(
-        d, data, dt, nat,
-        [&](int64_t bi) {
-            int16_t* b = coef.data() + bi * 64;
-            memset(b, 0, 128);
-            return b;
-        },
-        [](int64_t) {});
-    *status = st;
-    if (st) return 0;
     std::vector<uint8_t> planes((size_t)g.nblocks * 64);
     for (int64_t bi = 0; bi < g.nblocks; ++bi) {
         int comp, pitch;
@@ -503,16 +701,108 @@ extern "C" int hirest_jpeg_decode_host(const hirest_jpeg_image* img, const hires
             o[1] = (px >> 8) & 255;
             o[2] = (px >> 16) & 255;
         }
+}
+
+extern "C" int hirest_jpeg_decode_host(const hirest_jpeg_image* img, const hirest_jpeg_tables* tables, const uint8_t* data,
+                                       uint8_t* out, int32_t* status) {
+    if (!img || !tables || !data || !out || !status) return HIREST_E_BADARG;
+    const hirest_jpeg_image& d = *img;
+    if (!d.supported) {
+        *status = JPG_ST_UNSUPPORTED;
+        return 0;
+    }
+    const Geo g = geo_of(d);
+    jpg::DTable dt[6];
+    host_dtables(tables, dt);
+    const uint8_t nat[64] = JPG_NATURAL_ORDER;
+    std::vector<int16_t> coef((size_t)g.nblocks * 64);
+    const int st = decode_scan(
+        d, data, dt, nat,
+        [&](int64_t bi) {
+            int16_t* b = coef.data() + bi * 64;
+            memset(b, 0, 128);
+            return b;
+        },
+        [](int64_t) {});
+    *status = st;
+    if (st) return 0;
+    host_pixels(d, tables, coef, out);
     return 0;
 }
 
-extern "C" int hirest_jpeg_decode(const hirest_jpeg_image* imgs_host, const hirest_jpeg_image* imgs_dev, int32_t n,
-                                  const hirest_jpeg_tables* tables_dev, const uint8_t* data, uint8_t* out, int32_t* status,
-                                  void* workspace, int64_t workspace_bytes, void* stream) {
-    if (n == 0) return 0;
+// The chunked decode with the lanes run one after another: the same rounds as jpeg_entropy_chunked_kernel (every lane of a
+// round sees its neighbour's exit of the round before), so `rounds_out` is the device's count too.
+extern "C" int hirest_jpeg_decode_host_chunked(const hirest_jpeg_image* img, const hirest_jpeg_tables* tables, const uint8_t* data,
+                                               int64_t chunk_bytes, uint8_t* out, int32_t* status, int32_t* rounds_out) {
+    if (!img || !tables || !data || !out || !status || chunk_bytes < 0) return HIREST_E_BADARG;
+    const hirest_jpeg_image& d = *img;
+    if (rounds_out) *rounds_out = 0;
+    if (!d.supported) {
+        *status = JPG_ST_UNSUPPORTED;
+        return 0;
+    }
+    if (d.restart_interval != 0 || d.scan_end <= d.scan_begin) return HIREST_E_BADARG;   // restart intervals: hirest_jpeg_decode_host
+    const Geo g = geo_of(d);
+    jpg::DTable dt[6];
+    host_dtables(tables, dt);
+    const uint8_t nat[64] = JPG_NATURAL_ORDER;
+    const int64_t len = d.scan_end - d.scan_begin;
+    const int64_t cb = chunk_size(len, chunk_bytes, chunk_bytes > 0 ? len : CHUNK_MAX_LANES);   // a given size is kept as it is
+    const int64_t lanes = (len + cb - 1) / cb;
+    auto end_bits = [&](int64_t l) { return (l + 1 == lanes ? d.scan_end : d.scan_begin + (l + 1) * cb) * 8; };
+    auto none = [](int64_t) { return (int16_t*)nullptr; };
+    auto nop = [](int64_t) {};
+    std::vector<int64_t> entry(lanes), prev_exit(lanes);
+    std::vector<ChunkOut> rec(lanes);
+    int rounds = 0;
+    for (int64_t r = 0; r < lanes; ++r) {
+        for (int64_t l = 0; l < lanes; ++l) prev_exit[l] = rec[l].exit;
+        bool any = false;
+        for (int64_t l = 0; l < lanes; ++l) {
+            const int64_t e = r == 0 ? (l == 0 ? chunk_state(d.scan_begin * 8, 0) : chunk_guess(d, data, cb, l)) : (l == 0 ? entry[0] : prev_exit[l - 1]);
+            if (r > 0 && e == entry[l]) continue;
+            any = true;
+            entry[l] = e;
+            rec[l] = ChunkOut{};
+            decode_chunk<false>(d, g, data, dt, nat, e, end_bits(l), 0, &rec[l], none, nop);
+        }
+        if (!any) break;
+        ++rounds;
+    }
+    if (rounds_out) *rounds_out = rounds;
+    std::vector<int16_t> coef((size_t)g.nblocks * 64);
+    int st = 0;
+    int64_t first = 0;
+    int32_t pred[3] = {0, 0, 0};
+    for (int64_t l = 0; l < lanes; ++l) {
+        ChunkOut w{};
+        for (int c = 0; c < 3; ++c) w.dc[c] = pred[c];
+        decode_chunk<true>(
+            d, g, data, dt, nat, entry[l], end_bits(l), first, &w,
+            [&](int64_t bi) {
+                int16_t* b = coef.data() + bi * 64;
+                memset(b, 0, 128);
+                return b;
+            },
+            nop);
+        st |= w.status;
+        first += rec[l].nown;
+        for (int c = 0; c < 3; ++c) pred[c] += rec[l].dc[c];
+    }
+    if (first < g.nblocks) st |= JPG_ST_OUT_OF_DATA;      // the data ended before the image did
+    *status = st;
+    if (st) return 0;
+    host_pixels(d, tables, coef, out);
+    return 0;
+}
+
+// argument checks of the device entries; max_blocks / max_chunks size the IDCT and colour launches
+static int check_images(const hirest_jpeg_image* imgs_host, const hirest_jpeg_image* imgs_dev, int32_t n, const hirest_jpeg_tables* tables_dev,
+                        const uint8_t* data, uint8_t* out, int32_t* status, void* workspace, int64_t workspace_bytes, int64_t* max_blocks,
+                        int64_t* max_chunks) {
     if (!imgs_host || !imgs_dev || !tables_dev || !data || !out || !status || n < 0 || n > 65535) return HIREST_E_BADARG;
     if (((uintptr_t)workspace & 255) != 0 || ((uintptr_t)data & 7) != 0) return HIREST_E_BADARG;
-    int64_t max_blocks = 0, max_chunks = 0;
+    *max_blocks = *max_chunks = 0;
     for (int i = 0; i < n; ++i) {
         const hirest_jpeg_image& d = imgs_host[i];
         if (!d.supported) continue;
@@ -523,10 +813,31 @@ extern "C" int hirest_jpeg_decode(const hirest_jpeg_image* imgs_host, const hire
         if (d.table_set < 0 || d.data_offset < 0 || (d.data_offset & 7) || d.out_offset < 0 || d.scan_begin < 0 ||
             d.scan_end <= d.scan_begin)
             return HIREST_E_BADARG;
-        max_blocks = g.nblocks > max_blocks ? g.nblocks : max_blocks;
+        *max_blocks = g.nblocks > *max_blocks ? g.nblocks : *max_blocks;
         const int64_t ch = (int64_t)((d.width + 15) >> 4) * d.height;
-        max_chunks = ch > max_chunks ? ch : max_chunks;
+        *max_chunks = ch > *max_chunks ? ch : *max_chunks;
     }
+    return 0;
+}
+
+// coefficients -> frames of the images whose status is 0
+static int launch_pixels(const hirest_jpeg_image* imgs_dev, int32_t n, const hirest_jpeg_tables* tables_dev, uint8_t* out, int32_t* status,
+                         void* workspace, int64_t max_blocks, int64_t max_chunks, hipStream_t s) {
+    if (max_blocks == 0) return hirest_launch_status();
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS), n), dim3(IDCT_BLOCKS * 8), 0, s,
+                       imgs_dev, tables_dev, (uint8_t*)workspace, (const int32_t*)status);
+    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_chunks + COLOR_THREADS - 1) / COLOR_THREADS), n), dim3(COLOR_THREADS), 0, s,
+                       imgs_dev, (const uint8_t*)workspace, out, (const int32_t*)status);
+    return hirest_launch_status();
+}
+
+extern "C" int hirest_jpeg_decode(const hirest_jpeg_image* imgs_host, const hirest_jpeg_image* imgs_dev, int32_t n,
+                                  const hirest_jpeg_tables* tables_dev, const uint8_t* data, uint8_t* out, int32_t* status,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+    if (n == 0) return 0;
+    int64_t max_blocks = 0, max_chunks = 0;
+    const int rc = check_images(imgs_host, imgs_dev, n, tables_dev, data, out, status, workspace, workspace_bytes, &max_blocks, &max_chunks);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     // entropy decode: one launch per run of images sharing a table set (the caller groups them)
     for (int i = 0; i < n;) {
@@ -536,10 +847,54 @@ extern "C" int hirest_jpeg_decode(const hirest_jpeg_image* imgs_host, const hire
                            tables_dev, imgs_host[i].table_set, data, (uint8_t*)workspace, status);
         i = j;
     }
-    if (max_blocks == 0) return hirest_launch_status();
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS), n), dim3(IDCT_BLOCKS * 8), 0, s,
-                       imgs_dev, tables_dev, (uint8_t*)workspace, (const int32_t*)status);
-    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_chunks + COLOR_THREADS - 1) / COLOR_THREADS), n), dim3(COLOR_THREADS), 0, s,
-                       imgs_dev, (const uint8_t*)workspace, out, (const int32_t*)status);
-    return hirest_launch_status();
+    return launch_pixels(imgs_dev, n, tables_dev, out, status, workspace, max_blocks, max_chunks, s);
+}
+
+extern "C" int64_t hirest_jpeg_chunked_workspace_bytes(int32_t n) {
+    if (n < 0) return HIREST_E_BADARG;
+    return align256((int64_t)n * 16);
+}
+
+extern "C" int hirest_jpeg_decode_chunked(const hirest_jpeg_image* imgs_host, const hirest_jpeg_image* imgs_dev, int32_t n,
+                                          const hirest_jpeg_tables* tables_dev, const uint8_t* data, uint8_t* out, int32_t* status,
+                                          void* workspace, int64_t workspace_bytes, int64_t chunk_bytes, void* chunk_workspace,
+                                          int64_t chunk_workspace_bytes, void* stream) {
+    if (n == 0) return 0;
+    int64_t max_blocks = 0, max_chunks = 0;
+    const int rc = check_images(imgs_host, imgs_dev, n, tables_dev, data, out, status, workspace, workspace_bytes, &max_blocks, &max_chunks);
+    if (rc) return rc;
+    if (chunk_bytes < 0 || !chunk_workspace || ((uintptr_t)chunk_workspace & 15) != 0) return HIREST_E_BADARG;
+    if (chunk_workspace_bytes < hirest_jpeg_chunked_workspace_bytes(n)) return HIREST_E_WORKSPACE;
+    static HirestDevCfg cfg;
+    const int rc2 = hirest_configure(jpeg_entropy_chunked_kernel, CHUNK_MAX_LANES * 128, cfg);
+    if (rc2) return rc2;
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t me = hipMemsetAsync(chunk_workspace, 0, (size_t)n * 16, s);   // images the chunked kernel does not decode: all zero
+    if (me != hipSuccess) return (int)me;
+    for (int i = 0; i < n;) {
+        int j = i + 1;
+        while (j < n && imgs_host[j].table_set == imgs_host[i].table_set) ++j;
+        int64_t lanes = 0;
+        bool others = false;            // unsupported images (status only) and restart intervals: one lane per image
+        for (int k = i; k < j; ++k) {
+            const hirest_jpeg_image& d = imgs_host[k];
+            if (!d.supported || d.restart_interval != 0) {
+                others = true;
+                continue;
+            }
+            const int64_t len = d.scan_end - d.scan_begin, cb = chunk_size(len, chunk_bytes, CHUNK_MAX_LANES);
+            const int64_t l = (len + cb - 1) / cb;
+            lanes = l > lanes ? l : lanes;
+        }
+        if (lanes > 0) {
+            const int threads = (int)((lanes + 63) / 64 * 64);
+            hipLaunchKernelGGL(jpeg_entropy_chunked_kernel, dim3(j - i), dim3(threads), (size_t)threads * 128, s, imgs_dev, i, tables_dev,
+                               imgs_host[i].table_set, data, (uint8_t*)workspace, status, chunk_bytes, (int32_t*)chunk_workspace);
+        }
+        if (others)
+            hipLaunchKernelGGL(jpeg_entropy_restart_kernel, dim3((j - i + ENT_LANES - 1) / ENT_LANES), dim3(ENT_LANES), 0, s, imgs_dev, i, j - i,
+                               tables_dev, imgs_host[i].table_set, data, (uint8_t*)workspace, status);
+        i = j;
+    }
+    return launch_pixels(imgs_dev, n, tables_dev, out, status, workspace, max_blocks, max_chunks, s);
 }

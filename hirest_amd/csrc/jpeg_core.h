@@ -173,6 +173,32 @@ struct BitReader {
         skip(l);
         return t->vals[(code + t->valoff[l]) & 255];
     }
+    // ---- chunked decode: a position in the scan that a second reader can enter at ----
+    // The position of the next bit as 8 * (offset of the raw byte that holds it) + (bits of that byte already taken); a
+    // stuffed 0xFF counts at its 0xFF (the last one of a run of fill bytes).  8 * end once only padding is left.  The reader
+    // only knows `pos`, the next byte to load, so the bytes still buffered are walked back over: cheap, and only asked for
+    // near the end of a chunk.
+    JPG_HD int64_t bit_position() {
+        const int real = nbits - fake;                  // fake bits are the newest in the buffer
+        if (marker && real <= 0) return end * 8;
+        int64_t p = pos;
+        for (int m = (real + 7) >> 3; m > 0; --m) {
+            while (p - 1 > begin && at(p - 1) == 0xFF) --p;          // fill bytes: part of no data byte
+            p -= (p - 2 >= begin && at(p - 1) == 0 && at(p - 2) == 0xFF) ? 2 : 1;
+        }
+        return p * 8 + ((8 - (real & 7)) & 7);
+    }
+    // Starts reading at `bitpos` (a value of bit_position(), or a guess) as if the bits before it had been consumed.
+    JPG_HD void enter(const uint8_t* d, int64_t b, int64_t e, int64_t bitpos) {
+        init(d, b, e);
+        pos = bitpos >> 3;
+        begin = pos < e ? pos : b;                      // nothing in front of the entry byte is looked at again
+        const int off = (int)(bitpos & 7);
+        if (off) {
+            peek(off);
+            nbits -= off;
+        }
+    }
     // RSTn: drop the buffered bits, find the marker, check its number
     JPG_HD void restart(int expect) {
         buf = 0; nbits = 0; fake = 0; marker = 0;

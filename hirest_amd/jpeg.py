@@ -7,6 +7,7 @@ extract_features.py:45-49 ``preprocess(Image.open(image))``; inference_video_ret
     frames = jpeg.decode(paths_or_bytes)          # uint8 [B,H,W,3] cuda (one size) or a list of [H,W,3]
     frames = jpeg.read_frame_dir(video_dir)       # <video>/*.jpg in extract_features.py's integer order
     jpeg.last_fallbacks                           # [(index, reason), ...] of the last call's host-decoded files
+    frames = jpeg.decode(files, entropy="chunked")   # many lanes per image in the entropy stage: same bits
 
 Files are read on a pool of at most 16 threads and parsed on the host (``hirest_jpeg_parse``); the compressed bytes go to
 the device in one pinned copy and ``hirest_jpeg_decode`` (entropy decode, IDCT, upsampling + colour) writes the frames.
@@ -14,6 +15,13 @@ Files outside the supported subset (progressive, arithmetic, 12-bit, CMYK / RGB,
 files whose entropy decode reports an anomaly are decoded by Pillow on the host and uploaded: the result is Pillow's in
 every case, Pillow's exceptions included.  The device path never falls back silently: ``last_fallbacks`` names every file
 that took the host path and why.
+
+The entropy stage has two forms with the same output: ``"lanes"`` gives each image one lane
+(``hirest_jpeg_decode``), ``"chunked"`` gives each image a workgroup of up to 1024 lanes that find the block boundaries by
+self-synchronisation (``hirest_jpeg_decode_chunked``), so that its rate does not depend on the number of images in the call.
+``"chunked"`` is the default: it was the faster one at every size and batch measured.
+``Decoder(entropy=..., chunk_bytes=...)``, the same keywords on ``decode`` / ``read_frame_dir``, and ``HIREST_JPEG_ENTROPY``
+for the callers that use the module's own decoder (``extract_frame_dir``, ``JpegFrameSource``, ``evaluate_clip_score``).
 """
 from __future__ import annotations
 
@@ -32,6 +40,8 @@ from . import _lib, ops
 IO_THREADS = 16                       # file reads / host fallback: a command gets 16 CPUs, never size this from os.cpu_count()
 WORKSPACE_BYTES = 10 << 30            # coefficient + plane workspace cap (1024 1080p frames: 9.6 GB); larger batches go in sub-batches
 _ALIGN = 256
+ENTROPY_MODES = ("lanes", "chunked")
+DEFAULT_ENTROPY = "chunked"           # at least as fast on every measured row; HIREST_JPEG_ENTROPY overrides it
 
 last_fallbacks: List[Tuple[int, str]] = []
 
@@ -76,6 +86,22 @@ def decode_host(data: bytes) -> Tuple[np.ndarray, int]:
     return (out if st.value == 0 else np.zeros((0, 0, 3), np.uint8)), st.value
 
 
+def decode_host_chunked(data: bytes, chunk_bytes: int = 0, scan: bytes = None) -> Tuple[np.ndarray, int, int]:
+    """``hirest_jpeg_decode_host_chunked``: ``decode_host`` with the chunked entropy stage, the lanes run one after another
+    -> (uint8 [H,W,3], status, sync rounds).  The file must have no restart interval.  ``scan`` (optional) is decoded in
+    place of ``data`` with the descriptor and tables parsed from ``data``: a test's way to change bytes behind the parser."""
+    lib = _lib.load()
+    img, tab = parse(data)
+    if not img.supported:
+        return np.zeros((0, 0, 3), np.uint8), 16, 0
+    out = np.empty((img.height, img.width, 3), np.uint8)
+    buf = np.frombuffer(data if scan is None else scan, dtype=np.uint8)
+    st, rounds = C.c_int32(0), C.c_int32(0)
+    _lib.check(lib.hirest_jpeg_decode_host_chunked(C.byref(img), C.byref(tab), buf.ctypes.data, int(chunk_bytes), out.ctypes.data, C.byref(st),
+                                                   C.byref(rounds)), "hirest_jpeg_decode_host_chunked")
+    return (out if st.value == 0 else np.zeros((0, 0, 3), np.uint8)), st.value, rounds.value
+
+
 def _pillow(data: bytes) -> np.ndarray:
     from PIL import Image
     return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
@@ -90,10 +116,20 @@ def _status_reason(st: int) -> str:
 
 
 class Decoder:
-    """Reusable device decoder: keeps its pinned staging buffer, device buffers and workspace between calls."""
+    """Reusable device decoder: keeps its pinned staging buffer, device buffers and workspace between calls.
+    ``entropy``: "lanes" (one lane per image) or "chunked" (many lanes per image, ``chunk_bytes`` per lane, 0 = chosen per
+    image); None takes ``HIREST_JPEG_ENTROPY``, else the default.  The frames are the same."""
 
-    def __init__(self, workspace_bytes: int = WORKSPACE_BYTES):
+    def __init__(self, workspace_bytes: int = WORKSPACE_BYTES, entropy: str = None, chunk_bytes: int = 0):
+        entropy = entropy or os.environ.get("HIREST_JPEG_ENTROPY") or DEFAULT_ENTROPY
+        if entropy not in ENTROPY_MODES:
+            raise ValueError(f"entropy must be one of {ENTROPY_MODES}, not {entropy!r}")
+        if int(chunk_bytes) < 0:
+            raise ValueError("chunk_bytes must be >= 0")
         self.workspace_bytes = int(workspace_bytes)
+        self.entropy = entropy
+        self.chunk_bytes = int(chunk_bytes)
+        self._chunk_info = None              # device int32 [m, 4] of the last chunked call, rows in launch order
         self.last_fallbacks: List[Tuple[int, str]] = []
         self._pinned = None
         self._dev = {}
@@ -204,9 +240,20 @@ class Decoder:
         ws = self._buffer("ws", ws_need, device)
         status = torch.empty(m, dtype=torch.int32, device=device)
         base = stage.data_ptr()
+        info = None
+        if self.entropy == "chunked":
+            info = torch.empty((m, 4), dtype=torch.int32, device=device)
+        self._chunk_info = info
         for a, b in batches:
-            _lib.check(lib.hirest_jpeg_decode(C.byref(descs, a * sz), base + a * sz, b - a, base + o_tab, base + o_dat, out.data_ptr(),
-                                              status.data_ptr() + 4 * a, ws.data_ptr(), ws.numel(), ops.stream_ptr()), "hirest_jpeg_decode")
+            if info is None:
+                _lib.check(lib.hirest_jpeg_decode(C.byref(descs, a * sz), base + a * sz, b - a, base + o_tab, base + o_dat, out.data_ptr(),
+                                                  status.data_ptr() + 4 * a, ws.data_ptr(), ws.numel(), ops.stream_ptr()), "hirest_jpeg_decode")
+                continue
+            cws = self._buffer("chunk_ws", lib.hirest_jpeg_chunked_workspace_bytes(b - a), device)
+            _lib.check(lib.hirest_jpeg_decode_chunked(C.byref(descs, a * sz), base + a * sz, b - a, base + o_tab, base + o_dat, out.data_ptr(),
+                                                      status.data_ptr() + 4 * a, ws.data_ptr(), ws.numel(), self.chunk_bytes, cws.data_ptr(),
+                                                      cws.numel(), ops.stream_ptr()), "hirest_jpeg_decode_chunked")
+            info[a:b].copy_(cws[:(b - a) * 16].view(torch.int32).view(b - a, 4))
         st = status.cpu().numpy()               # the one device->host read: which images need the host decode
         bad = [(order[k], int(st[k])) for k in range(m) if st[k] != 0]
         if bad:
@@ -216,20 +263,31 @@ class Decoder:
                 host_px[i] = arr
 
 
-_default = None
+    def chunk_info(self) -> np.ndarray:
+        """int32 [images, 4] of the last chunked call: chunk bytes, lanes, sync rounds, blocks found of every image the
+        chunked kernel decoded (rows of zeros: unsupported files and files with a restart interval), in launch order."""
+        if self._chunk_info is None:
+            return np.zeros((0, 4), np.int32)
+        return self._chunk_info.cpu().numpy()
 
 
-def _decoder() -> Decoder:
-    global _default
-    if _default is None:
-        _default = Decoder()
-    return _default
+_default = {}
 
 
-def decode(sources: Sequence[Source], device=None):
+def _decoder(entropy: str = None, chunk_bytes: int = 0) -> Decoder:
+    """The module's decoder for an entropy mode; without one, ``HIREST_JPEG_ENTROPY`` or the default decides."""
+    entropy = entropy or os.environ.get("HIREST_JPEG_ENTROPY") or DEFAULT_ENTROPY
+    key = (entropy, int(chunk_bytes))
+    if key not in _default:
+        _default[key] = Decoder(entropy=entropy, chunk_bytes=chunk_bytes)
+    return _default[key]
+
+
+def decode(sources: Sequence[Source], device=None, entropy: str = None, chunk_bytes: int = 0):
     """Decode JPEG files (paths, bytes or a mix) on the device.  Returns one uint8 ``[B,H,W,3]`` tensor when every image has the
-    same size, else a list of ``[H,W,3]`` tensors (views of one buffer).  ``last_fallbacks`` lists the host-decoded files."""
-    return _decoder().decode(sources, device)
+    same size, else a list of ``[H,W,3]`` tensors (views of one buffer).  ``last_fallbacks`` lists the host-decoded files.
+    ``entropy`` / ``chunk_bytes``: see ``Decoder``; None takes ``HIREST_JPEG_ENTROPY``, else the default."""
+    return _decoder(entropy, chunk_bytes).decode(sources, device)
 
 
 def frame_index(path: str) -> int:
@@ -244,6 +302,6 @@ def list_frame_dir(path) -> List[str]:
     return files
 
 
-def read_frame_dir(path, device=None):
+def read_frame_dir(path, device=None, entropy: str = None, chunk_bytes: int = 0):
     """All frames of one video directory, decoded on the device (see ``decode``)."""
-    return decode(list_frame_dir(path), device)
+    return decode(list_frame_dir(path), device, entropy, chunk_bytes)

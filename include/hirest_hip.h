@@ -810,6 +810,22 @@ int hirest_preprocess_u8(const uint8_t* frames, int32_t B, int32_t in_h, int32_t
  *                               HIREST_JPEG_ST_* bits: the frame is then not written and the caller decodes the file on
  *                               the host.  workspace 256-B aligned, data 8-B aligned.
  *   hirest_jpeg_decode_host     HOST: the same arithmetic on the CPU for one image (data = the file, out = H*W*3 bytes).
+ * Chunked entropy decode: many lanes per image instead of one, same bits, same workspace layout.
+ * The scan of an image without a restart interval is cut into chunks of chunk_bytes, one lane per chunk, one workgroup of
+ * up to 1024 lanes per image; the lanes find the block boundaries by self-synchronisation (sync rounds), then each writes
+ * the blocks that start in its chunk.  chunk_bytes = 0 chooses max(256, ceil(scan bytes / 1024)).
+ *   hirest_jpeg_decode_chunked  DEVICE: hirest_jpeg_decode with that entropy stage; every argument they share means the
+ *                               same, status[i] is non-zero for exactly the same images.  Images with a restart interval
+ *                               take the one-lane kernel.  A chunk_bytes > 0 that would need more than 1024 lanes for an
+ *                               image is raised for that image to ceil(scan bytes / 1024).  chunk_workspace (device,
+ *                               16-B aligned, hirest_jpeg_chunked_workspace_bytes(n) bytes) receives int32[n][4]: chunk
+ *                               bytes used, lanes, sync rounds, blocks found; all 0 for an image this stage did not decode.
+ *   hirest_jpeg_chunked_workspace_bytes  HOST: bytes of chunk_workspace for n images.
+ *   hirest_jpeg_decode_host_chunked      HOST: hirest_jpeg_decode_host with the chunked entropy stage run one lane after
+ *                               another, round for round as the device runs it; restart_interval must be 0 (else
+ *                               HIREST_E_BADARG).  chunk_bytes > 0 is used as given (any number of lanes).  rounds_out
+ *                               (optional) = sync rounds in which a lane decoded, at most the number of chunks; >= 2
+ *                               means a lane's first guess was wrong and was corrected.
  * ------------------------------------------------------------------------------------ */
 enum hirest_jpeg_reason {
     HIREST_JPEG_OK = 0, HIREST_JPEG_NOT_JPEG = 1, HIREST_JPEG_PROGRESSIVE = 2, HIREST_JPEG_ARITHMETIC = 3,
@@ -849,6 +865,13 @@ int hirest_jpeg_decode(const hirest_jpeg_image* imgs_host, const hirest_jpeg_ima
                        void* workspace, int64_t workspace_bytes, void* stream);
 int hirest_jpeg_decode_host(const hirest_jpeg_image* img, const hirest_jpeg_tables* tables, const uint8_t* data,
                             uint8_t* out, int32_t* status);
+int64_t hirest_jpeg_chunked_workspace_bytes(int32_t n);
+int hirest_jpeg_decode_chunked(const hirest_jpeg_image* imgs_host, const hirest_jpeg_image* imgs_dev, int32_t n,
+                               const hirest_jpeg_tables* tables_dev, const uint8_t* data, uint8_t* out, int32_t* status,
+                               void* workspace, int64_t workspace_bytes, int64_t chunk_bytes, void* chunk_workspace,
+                               int64_t chunk_workspace_bytes, void* stream);
+int hirest_jpeg_decode_host_chunked(const hirest_jpeg_image* img, const hirest_jpeg_tables* tables, const uint8_t* data,
+                                    int64_t chunk_bytes, uint8_t* out, int32_t* status, int32_t* rounds_out);
 
 /* ------------------------------------------------------------------------------------
  * Moment-task evaluation on device (evaluate.py), double precision with Python's operation order:
