@@ -7,5 +7,7 @@ from .tokenizer import tokenize  # noqa: F401
 from .moment_model import MomentModel  # noqa: F401
 from .sentence_encoder import SentenceTransformer  # noqa: F401
 from . import optim  # noqa: F401
+from . import cascade  # noqa: F401
+from .cascade import run_end_to_end, end_to_end_results  # noqa: F401
 
 __version__ = "0.1.0"

@@ -3,6 +3,7 @@
 // suppression) are the reference's decisions bit for bit.  Tiny integer/branchy work: one thread per interval pair or
 // per video; no MFMA, no LDS.
 #include "common.h"
+#include "timeline_bins.h"
 
 namespace {
 
@@ -104,21 +105,7 @@ __global__ void preprocess_bounds_kernel(const double* __restrict__ preds, const
     out_count[v] = cnt;
 }
 
-// hirest_dataset.py:12-68: bins = np.linspace(0, int(duration) - 1, n).  numpy builds it as arange(n) * step with
-// step = (stop - start) / (n - 1) in double and overwrites the last element with `stop`; the bin value is recomputed
-// here on demand (one multiply) instead of materialising n doubles per conversion as the reference does.
-struct Bins {
-    int64_t n; double stop, step;
-    __device__ __forceinline__ double at(int64_t i) const { return (i == n - 1 && n > 1) ? stop : (n > 1 ? (double)i * step : 0.0); }
-};
-__device__ __forceinline__ bool make_bins(double duration, int32_t n_frames, Bins& b) {
-    const int64_t d = (int64_t)duration;                       // Python int(): truncation toward zero
-    b.n = n_frames < 0 ? d : n_frames;                         // n_frames < 0: one frame per second
-    b.stop = (double)(d - 1);
-    b.step = b.n > 1 ? b.stop / (double)(b.n - 1) : 0.0;
-    return d >= 1 && b.n >= 1;                                 // shorter than one second: the reference's bins are empty / decreasing
-}
-
+// hirest_dataset.py:12-68: the bins and both conversions are in timeline_bins.h (shared with csrc/cascade.hip)
 __global__ void frame_to_timestamp_kernel(const int64_t* __restrict__ frame, const double* __restrict__ duration,
                                           const int32_t* __restrict__ n_frames, int32_t n_frames_all, int64_t per_video, int64_t n,
                                           int64_t* __restrict__ ts) {
@@ -126,10 +113,8 @@ __global__ void frame_to_timestamp_kernel(const int64_t* __restrict__ frame, con
     if (i >= n) return;
     const int64_t v = i / per_video;
     Bins b;
-    int64_t f = frame[i];
     if (!make_bins(duration[v], n_frames ? n_frames[v] : n_frames_all, b)) { ts[i] = INT64_MIN; return; }
-    if (f < 0) f += b.n;                                       // numpy negative indexing
-    ts[i] = (f < 0 || f >= b.n) ? INT64_MIN : (int64_t)b.at(f);   // IndexError in the reference
+    ts[i] = bins_frame_to_timestamp(b, frame[i]);              // INT64_MIN: IndexError in the reference
 }
 
 // np.digitize(t, bins, right=True) = number of bins strictly below t, then min(., n - 1)
@@ -141,16 +126,7 @@ __global__ void timestamp_to_frame_kernel(const double* __restrict__ t, const do
     const int64_t v = i / per_video;
     Bins b;
     if (!make_bins(duration[v], n_frames ? n_frames[v] : n_frames_all, b)) { frame[i] = INT64_MIN; return; }
-    const double x = t[i];
-    if (x != x) { frame[i] = b.n - 1; return; }                // NaN sorts after every bin
-    int64_t k = 0;
-    if (b.step > 0.0 && x > 0.0) {                             // first guess from the spacing, then settle on the exact bin values
-        const double g = ceil(x / b.step);
-        k = g >= (double)b.n ? b.n : (int64_t)g;
-    }
-    while (k > 0 && !(b.at(k - 1) < x)) --k;
-    while (k < b.n && b.at(k) < x) ++k;
-    frame[i] = k < b.n - 1 ? k : b.n - 1;
+    frame[i] = bins_timestamp_to_frame(b, t[i]);
 }
 
 }  // namespace

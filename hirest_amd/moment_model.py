@@ -851,7 +851,15 @@ class MomentModel(nn.Module):
         rows = self._trim_rows(mmask, max_frames, dev)
         v = self._trim(vis, None, max_frames, idx=rows)
         a = self._trim(batch["asr_feats"].to(dev).float(), None, max_frames, idx=rows) if self.use_asr else None
-        text = self._text_feat(batch, dev)
+        return self._caption_trimmed(v, a, self._text_feat(batch, dev), num_beams, return_ids, **kwargs)
+
+    def _caption_trimmed(self, v, a, text, num_beams, return_ids, **kwargs):
+        """test_step_captioning behind trim_feats: v [B, max_frames, D] (a [B, max_frames, Da] or None) already trimmed, text [B, 1024]."""
+        from .beam import BeamState
+        c = self._w()
+        dev = c["dev"]
+        max_words = int(getattr(self.args, "max_words", 48)) if self.args is not None else 48
+        B, max_frames = v.shape[0], v.shape[1]
         ones = torch.ones((B, max_frames), dtype=torch.long, device=dev)
         base = self._fusion_base(v, text, a, ones)
         enc = self._features(base, ones.to(torch.int32).contiguous(), None, B, max_frames)          # [B*F, 768]
@@ -991,6 +999,27 @@ class MomentModel(nn.Module):
         if errors:
             raise errors[0]
         return results
+
+    @torch.no_grad()
+    def end_to_end(self, batch, num_beams=5, return_ids=False):
+        """The reference's ``run.py --end_to_end`` (run.py:383-490) for one moment-retrieval batch: retrieval, segmentation of the
+        retrieved moment and a caption per predicted step, chained on the device (hirest_amd/cascade.py, csrc/cascade.hip).
+
+        ``batch`` is what the moment-retrieval loader delivers (``vis_feats``, ``vis_mask``, an all-ones ``moment_mask``, ``asr_feats``
+        when the model uses ASR, ``text_feat`` or ``clip_text_ids``) plus ``video_duration`` [B] and, where the number of bins differs
+        per sample (the loader's ``n_model_frames = -1``: one frame per second), ``n_frames`` [B]; without it the model's ``n_frames``
+        is used (<= 0: one frame per second of each duration).  The text feature is computed once for all three stages and
+        ``set_precision`` applies as it does to ``test_step``.
+
+        Returns a dict of per-sample lists: ``moment_frames`` [start, end] (the arg-max frames), ``bounds`` [start_s, end_s]
+        (run.py:731-734), ``boundary_frames`` (the segmentation's ``prediction``), ``step_bounds`` [[s0, s1], [s1, s2], ...] in seconds
+        (run.py:766-776) and ``captions`` (one string per step; the token-id lists with ``return_ids``).
+
+        Deviation from the reference: a sample whose segmentation yields fewer than two boundaries has no step; it gets
+        ``step_bounds = []`` and ``captions = []`` here, where the reference's captioning dataset raises IndexError on the empty
+        step list (hirest_dataset.py:279 under --end_to_end)."""
+        from . import cascade
+        return cascade.run_end_to_end(self, [batch], num_beams=num_beams, return_ids=return_ids)[0]
 
     caption_device_readout = True    # the best hypothesis of every sample walked back on the device (hirest_beam_backtrack); False: on the host (BeamState)
 

@@ -906,6 +906,44 @@ int hirest_timestamp_to_frame(const double* t, const double* duration, const int
                               int64_t per_video, int64_t n, int64_t* frame, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Seams of the end-to-end cascade (run.py:383-490): the reference writes each stage's predictions into all_data_test.json and
+ * rebuilds the next stage's dataset from it (hirest_dataset.py:186-311).  These three steps do that re-derivation on the device,
+ * with the bins above, so that retrieval -> segmentation -> captioning runs without a host round trip.  n_frames as above
+ * (per sample [B], or NULL and n_frames_all; < 0: one frame per second).  All integer results are the reference's.
+ *
+ *   hirest_cascade_moment_bounds   pred_frames int32 [B,2] (start, end arg-max frames) ->
+ *       bounds_ts int64 [B,2]      frame_index_to_timestamp of each (run.py:731-732); INT64_MIN where the reference raises
+ *       bound_frames int32 [B,2]   timestamp_to_frame_index(bounds_ts) (hirest_dataset.py:250-254); -1 where bounds_ts is invalid
+ *       moment_mask int32 [B,T]    [s : e + 1] = 1 with Python's slice semantics (empty when s > e)
+ *       boundary_mask int32 [B,T]  a single one at s (modeling.py:376-382)
+ *   hirest_cascade_boundaries      steps int32 [B,iters,2] + nsteps [B] (hirest_segmentation_step's state) + bound_frames ->
+ *       n_bounds int32 [B], bounds int32 [B,cap], cap = 2 iters + 4 (unused entries -1): the post-processing of modeling.py:435-463
+ *           ([s,s] + steps + [l,l], stable sort by first element, flatten, drop trailing values > l, sorted set, keep the first value
+ *           and every interior value >= 5 frames after the last kept one; the final value is never kept)
+ *       offsets int32 [B+1]        exclusive prefix sum of max(n_bounds - 1, 0); offsets[B] = S, the number of steps
+ *       step_ts int64 [S,2]        timestamps of consecutive boundary pairs (run.py:766-770), rows offsets[b] .. offsets[b+1]-1 of sample b
+ *       step_frames int32 [S,2]    timestamp_to_frame_index of those (hirest_dataset.py:289-290)
+ *       step_sample int32 [S]      the sample a step belongs to
+ *     The step buffers hold B (cap - 1) rows; rows >= S are not written.  One wave per sample, fixed order, no atomics: the result
+ *     does not depend on the launch shape.  cap <= 64 (iters <= 30), else HIREST_E_SHAPE.
+ *   hirest_cascade_trim_gather     trim_feats (modeling.py:529-554) of the captioning mask `mask[a:e] = 1; mask[e] = 1`
+ *       (hirest_dataset.py:302-304) for step s = (a, e) = step_frames[s] of sample step_sample[s]: the selected frames are a .. e
+ *       (N = e - a + 1) when a <= e, else e alone (N = 1); slot p < F takes frame a + p when N > F, else selected frame
+ *       ceil((p + 1) N / F) - 1.  Copies that row of vis [B,T,D] (and of asr [B,T,Da] unless NULL) to out_vis [S,F,D]
+ *       (out_asr [S,F,Da]), fp32, 16 bytes per lane: D % 4 == 0 and Da % 4 == 0 (else HIREST_E_SHAPE), 16-byte aligned pointers.
+ *       A step whose sample or frames lie outside [0,B) x [0,T) yields zero rows.
+ * ------------------------------------------------------------------------------------ */
+int hirest_cascade_moment_bounds(const int32_t* pred_frames, const double* duration, const int32_t* n_frames, int32_t n_frames_all,
+                                 int32_t B, int32_t T, int64_t* bounds_ts, int32_t* bound_frames, int32_t* moment_mask,
+                                 int32_t* boundary_mask, void* stream);
+int hirest_cascade_boundaries(const int32_t* steps, const int32_t* nsteps, const int32_t* bound_frames, const double* duration,
+                              const int32_t* n_frames, int32_t n_frames_all, int32_t B, int32_t iters, int32_t* n_bounds,
+                              int32_t* bounds, int64_t* step_ts, int32_t* step_frames, int32_t* step_sample, int32_t* offsets,
+                              void* stream);
+int hirest_cascade_trim_gather(const float* vis, const float* asr, const int32_t* step_frames, const int32_t* step_sample, int32_t S,
+                               int32_t B, int32_t T, int32_t D, int32_t Da, int32_t F, float* out_vis, float* out_asr, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Optional per-launch timing (bench.py's live roofline measurement).  When enabled, every
  * GEMM / attention / LayerNorm launch is bracketed by hipEventRecord on ITS launch stream;
  * hirest_profile_collect synchronises those events and returns one record per launch.
