@@ -189,6 +189,23 @@ JPEG_STATUS = {1: "bad Huffman code", 2: "more than 64 coefficients in a block",
                16: "unsupported"}
 
 
+BATCH_GATHER_MAX = 8     # HIREST_BATCH_GATHER_MAX
+
+
+class BatchGather(C.Structure):
+    """hirest_batch_gather (include/hirest_hip.h)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_of_example", C.c_void_p), ("words", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BatchArgs(C.Structure):
+    """hirest_batch_args (include/hirest_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint64), ("index", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("B", "T", "D", "Da", "n_examples", "n_model_frames", "n_gather", "reserved")] + \
+               [(n, C.c_void_p) for n in ("frames", "frame_off", "asr_rows", "sub_off", "sub_span", "ex_video", "ex_len", "ex_range",
+                                          "bound_off", "bound_val", "vis", "asr", "vis_mask", "moment_mask", "prev_boundary_mask")] + \
+               [("gather", BatchGather * BATCH_GATHER_MAX)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("kind", C.c_int32), ("tag", C.c_int32), ("d0", C.c_int64), ("d1", C.c_int64), ("d2", C.c_int64),
                 ("ms", C.c_float)]
@@ -373,6 +390,7 @@ _SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hirest_cascade_trim_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hirest_batch_assemble": (C.c_int, [C.POINTER(BatchArgs), C.c_void_p]),
     "hirest_vision_workspace_bytes": (C.c_size_t, [C.POINTER(VisionTower), C.c_int32]),
     "hirest_vision_forward": (C.c_int, [C.POINTER(VisionTower), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),

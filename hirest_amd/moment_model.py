@@ -554,6 +554,15 @@ class MomentModel(nn.Module):
         return flat.to(device), keep
 
     @staticmethod
+    def _host_moment_mask(batch) -> torch.Tensor:
+        """``batch['moment_mask']`` for the host index arithmetic of trim_feats: a batch built on the device (hirest_amd.dataset)
+        carries a CPU copy in ``batch.host``, so the mask never travels back; any other batch gives the entry itself."""
+        host = getattr(batch, "host", None)
+        if host and "moment_mask" in host:
+            return host["moment_mask"]
+        return batch["moment_mask"]
+
+    @staticmethod
     def _trim_index_table(mask: torch.Tensor, max_frames: int) -> "np.ndarray":
         """_trim_index for every row of a [B, T] CPU mask at once (the per-sample list walk cost 0.5 ms of host time in front of a B = 32
         captioning batch, with the GPU idle): output position p of a sample with N <= max_frames selected frames takes selected frame
@@ -846,7 +855,7 @@ class MomentModel(nn.Module):
         max_frames = int(getattr(self.args, "max_frames_step_captioning", 20)) if self.args is not None else 20
         max_words = int(getattr(self.args, "max_words", 48)) if self.args is not None else 48
         vis = batch["vis_feats"].to(dev).float()
-        mmask = batch["moment_mask"]
+        mmask = self._host_moment_mask(batch)
         B = vis.shape[0]
         rows = self._trim_rows(mmask, max_frames, dev)
         v = self._trim(vis, None, max_frames, idx=rows)
@@ -901,7 +910,7 @@ class MomentModel(nn.Module):
         vs, as_, ts = [], [], []
         for b in group:
             vis = b["vis_feats"].to(dev).float()
-            rows = self._trim_rows(b["moment_mask"], max_frames, dev)
+            rows = self._trim_rows(self._host_moment_mask(b), max_frames, dev)
             vs.append(self._trim(vis, None, max_frames, idx=rows))
             if self.use_asr:
                 as_.append(self._trim(b["asr_feats"].to(dev).float(), None, max_frames, idx=rows))

@@ -24,6 +24,7 @@ from typing import Dict, List
 
 import os
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -1048,16 +1049,18 @@ def _train(model, batch, task) -> Dict[str, torch.Tensor]:
         args = model.args
         max_frames = int(getattr(args, "max_frames_step_captioning", 20)) if args is not None else 20
         B = inp["vis"].shape[0]
-        rows = model._trim_rows(batch["moment_mask"], max_frames, dev)      # from the batch's own (CPU) mask: no device round trip
+        rows = model._trim_rows(model._host_moment_mask(batch), max_frames, dev)      # from the batch's own (CPU) mask: no device round trip
         inp["vis"] = model._trim(inp["vis"].float(), None, max_frames, idx=rows)
         if model.use_asr:
             inp["asr"] = model._trim(inp["asr"].float(), None, max_frames, idx=rows)
         ones = torch.ones((B, max_frames), dtype=torch.long, device=dev)
         inp["vis_mask"], inp["moment_mask"] = ones, ones
         tt = batch["target_text"]
-        inp["input_ids"] = torch.tensor([list(t[5]) for t in tt], dtype=torch.long)
-        inp["decoder_mask"] = torch.tensor([list(t[6]) for t in tt], dtype=torch.long)
-        inp["output_ids"] = torch.tensor([list(t[7]) for t in tt], dtype=torch.long)
+        # (a field is a [max_words] list or the [1, max_words] array of clip4cap_get_text, hirest_dataset.py:575-577)
+        row = lambda f: np.asarray(f, dtype=np.int64).reshape(-1)
+        inp["input_ids"] = torch.from_numpy(np.stack([row(t[5]) for t in tt]))
+        inp["decoder_mask"] = torch.from_numpy(np.stack([row(t[6]) for t in tt]))
+        inp["output_ids"] = torch.from_numpy(np.stack([row(t[7]) for t in tt]))
         fn = CaptionLoss
     names = task_param_names(model, task)
     return {"loss": fn.apply(model, inp, names, *_parameters_by_name(model, names))}

@@ -1107,6 +1107,54 @@ int hirest_clip_coef_f32(const float* partials, int64_t count, float max_norm, f
 int hirest_adamw_grouped_f32(const hirest_optim_item* items, int32_t count, const float* coef, float decay, float one_minus_beta1,
                              float beta2, float one_minus_beta2, float step_size, float bc2_sqrt, float eps, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Loader batches of the joint model, assembled on the device from resident features: MomentDataset.__getitem__ + collate_fn
+ * (hirest_dataset.py:323-531) for B examples in ONE launch on `stream`, no host synchronisation, every output written in full.
+ * The feature files of a corpus live in two fp32 arrays (frame rows of all videos, ASR rows of all videos) with row-offset tables
+ * per video; an example is a row of integer tables (hirest_amd/dataset.py builds them).  Copies are pure gathers: bit-exact.
+ *
+ * Output row t of sample b (example e = index[b], video v = ex_video[e], n = frame_off[v + 1] - frame_off[v] file rows):
+ *   vis[b, t]  F = n_model_frames > 0:  n > F: file row (int64)(t * ((double)(n - 1) / (double)(F - 1))), the last one n - 1, F = 1: row 0
+ *                                        (np.linspace(0, n - 1, F).astype(int));  n <= F: row ceil((t + 1) n / F) - 1 (the bucket up-sample)
+ *              n_model_frames <= 0:      row t for t < n, zeros up to T
+ *   asr[b, t]  the ASR row of the LAST subtitle i (file order) of the video with span[i][0] <= t < span[i][1], zeros when there is none
+ *              or t is past the sample's fitted length (F, or n when n_model_frames <= 0); optional (asr_rows NULL: no ASR output)
+ *   vis_mask[b, t] = t < L;  moment_mask[b, t] = (lo <= t < hi or t == one) and t < L;  prev_boundary_mask[b, t] = t in the example's
+ *              boundary list and t < L — with L = ex_len[e] and (lo, hi, one) = ex_range[e]; int64; prev_boundary_mask optional
+ * Then `n_gather` row gathers: dst[b] = src[row_of_example ? row_of_example[e] : e], rows of `words` 4-byte words (an int64 is two).
+ * An index outside [0, n_examples) gives an all-zero sample.  D and Da may be any positive value: rows whose width is a multiple
+ * of four floats (and 16-byte aligned arrays) move as 16-byte vectors, others as single floats.
+ * HIREST_E_BADARG: NULL required pointer, wrong struct_size, non-positive size, n_gather out of range; HIREST_E_SHAPE: B * T rows
+ * beyond 2^31 - 1 workgroups.
+ * ------------------------------------------------------------------------------------ */
+#define HIREST_BATCH_GATHER_MAX 8
+typedef struct hirest_batch_gather {
+    const void* src;                  /* [rows, words] 4-byte words                                                    */
+    void*       dst;                  /* [B, words]                                                                    */
+    const int32_t* row_of_example;    /* [n_examples] or NULL (row = example)                                          */
+    int32_t words, reserved;
+} hirest_batch_gather;
+typedef struct hirest_batch_args {
+    uint64_t struct_size;
+    const int32_t* index;             /* [B] example numbers, device                                                   */
+    int32_t B, T, D, Da, n_examples, n_model_frames, n_gather, reserved;
+    const float*   frames;            /* [sum n, D]                                                                    */
+    const int64_t* frame_off;         /* [videos + 1]                                                                  */
+    const float*   asr_rows;          /* [sum s, Da] or NULL                                                           */
+    const int64_t* sub_off;           /* [videos + 1] subtitle (= ASR row) offsets                                     */
+    const int32_t* sub_span;          /* [sum s, 2] (start, end) whole seconds                                         */
+    const int32_t* ex_video;          /* [n_examples]                                                                  */
+    const int32_t* ex_len;            /* [n_examples] mask length L                                                    */
+    const int32_t* ex_range;          /* [n_examples, 3] lo, hi, one (-1: none)                                        */
+    const int32_t* bound_off;         /* [n_examples + 1] or NULL (with prev_boundary_mask NULL)                       */
+    const int32_t* bound_val;         /* boundary frames                                                               */
+    float*   vis;                     /* [B, T, D]                                                                     */
+    float*   asr;                     /* [B, T, Da]                                                                    */
+    int64_t *vis_mask, *moment_mask, *prev_boundary_mask;     /* [B, T]                                                */
+    hirest_batch_gather gather[HIREST_BATCH_GATHER_MAX];
+} hirest_batch_args;
+int hirest_batch_assemble(const hirest_batch_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
