@@ -7,55 +7,9 @@
 // Work is a table of items (one per parameter tensor) that travels in the kernel arguments like ColsumGroup of train.hip: gradient
 // pointers change every step (the loop sets param.grad = None), so a device-resident table would need a copy per step.  Item i
 // owns ceil(n_i / HIREST_OPTIM_CHUNK) consecutive blocks; a block works on one chunk of one tensor and never crosses into the next.
-#include "common.h"
+#include "optim_kernels.h"
 
 namespace {
-
-constexpr int CHUNK = HIREST_OPTIM_CHUNK;
-constexpr int THREADS = 256;
-
-struct OptimGroup { hirest_optim_item item[HIREST_OPTIM_GROUP_MAX]; int first[HIREST_OPTIM_GROUP_MAX]; int count; };
-
-// AdamW's scalars of one launch, all derived on the host in double (torch's _single_tensor_adam with capturable = False)
-struct AdamwScalars {
-    float decay;            // 1 - lr * weight_decay
-    float w1;               // 1 - beta1 (the lerp weight)
-    float beta2, w2;        // beta2, 1 - beta2
-    float step_size;        // lr / (1 - beta1^t)
-    float bc2_sqrt;         // sqrt(1 - beta2^t)
-    float eps;
-};
-
-// which chunk of which item this block owns: first[] ascends, so the item is the number of later items starting at or before this block
-// (independent scalar loads, as in weighted_colsum_grouped_kernel)
-__device__ __forceinline__ int find_item(const OptimGroup& g) {
-    int i = 0;
-#pragma unroll
-    for (int j = 1; j < HIREST_OPTIM_GROUP_MAX; ++j) i += (j < g.count && (int)blockIdx.x >= g.first[j]) ? 1 : 0;
-    return i;
-}
-
-__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// a 16-byte access where the address allows it, four 4-byte ones otherwise (`vec` is uniform over the block: no divergence)
-__device__ __forceinline__ f32x4 load4(const float* p, bool vec) {
-    if (vec) return *reinterpret_cast<const f32x4*>(p);
-    return f32x4{p[0], p[1], p[2], p[3]};
-}
-__device__ __forceinline__ void store4(float* p, bool vec, const f32x4& x) {
-    if (vec) { *reinterpret_cast<f32x4*>(p) = x; return; }
-    p[0] = x[0]; p[1] = x[1]; p[2] = x[2]; p[3] = x[3];
-}
-
-// A chunk [0, n) that starts `lead` elements (0..3) before a 16-byte boundary of its leading pointer splits into a scalar head of
-// `head` elements, `nvec` float4 and a scalar tail; the split depends on the pointer's phase alone, which is the same for every
-// chunk of a tensor (CHUNK is a multiple of 4).
-struct Split { int head, nvec, tail0; };
-__device__ __forceinline__ Split split_chunk(const float* lead, int n) {
-    int head = (int)((16 - (reinterpret_cast<uintptr_t>(lead) & 15)) & 15) >> 2;
-    head = head < n ? head : n;
-    const int nvec = (n - head) >> 2;
-    return {head, nvec, head + 4 * nvec};
-}
 
 // partial[block] = sum of g^2 over the block's chunk.  Fixed order: a thread adds its float4 (element 0..3 in turn) in ascending
 // address order, then at most one head and one tail element; the 64 lanes of a wave and then the four waves are added in a fixed
@@ -90,32 +44,8 @@ __global__ __launch_bounds__(THREADS) void grad_sqnorm_kernel(OptimGroup grp, fl
 // threads.  The few thousand partials are added in double (free here), so the sum's error is that of the chunks alone.
 __global__ __launch_bounds__(THREADS) void clip_coef_kernel(const float* __restrict__ partials, int64_t n, float max_norm,
                                                             float* __restrict__ out) {
-    __shared__ double red[THREADS];
-    const int t = threadIdx.x;
-    double a = 0.0;
-    for (int64_t k = t; k < n; k += THREADS) a += (double)partials[k];
-    red[t] = a;
-    __syncthreads();
-#pragma unroll
-    for (int w = THREADS / 2; w > 0; w >>= 1) {
-        if (t < w) red[t] += red[t + w];
-        __syncthreads();
-    }
-    if (t == 0) {
-        const float norm = (float)sqrt(red[0]);
-        out[0] = norm;
-        out[1] = fminf(1.0f, max_norm / (norm + 1e-6f));
-    }
-}
-
-// torch.optim.AdamW, one element: the operations of _single_tensor_adam (capturable = False) in its order, on g' = coef * g
-__device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, float coef, const AdamwScalars& h) {
-    g *= coef;                                               // clip_grad_norm_: g.mul_(coef)
-    p *= h.decay;                                            // param.mul_(1 - lr * weight_decay)
-    m = m + h.w1 * (g - m);                                  // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * h.beta2 + h.w2 * g * g;                          // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-    const float denom = sqrtf(v) / h.bc2_sqrt + h.eps;       // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-    p = p - h.step_size * (m / denom);                       // param.addcdiv_(exp_avg, denom, value = -step_size)
+    const double sum = sum_partials(partials, n);
+    if (threadIdx.x == 0) write_norm_coef(sum, max_norm, out);
 }
 
 // g is read and never written.  The head / body / tail split follows p (its loads and stores are always 16 bytes wide in the body);
@@ -160,21 +90,6 @@ __global__ __launch_bounds__(THREADS) void adamw_kernel(OptimGroup grp, const fl
             p[e] = pp; m[e] = mm; v[e] = vv;
         }
     }
-}
-
-// blocks of a group and their first-block numbers; < 0 when the table is unusable
-inline int64_t fill_group(const hirest_optim_item* items, int32_t count, bool update, OptimGroup* g) {
-    if (!items || count <= 0 || count > HIREST_OPTIM_GROUP_MAX) return -1;
-    int64_t blocks = 0;
-    for (int i = 0; i < count; ++i) {
-        const hirest_optim_item& it = items[i];
-        if (!it.g || it.n <= 0 || (update && (!it.p || !it.m || !it.v))) return -1;
-        if (g) { g->item[i] = it; g->first[i] = (int)blocks; }
-        blocks += (it.n + CHUNK - 1) / CHUNK;
-        if (blocks > INT32_MAX) return -2;
-    }
-    if (g) g->count = count;
-    return blocks;
 }
 
 }  // namespace

@@ -1106,6 +1106,25 @@ int hirest_clip_coef_f32(const float* partials, int64_t count, float max_norm, f
  * step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t) (> 0, else HIREST_E_BADARG). */
 int hirest_adamw_grouped_f32(const hirest_optim_item* items, int32_t count, const float* coef, float decay, float one_minus_beta1,
                              float beta2, float one_minus_beta2, float step_size, float bc2_sqrt, float eps, void* stream);
+/* The same step with every per-step scalar on the device (hirest_amd.optim.AdamW(capturable=True)): a recorded sequence of these
+ * launches stays right when a hipGraph replays it, and the verdict of a loss scaler never reaches the host.  `steps` is a HOST array
+ * of `count` device pointers, steps[i] the fp32 step count of items[i] (torch's capturable state layout), copied into the kernel
+ * arguments like the items.  grad_scale and found_inf are torch.amp.GradScaler's device floats: gradients count as g * (1 / grad_scale[0])
+ * (NULL = 1) and nothing at all is stored when found_inf[0] != 0 (NULL = 0).  A NULL steps table or step pointer, count <= 0 or
+ * count > HIREST_OPTIM_GROUP_MAX is HIREST_E_BADARG before any launch, as are the item errors above. */
+/* hirest_grad_sqnorm_grouped_f32 on g * (1 / grad_scale[0]): the squares of the unscaled gradients, same chunks, same order */
+int hirest_grad_sqnorm_scaled_grouped_f32(const hirest_optim_item* items, int32_t count, const float* grad_scale, float* partials,
+                                          void* stream);
+/* hirest_clip_coef_f32 with max_norm[0] a device float (a clip bound that changes between replays of a recorded step) */
+int hirest_clip_coef_dev_f32(const float* partials, int64_t count, const float* max_norm, float* norm_coef, void* stream);
+/* steps[i][0] += 1 unless found_inf[0] != 0: one workgroup, one thread per tensor.  Run it once per tensor and step, before the update */
+int hirest_optim_step_advance_f32(float* const* steps, int32_t count, const float* found_inf, void* stream);
+/* hirest_adamw_grouped_f32 on g' = coef[0] * g * (1 / grad_scale[0]), each workgroup deriving decay, step_size and bc2_sqrt in double
+ * from t = steps[i][0] (already advanced, >= 1) and lr = lr_ptr ? lr_ptr[0] : lr, then rounding them to fp32: tensors whose step
+ * counts differ share a launch.  0 <= beta < 1, else HIREST_E_BADARG. */
+int hirest_adamw_capturable_grouped_f32(const hirest_optim_item* items, float* const* steps, int32_t count, const float* coef,
+                                        const float* lr_ptr, double lr, const float* grad_scale, const float* found_inf,
+                                        double beta1, double beta2, float eps, double weight_decay, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Loader batches of the joint model, assembled on the device from resident features: MomentDataset.__getitem__ + collate_fn

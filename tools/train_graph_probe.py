@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """How much of the training step's wall time is the GPU's?  The whole loop iteration (train_step -> backward -> clip_grad_norm_ ->
 AdamW) is captured into one hipGraph and replayed: a replay has no host work between kernels, so its time is what the kernels and
-their dependencies need.  Measurement only (the replay re-uses one dropout seed and one batch).   python tools/train_graph_probe.py"""
+their dependencies need.  Legs: torch's fused AdamW (eager, capturable eager, capturable replay) and hirest_amd.optim.AdamW(capturable=True,
+max_grad_norm=1.0), whose step() clips itself (eager, replay).  Measurement only (the replay re-uses one dropout seed and one batch).   python tools/train_graph_probe.py"""
 import argparse
 import json
 import os
@@ -37,11 +38,14 @@ batch = {n: (v.to(dev) if isinstance(v, torch.Tensor) else v) for n, v in batch.
 
 
 def make_step(opt):
+    native = isinstance(opt, hirest_amd.optim.AdamW)          # its step() clips
+
     def step():
         opt.zero_grad(set_to_none=True)
         loss = model.train_step(batch)["loss"]
         loss.backward()
-        torch.nn.utils.clip_grad_norm_(params, 1.0)
+        if not native:
+            torch.nn.utils.clip_grad_norm_(params, 1.0)
         opt.step()
         return loss
     return step
@@ -59,35 +63,43 @@ def wall(step, reps):
     return best * 1e3
 
 
-for name, kw in (("AdamW(fused=True)", dict(fused=True)), ("AdamW(fused=True, capturable=True)", dict(fused=True, capturable=True))):
-    opt = torch.optim.AdamW(params, lr=1e-5, **kw)
-    print(f"{name}: eager loop {wall(make_step(opt), a.reps):.2f} ms/step", flush=True)
-opt = torch.optim.AdamW(params, lr=1e-5, fused=True, capturable=True)
-step = make_step(opt)
-s = torch.cuda.Stream()
-s.wait_stream(torch.cuda.current_stream())
-with torch.cuda.stream(s):
+def replay(name, step):
+    """Capture one iteration after torch's side-stream warm-up (which also creates the optimizer's state) and time its replay."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(3):
+            step()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    try:
+        with torch.cuda.graph(g):
+            loss = step()
+    except Exception as e:  # noqa: BLE001
+        print(f"{name}: capture failed:", type(e).__name__, str(e)[:400])
+        return
+    torch.cuda.synchronize()
     for _ in range(3):
-        step()
-torch.cuda.current_stream().wait_stream(s)
-torch.cuda.synchronize()
-g = torch.cuda.CUDAGraph()
-try:
-    with torch.cuda.graph(g):
-        loss = step()
-except Exception as e:  # noqa: BLE001
-    print("capture failed:", type(e).__name__, str(e)[:400])
-    sys.exit(0)
-torch.cuda.synchronize()
-for _ in range(3):
-    g.replay()
-torch.cuda.synchronize()
-best = 1e9
-for _ in range(3):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.reps):
         g.replay()
-    e1.record(); torch.cuda.synchronize()
-    best = min(best, e0.elapsed_time(e1) / a.reps)
-print(f"hipGraph replay of the whole iteration: {best:.2f} ms/step (loss {float(loss):.4f})")
+    torch.cuda.synchronize()
+    best = 1e9
+    for _ in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.reps):
+            g.replay()
+        e1.record(); torch.cuda.synchronize()
+        best = min(best, e0.elapsed_time(e1) / a.reps)
+    print(f"{name}: hipGraph replay of the whole iteration: {best:.2f} ms/step (loss {float(loss):.4f})", flush=True)
+
+
+LEGS = (("AdamW(fused=True)", lambda: torch.optim.AdamW(params, lr=1e-5, fused=True), False),
+        ("AdamW(fused=True, capturable=True)", lambda: torch.optim.AdamW(params, lr=1e-5, fused=True, capturable=True), True),
+        ("hirest_amd.optim.AdamW(capturable=True, max_grad_norm=1.0)",
+         lambda: hirest_amd.optim.AdamW(params, lr=1e-5, capturable=True, max_grad_norm=1.0), True))
+for name, make, capture in LEGS:
+    step = make_step(make())
+    print(f"{name}: eager loop {wall(step, a.reps):.2f} ms/step", flush=True)
+    if capture:
+        replay(name, step)
