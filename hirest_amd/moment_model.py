@@ -20,19 +20,15 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-import json
 import os
 from copy import deepcopy
-from typing import Dict, List, Optional
+from typing import List
 
 import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, ops
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-
+from . import _lib, caption_search, ops
 
 def _p(*shape):
     return nn.Parameter(torch.zeros(*shape))
@@ -308,12 +304,11 @@ class MomentModel(nn.Module):
         need = lib.hirest_joint_encoder_x3_workspace_bytes(C.byref(x3["desc"]), B, T)
         if need == 0:
             raise RuntimeError("hirest_joint_encoder_x3: unsupported encoder shape")
-        ws = x3.get("ws")
-        if ws is None or ws.numel() < need or ws.device != f2d.device:
-            ws = x3["ws"] = torch.empty((need,), dtype=torch.uint8, device=f2d.device)
+        st = ops.stream_ptr()
+        ws, wsb = ops.stream_workspace(f2d.device, need, "encoder_x3", st)     # per stream: caption_batches runs this on several at once
         out = torch.empty((B * T, x3["width"]), dtype=torch.float32, device=f2d.device)
-        _lib.check(lib.hirest_joint_encoder_x3_forward(C.byref(x3["desc"]), f2d.data_ptr(), B, T, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                       ops.stream_ptr()), "hirest_joint_encoder_x3_forward")
+        _lib.check(lib.hirest_joint_encoder_x3_forward(C.byref(x3["desc"]), f2d.data_ptr(), B, T, out.data_ptr(), ws, wsb, st),
+                   "hirest_joint_encoder_x3_forward")
         return out
 
     # ------------------------------------------------------------------ kernels
@@ -324,7 +319,7 @@ class MomentModel(nn.Module):
         N = w.shape[0]
         if out is None:
             out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-        ws, wsb = ops.f32_gemm_workspace(a.device, lib.hirest_gemm_f32_workspace_bytes(M, N, K))
+        ws, wsb = ops.stream_workspace(a.device, lib.hirest_gemm_f32_workspace_bytes(M, N, K))
         _lib.check(lib.hirest_gemm_f32_ws(a.data_ptr(), K, w.data_ptr(), w.shape[1], bias.data_ptr() if bias is not None else None,
                                           resid.data_ptr() if resid is not None else None, N,
                                           periodic.data_ptr() if periodic is not None else None, period,
@@ -589,338 +584,40 @@ class MomentModel(nn.Module):
             out = out * keep
         return out.reshape(B, max_frames, D)
 
-    def _decoder_last_logprob(self, ids: torch.Tensor, enc_kv: List[torch.Tensor], row_add: torch.Tensor) -> torch.Tensor:
-        """DecoderModel.forward on the whole prefix (no KV cache, like the reference), then log_softmax of the LAST
-        position + row_add (train.py:547-566, beam.py:76).  ids [R,t] int64, enc_kv[i] [R,20,1536] -> [R, vocab]."""
-        c, lib = self._w(), _lib.load()
-        Dp = "clip4cap_model.decoder."
-        R, t = ids.shape
-        H, Dm = self.heads, 768
-        x = torch.empty((R * t, Dm), dtype=torch.float32, device=ids.device)
-        _lib.check(lib.hirest_embed_tokens(ids.contiguous().data_ptr(), c[Dp + "embeddings.word_embeddings.weight"].data_ptr(),
-                                           c[Dp + "embeddings.position_embeddings.weight"].data_ptr(), x.data_ptr(), None,
-                                           R, t, Dm, c[Dp + "embeddings.word_embeddings.weight"].shape[0], ops.stream_ptr()),
-                   "hirest_embed_tokens")
-        x = self._ln(x, c[Dp + "embeddings.LayerNorm.weight"], c[Dp + "embeddings.LayerNorm.bias"], 1e-12)
-        scale = (Dm // H) ** -0.5
-        for i in range(len(self.clip4cap_model.decoder.decoder.layer)):
-            p = Dp + f"decoder.layer.{i}."
-            qkv = self._gemm(x, c[f"dec_qkv_w.{i}"], c[f"dec_qkv_b.{i}"])
-            ctx = torch.empty_like(x)
-            _lib.check(lib.hirest_attention_f32_qkv(qkv.data_ptr(), 3 * Dm, qkv.data_ptr() + 4 * Dm, qkv.data_ptr() + 8 * Dm, 3 * Dm,
-                                                    ctx.data_ptr(), R, t, t, H, Dm // H, scale, 0.0, -10000.0, ops.stream_ptr()),
-                       "self attention")
-            s1 = self._gemm(ctx, c[p + "slf_attn.output.dense.weight"], c[p + "slf_attn.output.dense.bias"], resid=x)
-            s1 = self._ln(s1, c[p + "slf_attn.output.LayerNorm.weight"], c[p + "slf_attn.output.LayerNorm.bias"], 1e-12)
-            q2 = self._gemm(s1, c[p + "enc_attn.att.query.weight"], c[p + "enc_attn.att.query.bias"])
-            kv = enc_kv[i]
-            Tk = kv.shape[1]
-            _lib.check(lib.hirest_attention_f32_qkv(q2.data_ptr(), Dm, kv.data_ptr(), kv.data_ptr() + 4 * Dm, 2 * Dm, ctx.data_ptr(),
-                                                    R, t, Tk, H, Dm // H, scale, -10000.0, 0.0, ops.stream_ptr()), "cross attention")
-            d = self._gemm(ctx, c[p + "enc_attn.output.dense.weight"], c[p + "enc_attn.output.dense.bias"], resid=s1)
-            d = self._ln(d, c[p + "enc_attn.output.LayerNorm.weight"], c[p + "enc_attn.output.LayerNorm.bias"], 1e-12)
-            hmid = self._gemm(d, c[p + "intermediate.dense.weight"], c[p + "intermediate.dense.bias"], act=1)
-            y = self._gemm(hmid, c[p + "output.dense.weight"], c[p + "output.dense.bias"], resid=d)
-            x = self._ln(y, c[p + "output.LayerNorm.weight"], c[p + "output.LayerNorm.bias"], 1e-12)
-        last = x.reshape(R, t, Dm)[:, -1, :].contiguous()                     # dec_output[:, -1, :] (train.py:562)
-        cp = Dp + "classifier.cls.predictions."
-        hh = self._gemm(last, c[cp + "transform.dense.weight"], c[cp + "transform.dense.bias"], act=1)
-        hh = self._ln(hh, c[cp + "transform.LayerNorm.weight"], c[cp + "transform.LayerNorm.bias"], 1e-12)
-        logits = self._gemm(hh, c["lm_w"], c["lm_b"])
-        V = logits.shape[1]
-        out = torch.empty_like(logits)
-        _lib.check(lib.hirest_log_softmax_f32(logits.data_ptr(), V, row_add.data_ptr(), out.data_ptr(), V, R, V, ops.stream_ptr()),
-                   "hirest_log_softmax_f32")
-        return out
-
-    def _beam_search_cached(self, beams, enc_kv_all, num_beams, max_words, return_ids):
-        """Beam search without a host round trip per word: one C-side decoder step (csrc/caption.hip: ~35 kernels enqueued without
-        returning to Python, each beam's self-attention K / V kept and re-gathered by parent beam), the top-k over beams x vocabulary
-        and the beam bookkeeping (`hirest_beam_advance`: beam.py:70-92) all stay on the device.  The host only watches the "done" flags,
-        two steps behind, to stop early.  The row set never shrinks: a finished sample's rows keep being computed and are ignored."""
-        from .beam import BOS_ID, EOS_ID
-        c, lib = self._w(), _lib.load()
-        dev = c["dev"]
-        B, F = enc_kv_all[0].shape[0], enc_kv_all[0].shape[1]
-        R, nl, Dm = B * num_beams, len(enc_kv_all), 768
-        desc = self._dec_desc()
-        Vp = desc.vocab_padded
-        enc = [kv.repeat_interleave(num_beams, 0).contiguous() for kv in enc_kv_all]             # [R, F, 1536], loop invariant
-        enc_ptrs = (C.c_void_p * nl)(*[e.data_ptr() for e in enc])
-        ws = torch.empty(lib.hirest_caption_step_workspace_bytes(C.byref(desc), R), dtype=torch.uint8, device=dev)
-        cache = [torch.empty((2 * nl, R, max_words, Dm), dtype=torch.float32, device=dev) for _ in range(2)]   # ping-pong
-        ptrs = [(C.c_void_p * (2 * nl))(*[cb[i].data_ptr() for i in range(2 * nl)]) for cb in cache]
-        logp = torch.empty((R, Vp), dtype=torch.float32, device=dev)
-        # device-side beam state (beam.py: scores, next_ys, prev_ks) and the inputs of the next step, in two packed buffers (one fill,
-        # two small copies and one read-back per batch instead of a dozen): int32 = tokens | backptr | n_steps | done | ids | parents
-        nt = B * max_words * num_beams
-        ibuf = torch.zeros((2 * nt + 2 * B + 2 * R,), dtype=torch.int32, device=dev)
-        tokens, backptr = ibuf[:nt].view(B, max_words, num_beams), ibuf[nt:2 * nt].view(B, max_words, num_beams)
-        n_steps, done = ibuf[2 * nt:2 * nt + B], ibuf[2 * nt + B:2 * nt + 2 * B]
-        ids, parents = ibuf[2 * nt + 2 * B:2 * nt + 2 * B + R], ibuf[2 * nt + 2 * B + R:]
-        key = (B, num_beams, max_words, str(dev))
-        init = self.__dict__.setdefault("_beam_init", {}).get(key)
-        if init is None:                                  # constants of the search, built once per shape
-            add0 = torch.full((B, num_beams), -3.0e38, dtype=torch.float32)    # first step: only beam 0 competes
-            add0[:, 0] = 0.0                                                   # (beam.py:78)
-            init = self._beam_init[key] = (
-                torch.cat([torch.full((R,), BOS_ID, dtype=torch.int32), torch.arange(R, dtype=torch.int32)]).to(dev),
-                torch.cat([add0.reshape(-1), torch.zeros(R)]).to(dev))
-        ibuf[2 * nt + 2 * B:].copy_(init[0])
-        fbuf = init[1].clone()                             # float32 = add | scores
-        add, scores = fbuf[:R].view(B, num_beams), fbuf[R:]
-        # the stamped done flags of every step, pinned, ONE TABLE PER CALL: a table cached per shape could still be written by kernels of
-        # an earlier call that left its loop by an exception, or by a concurrent call of the same shape on another stream
-        # (caption_batches), and a stale stamp would end this search early
-        done_rows = torch.zeros((max_words, B), dtype=torch.int32).pin_memory()
-        done_host = [done_rows[t] for t in range(max_words)]
-        fused_tail = bool(getattr(self, "caption_fused_tail", True)) and num_beams <= 16 and Vp <= 32768    # (the tail kernels' limits)
-        copied = None if fused_tail else [torch.cuda.Event() for _ in range(max_words)]
-        need = lib.hirest_topk_workspace_bytes(B, num_beams * Vp, num_beams)
-        tk_ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
-        val = torch.empty((B, num_beams), dtype=torch.float32, device=dev)
-        idx = torch.empty((B, num_beams), dtype=torch.int32, device=dev)
-        st = ops.stream_ptr()
-        if fused_tail:
-            tail_ws = torch.empty(max(int(lib.hirest_caption_beam_tail_workspace_bytes(B, num_beams, Vp)), 16), dtype=torch.uint8,
-                                  device=dev)
-        for t in range(1, max_words + 1):
-            if fused_tail:
-                # one C call per word: the decoder step up to the LM-head logits (20 kernels), then log-softmax + beam score + top-k +
-                # bookkeeping + the done flags to pinned memory (2 kernels, fed the LM head's tile maxima)
-                _lib.check(lib.hirest_caption_beam_step(
-                    C.byref(desc), B, num_beams, t - 1, ids.data_ptr(), parents.data_ptr(), ptrs[t & 1] if t > 1 else None,
-                    ptrs[(t + 1) & 1], enc_ptrs, F, add.data_ptr(), logp.data_ptr(), max_words, EOS_ID, scores.data_ptr(),
-                    tokens.data_ptr(), backptr.data_ptr(), n_steps.data_ptr(), done.data_ptr(), done_host[t - 1].data_ptr(),
-                    ws.data_ptr(), ws.numel(), tail_ws.data_ptr(), tail_ws.numel(), st), "hirest_caption_beam_step")
-            else:
-                _lib.check(lib.hirest_caption_decode_step(
-                    C.byref(desc), R, t - 1, ids.data_ptr(), parents.data_ptr() if t > 1 else None,
-                    ptrs[t & 1] if t > 1 else None, ptrs[(t + 1) & 1], enc_ptrs, F, add.data_ptr(), logp.data_ptr(),
-                    ws.data_ptr(), ws.numel(), st), "hirest_caption_decode_step")
-                _lib.check(lib.hirest_topk_f32_ws(logp.data_ptr(), None, B, num_beams * Vp, num_beams, idx.data_ptr(), val.data_ptr(),
-                                                  tk_ws.data_ptr(), tk_ws.numel(), st), "hirest_topk_f32_ws")
-                _lib.check(lib.hirest_beam_advance(val.data_ptr(), idx.data_ptr(), B, num_beams, Vp, t - 1, max_words, EOS_ID,
-                                                   scores.data_ptr(), tokens.data_ptr(), backptr.data_ptr(), n_steps.data_ptr(),
-                                                   done.data_ptr(), ids.data_ptr(), parents.data_ptr(), add.data_ptr(), st),
-                           "hirest_beam_advance")
-                done_host[t - 1].copy_(done, non_blocking=True)
-            if fused_tail:
-                # the kernel stamps each sample's word with its step: read whatever has arrived of two steps ago, never wait
-                if t >= 3 and all((v >> 1) == t - 2 and (v & 1) for v in done_host[t - 3].tolist()):
-                    break
-                continue
-            copied[t - 1].record()
-            if t >= 3:                                   # look at the flags of two steps ago: never waits for the GPU
-                copied[t - 3].synchronize()
-                if int(done_host[t - 3].min()) == 1:
-                    break
-        if self.caption_device_readout:
-            return self._device_readout(scores, tokens, backptr, n_steps, B, num_beams, max_words, return_ids)
-        ih = ibuf[:2 * nt + B].cpu()                       # tokens | backptr | n_steps in one copy (this is the batch's synchronisation)
-        tok_h, bp_h = ih[:nt].view(B, max_words, num_beams).tolist(), ih[nt:2 * nt].view(B, max_words, num_beams).tolist()
-        n_h, sc_h = ih[2 * nt:].tolist(), scores.view(B, -1).cpu().tolist()
-        for b in range(B):                               # hand the recorded search to the host-side BeamState for the read-out
-            beams[b].scores = sc_h[b]
-            beams[b].backptr = [bp_h[b][j] for j in range(n_h[b])]
-            beams[b].tokens = [[BOS_ID] * num_beams] + [tok_h[b][j] for j in range(n_h[b])]
-        return self._caption_result(beams, return_ids)
-
-    # -------------------------------------------------------------------------------------------------------------------
-    # The same search replayed from hipGraphs (caption_batches): a word step is ~22 launches of ~3 us of host time each, and HIP
-    # serialises launches across host threads, so three batches in flight were HOST-bound (532 -> 766 captions/s instead of the ~2x
-    # the idle CUs allow).  Here all buffers of a search are static per (shape, slot), the word steps are captured once in chunks of
-    # CAPTION_GRAPH_CHUNK words, and a batch costs max_words / chunk graph launches.  Same kernels, same arguments, same tokens.
-    # -------------------------------------------------------------------------------------------------------------------
-    CAPTION_GRAPH_CHUNK = 8
-
-    def _caption_graph_ctx(self, B, num_beams, max_words, F, nl, slot):
-        from .beam import BOS_ID
-        c, lib = self._w(), _lib.load()
-        ctxs = c.setdefault("caption_graphs", {})           # lives and dies with the weight cache: the graphs hold its pointers
-        key = (B, num_beams, max_words, F, nl, slot, self.precision)      # (a captured graph holds the descriptor of its precision)
-        ctx = ctxs.get(key)
-        if ctx is not None:
-            return ctx
-        dev, desc = c["dev"], self._dec_desc()
-        R, Dm, Vp = B * num_beams, 768, desc.vocab_padded
-        nt = B * max_words * num_beams
-        add0 = torch.full((B, num_beams), -3.0e38, dtype=torch.float32)
-        add0[:, 0] = 0.0
-        ctx = {
-            "enc": [torch.empty((R, F, 2 * Dm), dtype=torch.float32, device=dev) for _ in range(nl)],
-            "ws": torch.empty(lib.hirest_caption_step_workspace_bytes(C.byref(desc), R), dtype=torch.uint8, device=dev),
-            "cache": [torch.empty((2 * nl, R, max_words, Dm), dtype=torch.float32, device=dev) for _ in range(2)],
-            "logp": torch.empty((R, Vp), dtype=torch.float32, device=dev),
-            "ibuf": torch.zeros((2 * nt + 2 * B + 2 * R,), dtype=torch.int32, device=dev),
-            "fbuf": torch.zeros((2 * R,), dtype=torch.float32, device=dev),
-            "ibuf0": torch.cat([torch.full((R,), BOS_ID, dtype=torch.int32), torch.arange(R, dtype=torch.int32)]).to(dev),
-            "fbuf0": torch.cat([add0.reshape(-1), torch.zeros(R)]).to(dev),
-            "tail_ws": torch.empty(max(int(lib.hirest_caption_beam_tail_workspace_bytes(B, num_beams, Vp)), 16), dtype=torch.uint8, device=dev),
-            "done_rows": torch.zeros((max_words, B), dtype=torch.int32).pin_memory(),
-            "graphs": [],
-        }
-        ctx["enc_ptrs"] = (C.c_void_p * nl)(*[e.data_ptr() for e in ctx["enc"]])
-        ctx["ptrs"] = [(C.c_void_p * (2 * nl))(*[cb[i].data_ptr() for i in range(2 * nl)]) for cb in ctx["cache"]]
-        ctxs[key] = ctx
-        return ctx
-
-    def _caption_issue_step(self, ctx, B, num_beams, max_words, F, t, st):
-        """One word (1-based t) of the search on the static buffers of `ctx`: hirest_caption_beam_step on stream pointer `st`."""
-        from .beam import EOS_ID
-        c, lib = self._w(), _lib.load()
-        R, nt = B * num_beams, B * max_words * num_beams
-        ibuf, fbuf = ctx["ibuf"], ctx["fbuf"]
-        tokens, backptr = ibuf[:nt], ibuf[nt:2 * nt]
-        n_steps, done = ibuf[2 * nt:2 * nt + B], ibuf[2 * nt + B:2 * nt + 2 * B]
-        ids, parents = ibuf[2 * nt + 2 * B:2 * nt + 2 * B + R], ibuf[2 * nt + 2 * B + R:]
-        add, scores = fbuf[:R], fbuf[R:]
-        _lib.check(lib.hirest_caption_beam_step(
-            C.byref(self._dec_desc()), B, num_beams, t - 1, ids.data_ptr(), parents.data_ptr(), ctx["ptrs"][t & 1] if t > 1 else None,
-            ctx["ptrs"][(t + 1) & 1], ctx["enc_ptrs"], F, add.data_ptr(), ctx["logp"].data_ptr(), max_words, EOS_ID, scores.data_ptr(),
-            tokens.data_ptr(), backptr.data_ptr(), n_steps.data_ptr(), done.data_ptr(), ctx["done_rows"][t - 1].data_ptr(),
-            ctx["ws"].data_ptr(), ctx["ws"].numel(), ctx["tail_ws"].data_ptr(), ctx["tail_ws"].numel(), st), "hirest_caption_beam_step")
-
-    def _caption_capture(self, ctx, B, num_beams, max_words, F):
-        """Capture the word steps of one search shape into hipGraphs (once per context; call from ONE thread while no other thread
-        issues HIP work: stream capture is process-global)."""
-        if ctx["graphs"]:
-            return
-        ctx["ibuf"][2 * B * max_words * num_beams + 2 * B:].copy_(ctx["ibuf0"])
-        ctx["fbuf"].copy_(ctx["fbuf0"])
-        for e in ctx["enc"]:
-            e.zero_()
-        for t in range(1, min(3, max_words) + 1):          # eager warm-up on these buffers (one-time kernel configuration must not be captured)
-            self._caption_issue_step(ctx, B, num_beams, max_words, F, t, ops.stream_ptr())
-        torch.cuda.synchronize()
-        step = max(1, int(self.CAPTION_GRAPH_CHUNK))
-        for lo in range(1, max_words + 1, step):
-            hi = min(max_words, lo + step - 1)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                st = ops.stream_ptr()
-                for t in range(lo, hi + 1):
-                    self._caption_issue_step(ctx, B, num_beams, max_words, F, t, st)
-            ctx["graphs"].append((lo, hi, g))
-        torch.cuda.synchronize()
-
-    def _beam_search_graph(self, beams, enc_kv_all, num_beams, max_words, return_ids, slot):
-        from .beam import BOS_ID
-        B, F = enc_kv_all[0].shape[0], enc_kv_all[0].shape[1]
-        nl = len(enc_kv_all)
-        ctx = self._caption_graph_ctx(B, num_beams, max_words, F, nl, slot)
-        if not ctx["graphs"]:
-            raise RuntimeError("hirest_amd: caption graphs are captured by caption_batches before its threads start")
-        R, nt = B * num_beams, B * max_words * num_beams
-        for e, kv in zip(ctx["enc"], enc_kv_all):
-            e.copy_(kv.repeat_interleave(num_beams, 0))
-        ctx["ibuf"].zero_()
-        ctx["ibuf"][2 * nt + 2 * B:].copy_(ctx["ibuf0"])
-        ctx["fbuf"].copy_(ctx["fbuf0"])
-        # (the previous search on this context ended with the blocking read-out below: nothing still writes the pinned table)
-        done_rows = ctx["done_rows"]
-        done_rows.zero_()
-        events = []
-        for k, (lo, hi, g) in enumerate(ctx["graphs"]):
-            # at most two chunks ahead of the GPU, so that a search whose samples have all emitted [SEP] stops within two chunks: the
-            # flags are those of the last word of chunk k - 2, which has completed (a finished sample's rows are inert meanwhile)
-            if k >= 2:
-                events[k - 2].synchronize()
-                last = ctx["graphs"][k - 2][1]
-                if all((v >> 1) == last and (v & 1) for v in done_rows[last - 1].tolist()):
-                    break
-            g.replay()
-            ev = torch.cuda.Event()
-            ev.record()
-            events.append(ev)
-        if self.caption_device_readout:
-            ib = ctx["ibuf"]
-            return self._device_readout(ctx["fbuf"][R:], ib[:nt], ib[nt:2 * nt], ib[2 * nt:2 * nt + B], B, num_beams, max_words, return_ids)
-        ih = ctx["ibuf"][:2 * nt + B].cpu()
-        tok_h, bp_h = ih[:nt].view(B, max_words, num_beams).tolist(), ih[nt:2 * nt].view(B, max_words, num_beams).tolist()
-        n_h, sc_h = ih[2 * nt:].tolist(), ctx["fbuf"][R:].view(B, -1).cpu().tolist()
-        for b in range(B):
-            beams[b].scores = sc_h[b]
-            beams[b].backptr = [bp_h[b][j] for j in range(n_h[b])]
-            beams[b].tokens = [[BOS_ID] * num_beams] + [tok_h[b][j] for j in range(n_h[b])]
-        return self._caption_result(beams, return_ids)
+    # the search itself lives in hirest_amd/caption_search.py; its switches stay here
+    CAPTION_GRAPH_CHUNK = 8           # words per captured hipGraph of the search replayed by caption_batches (caption_search.capture)
+    CAPTION_ROWS_IN_FLIGHT = 160      # beam rows of one merged search (caption_batches): 32 videos x 5 beams, the reference's default eval batch
+    caption_fused_tail = True         # log-softmax, top-k and beam bookkeeping inside the word step's C call; False: separate kernels
+    caption_device_readout = True     # the best hypothesis of every sample walked back on the device (hirest_beam_backtrack); False: on the host (BeamState)
 
     @torch.no_grad()
     def test_step_captioning(self, batch, num_beams=5, return_ids=False, **kwargs):
         """modeling.py:556-632.  Returns {'prediction': [str]} (token strings joined like the reference; ids are
         printed as decimal strings when no BERT vocab is attached via ``tokenizer_vocab``)."""
-        from .beam import BeamState
-        dev = self._w()["dev"]
-        c = self._w()
-        max_frames = int(getattr(self.args, "max_frames_step_captioning", 20)) if self.args is not None else 20
-        max_words = int(getattr(self.args, "max_words", 48)) if self.args is not None else 48
-        vis = batch["vis_feats"].to(dev).float()
-        mmask = self._host_moment_mask(batch)
-        B = vis.shape[0]
-        rows = self._trim_rows(mmask, max_frames, dev)
-        v = self._trim(vis, None, max_frames, idx=rows)
+        return self._caption_trimmed(*self._caption_inputs(batch, self._w()["dev"]), num_beams, return_ids, **kwargs)
+
+    def _caption_limits(self):
+        """(max_frames, max_words) of step captioning: args.max_frames_step_captioning / args.max_words, the reference's defaults without args."""
+        return int(getattr(self.args, "max_frames_step_captioning", 20)), int(getattr(self.args, "max_words", 48))
+
+    def _caption_inputs(self, batch, dev):
+        """trim_feats (modeling.py:529-554) of one loader batch: (vis [B, max_frames, D], asr [B, max_frames, Da] or None, text [B, 1024])."""
+        max_frames = self._caption_limits()[0]
+        rows = self._trim_rows(self._host_moment_mask(batch), max_frames, dev)
+        v = self._trim(batch["vis_feats"].to(dev).float(), None, max_frames, idx=rows)
         a = self._trim(batch["asr_feats"].to(dev).float(), None, max_frames, idx=rows) if self.use_asr else None
-        return self._caption_trimmed(v, a, self._text_feat(batch, dev), num_beams, return_ids, **kwargs)
+        return v, a, self._text_feat(batch, dev)
 
     def _caption_trimmed(self, v, a, text, num_beams, return_ids, **kwargs):
         """test_step_captioning behind trim_feats: v [B, max_frames, D] (a [B, max_frames, Da] or None) already trimmed, text [B, 1024]."""
-        from .beam import BeamState
-        c = self._w()
-        dev = c["dev"]
-        max_words = int(getattr(self.args, "max_words", 48)) if self.args is not None else 48
-        B, max_frames = v.shape[0], v.shape[1]
-        ones = torch.ones((B, max_frames), dtype=torch.long, device=dev)
+        c, (B, max_frames) = self._w(), v.shape[:2]
+        ones = torch.ones((B, max_frames), dtype=torch.long, device=c["dev"])
         base = self._fusion_base(v, text, a, ones)
         enc = self._features(base, ones.to(torch.int32).contiguous(), None, B, max_frames)          # [B*F, 768]
         # encoder-side K/V of the cross-attention are loop invariant: once per layer, [B, F, 1536]
         enc_kv_all = [self._gemm(enc, c[f"dec_kv_w.{i}"], c[f"dec_kv_b.{i}"]).reshape(B, max_frames, -1)
                       for i in range(len(self.clip4cap_model.decoder.decoder.layer))]
-        beams = [BeamState(num_beams) for _ in range(B)]
-        active = list(range(B))
-        if bool(getattr(self, "caption_kv_cache", True)):
-            if kwargs.get("graph_slot") is not None:         # caption_batches: replay the captured word steps of this slot's context
-                ctx = self._caption_graph_ctx(B, num_beams, max_words, max_frames, len(enc_kv_all), kwargs["graph_slot"])
-                if ctx["graphs"]:                            # (a batch of another size, e.g. the loader's last one, runs eagerly)
-                    return self._beam_search_graph(beams, enc_kv_all, num_beams, max_words, return_ids, kwargs["graph_slot"])
-            return self._beam_search_cached(beams, enc_kv_all, num_beams, max_words, return_ids)
-        for t in range(1, max_words + 1):
-            sel = torch.tensor([b for b in active for _ in range(num_beams)], dtype=torch.long, device=dev)
-            enc_kv = [kv.index_select(0, sel).contiguous() for kv in enc_kv_all]
-            # row_add = running beam scores (beam.py:76); on the first step only beam 0 competes (beam.py:78)
-            add = torch.tensor([(x if (t > 1 or k == 0) else -3.0e38) for b in active
-                                for k, x in enumerate(beams[b].scores)], dtype=torch.float32, device=dev)
-            seqs = [s for b in active for s in beams[b].current_state()]                            # full-prefix recompute
-            logp = self._decoder_last_logprob(torch.tensor(seqs, dtype=torch.long, device=dev), enc_kv, add)   # [n*beam, V]
-            n, V = len(active), logp.shape[1]
-            val, idx = ops.topk(logp.reshape(n, num_beams * V), num_beams)
-            val_h, idx_h = val.cpu().tolist(), idx.cpu().tolist()
-            active = [b for i, b in enumerate(active) if not beams[b].advance(val_h[i], idx_h[i], V)]
-            if not active:
-                break
-        return self._caption_result(beams, return_ids)
-
-    CAPTION_ROWS_IN_FLIGHT = 160      # beam rows of one merged search (caption_batches): 32 videos x 5 beams, the reference's default eval batch
-
-    def _caption_merge(self, group, dev):
-        """Several loader batches as ONE step-captioning batch: each batch is trimmed on its own (its T and its moment mask), the
-        [B_i, max_frames, D] results are concatenated and the merged batch carries an all-ones moment mask — trim_feats of exactly
-        max_frames selected rows is the identity, and rows a short moment left at zero stay zero.  Every kernel downstream is
-        batch-invariant, so a video's caption does not depend on what it is merged with."""
-        max_frames = int(getattr(self.args, "max_frames_step_captioning", 20)) if self.args is not None else 20
-        vs, as_, ts = [], [], []
-        for b in group:
-            vis = b["vis_feats"].to(dev).float()
-            rows = self._trim_rows(self._host_moment_mask(b), max_frames, dev)
-            vs.append(self._trim(vis, None, max_frames, idx=rows))
-            if self.use_asr:
-                as_.append(self._trim(b["asr_feats"].to(dev).float(), None, max_frames, idx=rows))
-            ts.append(self._text_feat(b, dev))
-        v = torch.cat(vs, 0)
-        merged = {"tasks": ["step_captioning"], "vis_feats": v, "moment_mask": torch.ones((v.shape[0], max_frames), dtype=torch.long),
-                  "text_feat": torch.cat(ts, 0)}
-        if self.use_asr:
-            merged["asr_feats"] = torch.cat(as_, 0)
-        return merged
+        return caption_search.search(self, enc_kv_all, num_beams, self._caption_limits()[1], return_ids, kwargs.get("graph_slot"))
 
     @torch.no_grad()
     def caption_batches(self, batches, num_beams=5, streams=1, return_ids=False, graphs=True, merge=True, rows_in_flight=None):
@@ -941,73 +638,7 @@ class MomentModel(nn.Module):
         fill those gaps; only the LM head (HBM-bound, all CUs) serialises.  Every call owns its buffers (workspace, K / V cache, beam
         state, pinned done table), the weight cache is read-only, and every kernel is batch-invariant, so each batch's result is
         exactly what ``test_step`` returns for it alone.  Returns the per-batch result dicts in order."""
-        import threading
-        batches = list(batches)
-        if merge and len(batches) > 1:
-            dev0 = self._w()["dev"]
-            cap = max(1, int(rows_in_flight or self.CAPTION_ROWS_IN_FLIGHT) // max(1, num_beams))      # videos per merged search
-            groups, cur, cnt = [], [], 0
-            for b in batches:
-                nb = int(b["vis_feats"].shape[0])
-                if cur and cnt + nb > cap:
-                    groups.append(cur); cur, cnt = [], 0
-                cur.append(b); cnt += nb
-            if cur:
-                groups.append(cur)
-            if any(len(g) > 1 for g in groups):
-                with torch.cuda.device(dev0):
-                    merged = [self._caption_merge(g, dev0) if len(g) > 1 else g[0] for g in groups]
-                res = self.caption_batches(merged, num_beams=num_beams, streams=streams, return_ids=return_ids, graphs=graphs, merge=False)
-                out = []
-                for g, r in zip(groups, res):           # hand each loader batch its own slice of the merged result
-                    lo = 0
-                    for b in g:
-                        nb = int(b["vis_feats"].shape[0])
-                        out.append({k: v[lo:lo + nb] for k, v in r.items()})
-                        lo += nb
-                return out
-        n = max(1, min(int(streams), len(batches)))
-        c = self._w()                                       # weight cache built (and the kernels' per-device setup done) before the threads
-        dev = c["dev"]
-        if n == 1 or len(batches) <= 1:
-            return [self.test_step_captioning(b, num_beams=num_beams, return_ids=return_ids) for b in batches]
-        results, errors = [None] * len(batches), []
-        results[0] = self.test_step_captioning(batches[0], num_beams=num_beams, return_ids=return_ids)   # warm: one-time kernel configuration
-        main = torch.cuda.current_stream(dev)
-        side = [torch.cuda.Stream(device=dev) for _ in range(n)]
-        if graphs and bool(getattr(self, "caption_kv_cache", True)) and bool(getattr(self, "caption_fused_tail", True)) and num_beams <= 16:
-            # the word steps of this batch shape, captured once per slot (hipGraphs: a batch then costs max_words / 8 launches instead
-            # of ~22 per word — three host threads issuing ~3-us launches through HIP's one launch lock were the bottleneck)
-            max_frames = int(getattr(self.args, "max_frames_step_captioning", 20)) if self.args is not None else 20
-            max_words = int(getattr(self.args, "max_words", 48)) if self.args is not None else 48
-            B0 = batches[1]["vis_feats"].shape[0]
-            nl = len(self.clip4cap_model.decoder.decoder.layer)
-            with torch.cuda.device(dev):
-                for w in range(n):
-                    self._caption_capture(self._caption_graph_ctx(B0, num_beams, max_words, max_frames, nl, w), B0, num_beams, max_words, max_frames)
-            slot_of = lambda w: w
-        else:
-            slot_of = lambda w: None
-
-        def work(w):
-            try:
-                torch.cuda.set_device(dev)
-                side[w].wait_stream(main)
-                with torch.cuda.stream(side[w]):
-                    for i in range(1 + w, len(batches), n):
-                        results[i] = self.test_step_captioning(batches[i], num_beams=num_beams, return_ids=return_ids, graph_slot=slot_of(w))
-            except BaseException as e:      # surfaced after the join
-                errors.append(e)
-        threads = [threading.Thread(target=work, args=(w,), daemon=True) for w in range(n)]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
-        for st in side:
-            main.wait_stream(st)
-        if errors:
-            raise errors[0]
-        return results
+        return caption_search.caption_batches(self, batches, num_beams, streams, return_ids, graphs, merge, rows_in_flight)
 
     @torch.no_grad()
     def end_to_end(self, batch, num_beams=5, return_ids=False):
@@ -1029,19 +660,6 @@ class MomentModel(nn.Module):
         step list (hirest_dataset.py:279 under --end_to_end)."""
         from . import cascade
         return cascade.run_end_to_end(self, [batch], num_beams=num_beams, return_ids=return_ids)[0]
-
-    caption_device_readout = True    # the best hypothesis of every sample walked back on the device (hirest_beam_backtrack); False: on the host (BeamState)
-
-    def _device_readout(self, scores, tokens, backptr, n_steps, B, num_beams, max_words, return_ids):
-        """The batch's synchronisation: one [B, max_words + 1] int32 copy (length | words of the best beam) instead of the whole token / parent
-        tables and a Python walk per sample (0.3 ms of host time behind a B = 32 search, with the GPU idle)."""
-        hyp = torch.empty((B, max_words + 1), dtype=torch.int32, device=scores.device)
-        _lib.check(_lib.load().hirest_beam_backtrack(scores.data_ptr(), tokens.data_ptr(), backptr.data_ptr(), n_steps.data_ptr(), B, num_beams,
-                                                     max_words, hyp.data_ptr(), ops.stream_ptr()), "hirest_beam_backtrack")
-        return self._caption_texts([r[1:1 + r[0]] for r in hyp.cpu().tolist()], return_ids)
-
-    def _caption_result(self, beams, return_ids):
-        return self._caption_texts([bm.best_hypothesis() for bm in beams], return_ids)
 
     def _caption_texts(self, hyps, return_ids):
         vocab = self.tokenizer_vocab

@@ -299,25 +299,25 @@ def to_device(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device)
 
 
-_F32_GEMM_WS = {}
-_F32_GEMM_RETIRED = []
+_STREAM_WS = {}
+_STREAM_WS_RETIRED = []
 
 
-def f32_gemm_workspace(device, nbytes: int, tag: int = 0, stream: Optional[int] = None):
-    """Scratch for hirest_gemm_f32_ws (the split form of few-tile fp32 GEMMs): one buffer per (device, tag, stream), so two
-    streams never share scratch (tag 1: the training step's side stream; `stream` = the raw stream pointer the GEMM is
-    enqueued on, default the current torch stream).  Grown geometrically on demand; an outgrown buffer is RETIRED, not
-    freed: torch's caching allocator only orders a block's reuse against the stream it was allocated on, and the split
-    GEMMs still in flight on this key's stream may be reading it — the retired blocks (their sizes sum to less than the
-    live buffer) stay referenced for the life of the process.  Returns (pointer, bytes) — (None, 0) when the problem
-    wants none."""
+def stream_workspace(device, nbytes: int, tag=0, stream: Optional[int] = None):
+    """Scratch that a C call uses on ONE stream (hirest_gemm_f32_ws, the split form of few-tile fp32 GEMMs; the bf16x3 encoder): one
+    buffer per (device, tag, stream), so two streams never share scratch (`tag` tells users on one stream apart — 0: the fp32 GEMMs,
+    1: the training step's side stream; `stream` = the raw stream pointer the call is enqueued on, default the current torch
+    stream).  Grown geometrically on demand; an outgrown buffer is RETIRED, not freed: torch's caching allocator only orders a
+    block's reuse against the stream it was allocated on, and the calls still in flight on this key's stream may be reading
+    it — the retired blocks (their sizes sum to less than the live buffer) stay referenced for the life of the process.
+    Returns (pointer, bytes) — (None, 0) when the problem wants none."""
     if nbytes <= 0:
         return None, 0
     key = (device.type, device.index, tag, int(stream) if stream is not None else stream_ptr())
-    buf = _F32_GEMM_WS.get(key)
+    buf = _STREAM_WS.get(key)
     if buf is None or buf.numel() < nbytes:
         if buf is not None:
-            _F32_GEMM_RETIRED.append(buf)
+            _STREAM_WS_RETIRED.append(buf)
         buf = torch.empty(max(int(nbytes), 2 * (buf.numel() if buf is not None else 0), 32 << 20), dtype=torch.uint8, device=device)
-        _F32_GEMM_WS[key] = buf
+        _STREAM_WS[key] = buf
     return buf.data_ptr(), buf.numel()

@@ -68,7 +68,7 @@ class _K:
         M, K = a.shape
         N = w.shape[0]
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-        ws, wsb = ops.f32_gemm_workspace(a.device, lib.hirest_gemm_f32_workspace_bytes(M, N, K))
+        ws, wsb = ops.stream_workspace(a.device, lib.hirest_gemm_f32_workspace_bytes(M, N, K))
         _chk(lib.hirest_gemm_f32_ws(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr() if bias is not None else None,
                                     resid.data_ptr() if resid is not None else None, N,
                                     periodic.data_ptr() if periodic is not None else None, period,
@@ -95,7 +95,7 @@ class _K:
     def layouts(a, lda, a_kmajor, w, ldw, w_kmajor, M, N, K, resid=None, stream=None):
         lib = _lib.load()
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-        ws, wsb = ops.f32_gemm_workspace(a.device, lib.hirest_gemm_f32_layouts_workspace_bytes(M, N, K), 0 if stream is None else 1, stream)
+        ws, wsb = ops.stream_workspace(a.device, lib.hirest_gemm_f32_layouts_workspace_bytes(M, N, K), 0 if stream is None else 1, stream)
         _chk(lib.hirest_gemm_f32_layouts(a.data_ptr(), lda, int(a_kmajor), w.data_ptr(), ldw, int(w_kmajor), None,
                                          resid.data_ptr() if resid is not None else None, resid.stride(0) if resid is not None else 0,
                                          out.data_ptr(), N, M, N, K, 0, ws, wsb, ops.stream_ptr() if stream is None else stream),
@@ -329,15 +329,15 @@ def task_param_names(model, task: str) -> List[str]:
 
 
 def _block_workspaces(dev, R, Hd, mlp, side_stream):
-    """Split-form scratch of the fp32 GEMMs of one block (ops.f32_gemm_workspace: one buffer per stream), sized for the largest problem."""
+    """Split-form scratch of the fp32 GEMMs of one block (ops.stream_workspace: one buffer per stream), sized for the largest problem."""
     lib = _lib.load()
     fwd = max(lib.hirest_gemm_f32_workspace_bytes(R, n, k) for n, k in ((3 * Hd, Hd), (Hd, Hd), (mlp, Hd), (Hd, mlp)))
     bwd = max(lib.hirest_gemm_f32_layouts_workspace_bytes(R, n, k) for n, k in ((mlp, Hd), (Hd, mlp), (Hd, Hd), (Hd, 3 * Hd)))
-    main = ops.f32_gemm_workspace(dev, max(fwd, bwd, 1))
+    main = ops.stream_workspace(dev, max(fwd, bwd, 1))
     if side_stream is None:
         return main, (None, 0)
     dw = max(lib.hirest_gemm_f32_layouts_workspace_bytes(m, n, R) for m, n in ((Hd, mlp), (mlp, Hd), (Hd, Hd), (3 * Hd, Hd)))
-    return main, ops.f32_gemm_workspace(dev, max(dw, 1), 1, side_stream)
+    return main, ops.stream_workspace(dev, max(dw, 1), 1, side_stream)
 
 
 def _split_block_weights(P, wqkvs, dev):
@@ -595,10 +595,10 @@ def _fusion_backward(model, P, S, dx, G):
     side = st["stream"].cuda_stream if st is not None else None
     shapes_main = [(R, E, Hd), (R, E, E)] + ([(R, A, E)] if asr else [])                                 # dX products: (M, N, K)
     shapes_side = [(Hd, E, R), (E, E, R), (E, S["vis2"].shape[1], R), (E, S["text"].shape[1], B)] + ([(E, A, R)] if asr else [])
-    d.ws, d.ws_bytes = ops.f32_gemm_workspace(dev, max(max(lib.hirest_gemm_f32_layouts_workspace_bytes(*m) for m in shapes_main), 1))
+    d.ws, d.ws_bytes = ops.stream_workspace(dev, max(max(lib.hirest_gemm_f32_layouts_workspace_bytes(*m) for m in shapes_main), 1))
     if side is not None:
         d.side_stream = side
-        d.side_ws, d.side_ws_bytes = ops.f32_gemm_workspace(dev, max(max(lib.hirest_gemm_f32_layouts_workspace_bytes(*m) for m in shapes_side), 1), 1, side)
+        d.side_ws, d.side_ws_bytes = ops.stream_workspace(dev, max(max(lib.hirest_gemm_f32_layouts_workspace_bytes(*m) for m in shapes_side), 1), 1, side)
     d.items, d.n_items, d.max_items = _K._c_items, C.pointer(_K._c_count), 64
     need = lib.hirest_train_fusion_backward_scratch_bytes(C.byref(d))
     if need == 0:

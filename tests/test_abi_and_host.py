@@ -652,3 +652,28 @@ def test_joint_inference_entry_points_refuse_bad_arguments_without_gpu(lib):
     # log_softmax(x, ldx, row_add, out, ldo, rows, V)
     assert lib.hirest_log_softmax_f32(None, 8, None, X, 8, 2, 8, None) == BAD and lib.hirest_log_softmax_f32(X, 8, None, None, 8, 2, 8, None) == BAD
     assert lib.hirest_log_softmax_f32(X, 8, None, X, 8, 0, 8, None) == BAD and lib.hirest_log_softmax_f32(X, 8, None, X, 8, 2, 0, None) == BAD
+
+
+def test_stream_workspace_is_keyed_by_stream_and_retires_outgrown_buffers():
+    """ops.stream_workspace on the CPU with explicit stream keys: one buffer per (device, tag, stream); a request that fits returns the
+    same buffer; a larger one gets a new buffer of at least twice the size while the old tensor stays referenced (work still in flight on
+    that stream may be reading it) and no other key's buffer moves."""
+    from hirest_amd import ops
+    cpu, MB = torch.device("cpu"), 1 << 20
+    s1, s2 = 0x7001, 0x7002                                 # stand-ins for raw stream pointers
+    tag = "test_stream_workspace"                           # this test's own buffers
+    assert ops.stream_workspace(cpu, 0, tag, s1) == (None, 0) and ops.stream_workspace(cpu, -5, tag, s1) == (None, 0)
+    p1, n1 = ops.stream_workspace(cpu, 1000, tag, s1)
+    p2, n2 = ops.stream_workspace(cpu, 1000, tag, s2)
+    assert p1 != p2 and n1 == n2 == 32 * MB                 # the minimum size
+    assert ops.stream_workspace(cpu, n1, tag, s1) == (p1, n1) and ops.stream_workspace(cpu, 1, tag, s1) == (p1, n1)
+    po, no = ops.stream_workspace(cpu, 1000, tag + ".other", s1)        # another tag on the same stream
+    assert po not in (p1, p2) and no == 32 * MB
+    old = ops._STREAM_WS[("cpu", None, tag, s1)]
+    retired = len(ops._STREAM_WS_RETIRED)
+    q1, m1 = ops.stream_workspace(cpu, n1 + 1, tag, s1)
+    assert q1 != p1 and m1 >= 2 * n1
+    assert len(ops._STREAM_WS_RETIRED) == retired + 1 and ops._STREAM_WS_RETIRED[-1] is old and old.data_ptr() == p1 and old.numel() == n1
+    assert ops.stream_workspace(cpu, 1000, tag, s2) == (p2, n2)          # the other stream's buffer is untouched
+    assert ops.stream_workspace(cpu, 1000, tag + ".other", s1) == (po, no)
+    assert ops.stream_workspace(cpu, 1000, tag, s1) == (q1, m1)

@@ -1,8 +1,9 @@
-"""Host-side pieces of step captioning.  MomentModel._trim_index_table (the vectorised form test_step_captioning uses) against the per-sample list walk _trim_index, which restates
+"""Host-side pieces of step captioning.  caption_search.beam_layout: the one statement of the packed beam-state buffers.  MomentModel._trim_index_table (the vectorised form test_step_captioning uses) against the per-sample list walk _trim_index, which restates
 trim_feats (modeling.py:529-554): more selected frames than slots -> the first max_frames; fewer -> frame j repeated
 (j + 1) F // N - j F // N times; none -> zero rows (-1)."""
 import random
 
+import pytest
 import torch
 
 from hirest_amd.moment_model import MomentModel
@@ -42,3 +43,23 @@ def test_caption_texts_with_and_without_a_vocabulary():
     m.tokenizer_vocab = ["[PAD]", "[CLS]", "[SEP]", "cut", "##ting", "board", "##s"]
     res = m._caption_texts([[3, 4, 5, 6, 2, 3], [5, 0, 3], [2]], False)
     assert res == {"prediction": ["cutting boards", "board", ""]}
+
+
+@pytest.mark.parametrize("B,beams,max_words", [(1, 1, 1), (1, 7, 3), (5, 5, 48), (32, 3, 48)])
+def test_beam_layout_names_disjoint_slices_that_cover_the_buffers(B, beams, max_words):
+    """ibuf = tokens | backptr | n_steps | done | ids | parents and fbuf = add | scores: in that order, back to back, of the sizes the
+    kernels index them with; the host read-out copies everything in front of `done` and reset() rewrites everything from `ids` on."""
+    from hirest_amd.caption_search import beam_layout
+    L = beam_layout(B, beams, max_words)
+    nt, R = B * max_words * beams, B * beams
+    for slices, length, want in ((L.ibuf, L.ibuf_len, [("tokens", nt), ("backptr", nt), ("n_steps", B), ("done", B), ("ids", R), ("parents", R)]),
+                                 (L.fbuf, L.fbuf_len, [("add", R), ("scores", R)])):
+        assert list(slices) == [name for name, _ in want]
+        at = 0
+        for name, n in want:                              # back to back from 0: pairwise disjoint, in order
+            assert (slices[name].start, slices[name].stop, slices[name].step) == (at, at + n, None), name
+            at += n
+        assert at == length                               # ... and they cover the buffer exactly
+        assert sorted(i for s in slices.values() for i in range(length)[s]) == list(range(length))
+    assert (L.readout.start, L.readout.stop) == (0, L.ibuf["done"].start) and L.readout.step is None
+    assert L.reset.start == L.ibuf["ids"].start and range(L.ibuf_len)[L.reset] == range(L.ibuf["ids"].start, L.ibuf_len)

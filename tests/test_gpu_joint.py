@@ -594,3 +594,38 @@ def test_caption_batches_with_three_in_flight_equal_sequential_calls(dev, golden
     short = [model.test_step(b, num_beams=beams, return_ids=True)["token_ids"] for b in batches[:4]]
     assert all(len(h) <= 2 for hyp in short for h in hyp)
     assert [g["token_ids"] for g in model.caption_batches(batches[:4], num_beams=beams, streams=2, return_ids=True)] == short
+
+
+def test_caption_batches_bf16x3_two_streams_with_different_workspace_requests(dev, golden_dir):
+    """precision 'bf16x3' under caption_batches(streams=2): the split-operand encoder (hirest_joint_encoder_x3_forward) runs on two host
+    threads and HIP streams at once, and batches 2 and 4 are cut to 3 videos, so consecutive calls on one stream ask for different
+    amounts of scratch.  Every batch's token ids must equal those of one test_step call for it alone, with the word steps issued
+    eagerly and replayed from hipGraphs.
+
+    A guard, not a proof: with ONE workspace per model two concurrent encoder calls wrote the same scratch, and whether a token then
+    changed was a matter of timing, so that code could pass this test.  The proof is in the code — the encoder's scratch comes from
+    ops.stream_workspace, whose key contains the stream (tests/test_abi_and_host.py checks the helper itself)."""
+    import hirest_amd
+    from hirest_amd.synth import joint_inputs, CAPTION_CASES
+    shapes = {k: tuple(v) for k, v in json.load(open(os.path.join(golden_dir, "joint_schema.json"))).items()}
+    sd = synth.joint_state_dict(shapes, 31)
+    sd["clip4cap_model.decoder.classifier.cls.predictions.bias"][102] += 1.5
+    model = hirest_amd.MomentModel(n_frames=-1, asr_dim=384, args=None, clip_model=None)
+    model.load_state_dict(sd, strict=False)
+    model = model.to(dev).eval().set_precision("bf16x3")
+    B, T, beams, lens = CAPTION_CASES["c5"]
+    batches = []
+    for i in range(4):
+        vis, asr, text, vis_mask, _, _ = joint_inputs(f"cap.x3ws{i}", B, T, 61 + 5 * i)
+        mm = torch.zeros(B, T, dtype=torch.long)
+        for b in range(B):
+            mm[b, 5 + b:5 + b + 6 + ((7 * i + 3 * b) % 30)] = 1
+        batch = {"tasks": ["step_captioning"], "vis_feats": vis, "vis_mask": vis_mask, "moment_mask": mm, "asr_feats": asr, "text_feat": text}
+        if i in (1, 3):                                  # batches 2 and 4: three videos
+            batch = {k: (v[:3] if torch.is_tensor(v) else v) for k, v in batch.items()}
+        batches.append(batch)
+    want = [model.test_step(b, num_beams=beams, return_ids=True)["token_ids"] for b in batches]
+    assert [len(w) for w in want] == [5, 3, 5, 3]
+    for graphs in (False, True):
+        got = model.caption_batches(batches, num_beams=5, streams=2, merge=False, graphs=graphs, return_ids=True)
+        assert [g["token_ids"] for g in got] == want, graphs

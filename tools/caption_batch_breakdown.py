@@ -6,7 +6,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import hirest_amd
-from hirest_amd import synth, _lib
+from hirest_amd import synth, _lib, caption_search
 from hirest_amd.synth import joint_inputs
 shapes = {k: tuple(v) for k, v in json.load(open(os.path.join(ROOT, "tests", "golden", "joint_schema.json"))).items()}
 sd = synth.joint_state_dict(shapes, 31)
@@ -24,13 +24,13 @@ for _ in range(3):
     model.test_step(batch, num_beams=beams)
 lib = _lib.load()
 acc = {"search": 0.0, "words": 0.0, "calls": 0}
-inner = type(model)._beam_search_cached
-def timed_search(self, *a, **k):
+inner = caption_search.beam_search                     # the eager driver; caption_search.search looks it up per call
+def timed_search(*a, **k):
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    r = inner(self, *a, **k)
+    r = inner(*a, **k)
     torch.cuda.synchronize(); acc["search"] += time.perf_counter() - t0
     return r
-type(model)._beam_search_cached = timed_search
+caption_search.beam_search = timed_search
 step = lib.hirest_caption_beam_step
 first = [None]
 def timed_step(*a):
