@@ -6,6 +6,8 @@ from .eva_clip import (EVA_CLIP, build_eva_model_and_transforms, create_model, i
 from .tokenizer import tokenize  # noqa: F401
 from .moment_model import MomentModel  # noqa: F401
 from .sentence_encoder import SentenceTransformer  # noqa: F401
+from .bert_score import BERTScorer  # noqa: F401
+from .evaluation import evaluate_bert_score  # noqa: F401
 from . import optim  # noqa: F401
 from . import cascade  # noqa: F401
 from .cascade import run_end_to_end, end_to_end_results  # noqa: F401

@@ -7,6 +7,7 @@ names and dict layouts, so a driver holding predictions can score them without t
     compute_step_bound_scores(gt, pred, video_to_cat)       # evaluate.py:123-188  step recall / precision at tIoU
     preprocess_moment_bounds(gt, pred)                      # evaluate.py:322-412  filter + NMS + gap filling
     evaluate_clip_score(gt, pred, video_to_cat, model, dir) # evaluate.py:190-320  the CLIPScore leg of step captioning
+    evaluate_bert_score(gt, pred, video_to_cat, scorer)     # evaluate.py:190-320  the BERTScore_F1 leg of step captioning
 
 ``gt`` / ``pred`` are the reference's dicts (or JSON paths).  The category maps are arguments (the reference reads them
 into module globals in ``__main__``, :444-466).  Intervals are flattened to float64 tensors, the per-pair / per-video
@@ -14,7 +15,8 @@ work runs in ``csrc/eval.hip`` in double precision with Python's operation order
 means are taken on the host in the reference's summation order, so results are equal to the last bit.
 Tensor-level entry points (`interval_iou`, `step_bound_pr`, `preprocess_bounds`) take device tensors directly.
 No CPU fallback.  CLIPScore runs as a batch: frames decoded and encoded once on the device, one scoring kernel
-(``csrc/score.hip``); the other caption metrics (BERTScore / entailment / COCO, :190-320) are out of scope.
+(``csrc/score.hip``); BERTScore likewise: unique sentences encoded once, one matching kernel (``csrc/bertscore.hip``).  The other
+caption metrics (entailment / COCO, :190-320) are out of scope.
 """
 from __future__ import annotations
 
@@ -239,6 +241,40 @@ def _frame_files(frame_dir, video: str) -> List[str]:
     return frames
 
 
+def _caption_plan(gt: dict, pred: dict, video_to_cat: Optional[Dict[str, str]], per_category: bool,
+                  videos: Optional[Sequence[str]] = None):
+    """What evaluate_moment_summarization's loops (evaluate.py:212-291) decide for every model-based caption metric, host only:
+    ``(order, captions, candidates, references, categories)`` — the GT videos walked, every (video, caption index) in loop order,
+    the lower-cased predicted and GT sentence of each (:233-234), and ``{category: {"Total": matching videos, "captions": indices
+    into captions}}`` in ``_categories`` order without the categories that have no caption (:290-291).  ``video_to_cat[video]`` is
+    looked up for every GT video (:225: a missing one raises KeyError); None: only "all", no lookups."""
+    if videos is None:
+        order = list(gt)
+    else:
+        wanted = set(videos)
+        missing = wanted - set(gt)
+        if missing:
+            raise KeyError(f"videos not in the GT data: {sorted(missing)[:5]}")
+        order = [v for v in gt if v in wanted]
+    cats = _categories(video_to_cat) if (per_category and video_to_cat is not None) else ["all"]
+    members = {c: [] for c in cats}
+    totals = {c: 0 for c in cats}
+    captions, candidates, references = [], [], []
+    for video in order:
+        video_cat = video_to_cat[video] if video_to_cat is not None else None     # evaluate.py:219, KeyError like VIDEOS_TO_CAT
+        mine = [c for c in cats if c == "all" or c == video_cat]
+        for c in mine:
+            totals[c] += 1
+        for i, d in enumerate(gt[video]["captions"]):
+            for c in mine:
+                members[c].append(len(captions))
+            captions.append((video, i))
+            references.append(d["sentence"].lower())
+            candidates.append(pred[video]["captions"][i]["sentence"].lower())
+    categories = {c: {"Total": totals[c], "captions": members[c]} for c in cats if members[c]}
+    return order, captions, candidates, references, categories
+
+
 class ClipScorePlan:
     """Host-side selection of a CLIPScore run (see ``clip_score_plan``).
 
@@ -278,31 +314,14 @@ def clip_score_plan(gt_data, pred_data, frame_dir, video_to_cat: Optional[Dict[s
     from .tokenizer import tokenize
     gt, pred = _load(gt_data), _load(pred_data)
     no_frames = _no_frames(frame_dir)
-    if videos is None:
-        order = list(gt)
-    else:
-        wanted = set(videos)
-        missing = wanted - set(gt)
-        if missing:
-            raise KeyError(f"videos not in the GT data: {sorted(missing)[:5]}")
-        order = [v for v in gt if v in wanted]
-    cats = _categories(video_to_cat) if (per_category and video_to_cat is not None) else ["all"]
-    members = {c: [] for c in cats}
-    totals = {c: 0 for c in cats}
-    captions, candidates, skip, scored, sel_rows = [], [], [], [], []
+    order, captions, candidates, _, categories = _caption_plan(gt, pred, video_to_cat, per_category, videos)
+    skip, scored, sel_rows = [], [], []
     frames, row_of = [], {}
+    k = 0
     for video in order:
-        video_cat = video_to_cat[video] if video_to_cat is not None else None     # evaluate.py:219, KeyError like VIDEOS_TO_CAT
-        mine = [c for c in cats if c == "all" or c == video_cat]
-        for c in mine:
-            totals[c] += 1
         files = None
         for i, d in enumerate(gt[video]["captions"]):
-            k = len(captions)
-            captions.append((video, i))
-            candidates.append(pred[video]["captions"][i]["sentence"].lower())
-            for c in mine:
-                members[c].append(k)
+            k += 1
             if no_frames:
                 skip.append(True)
                 continue
@@ -321,11 +340,10 @@ def clip_score_plan(gt_data, pred_data, frame_dir, video_to_cat: Optional[Dict[s
                     row_of[f] = len(frames)
                     frames.append(f)
                 row.append(row_of[f])
-            scored.append(k)
+            scored.append(k - 1)
             sel_rows.append(row)
     sel = np.array(sel_rows, dtype=np.int32).reshape(len(sel_rows), CLIP_SCORE_FRAMES)
     tokens = tokenize([candidates[k] for k in scored], context_length=context_length, truncate=False)
-    categories = {c: {"Total": totals[c], "captions": members[c]} for c in cats if members[c]}
     return ClipScorePlan(captions, candidates, skip, scored, sel, frames, tokens, categories)
 
 
@@ -432,3 +450,21 @@ def evaluate_clip_score(gt_data, pred_data, video_to_cat: Dict[str, str], model,
             clip_scores = [0]
         results[c] = {"CLIPScore": float(np.average(clip_scores)), "Total": m["Total"]}
     return results
+
+
+def evaluate_bert_score(gt_data, pred_data, video_to_cat: Dict[str, str], scorer, per_category: bool = False, device=None,
+                        stats: Optional[dict] = None) -> dict:
+    """The BERTScore leg of evaluate_moment_summarization (evaluate.py:190-320): ``{category: {"BERTScore_F1": float, "Total": int}}``.
+
+    Categories, their order, ``Total`` and the rule that drops a category without captions are ``clip_score_plan``'s (one shared
+    walk of the GT videos).  Per caption the pair is (predicted sentence, GT sentence), both lower-cased (:233-234).  ``scorer`` is a
+    ``hirest_amd.bert_score.BERTScorer``: every unique sentence is encoded once, one ``hirest_bertscore_greedy`` launch scores all
+    pairs of all categories, and a category's figure is ``f.mean().item()`` of the fp32 F of its pairs in loop order (:308)."""
+    gt, pred = _load(gt_data), _load(pred_data)
+    _, captions, candidates, references, categories = _caption_plan(gt, pred, video_to_cat, per_category)
+    if not captions:
+        return {}
+    if device is not None:
+        scorer.to(_dev(device))
+    f = scorer.score_device(candidates, references, stats=stats)[:, 2].cpu()          # the one device -> host read
+    return {c: {"BERTScore_F1": f[torch.tensor(m["captions"])].mean().item(), "Total": m["Total"]} for c, m in categories.items()}

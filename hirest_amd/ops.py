@@ -289,6 +289,42 @@ def clip_score(img_rows: torch.Tensor, txt_rows: torch.Tensor, sel) -> torch.Ten
                                      sel.data_ptr(), C, sel.shape[1], E, out.data_ptr(), stream_ptr()), "hirest_clip_score")
     return out
 
+BERTSCORE_MAX_TOKENS = 1024      # HIREST_BERTSCORE_MAX_TOKENS
+
+
+@on_tensor_device
+def bertscore_greedy(states: torch.Tensor, seq_off, tok_weight: torch.Tensor, cand_seq, ref_seq) -> torch.Tensor:
+    """[n_pairs, 3] fp32 (P, R, F) of BERTScore's greedy matching (hirest_bertscore_greedy).  states: [tokens, D] fp32 GPU rows of
+    the unique sentences (row stride a multiple of 4), sentence s = rows seq_off[s] .. seq_off[s+1]; tok_weight: [tokens] fp32;
+    cand_seq / ref_seq: int [n_pairs] sentence ids (an id outside [0, n_seq) gives NaN for its pair).  The int tables may live on
+    the CPU or the GPU; a CPU seq_off is checked against the rows here."""
+    lib = _lib.load()
+    if not isinstance(states, torch.Tensor) or not states.is_cuda or states.dtype != torch.float32 or states.dim() != 2 \
+            or (states.numel() and states.stride(1) != 1):
+        raise RuntimeError("bertscore_greedy.states: expected a [tokens, D] fp32 GPU tensor with unit column stride")
+    rows, D = states.shape
+    ld = states.stride(0) if rows > 1 else D
+    seq_off, cand_seq, ref_seq = torch.as_tensor(seq_off), torch.as_tensor(cand_seq), torch.as_tensor(ref_seq)
+    if seq_off.dim() != 1 or seq_off.numel() < 2 or cand_seq.dim() != 1 or cand_seq.shape != ref_seq.shape:
+        raise RuntimeError("bertscore_greedy: seq_off must be [n_seq + 1 >= 2], cand_seq and ref_seq [n_pairs]")
+    if not seq_off.is_cuda:
+        lens = seq_off[1:] - seq_off[:-1]
+        if int(seq_off[0]) < 0 or int(seq_off[-1]) > rows or int(lens.min()) < 1 or int(lens.max()) > BERTSCORE_MAX_TOKENS:
+            raise RuntimeError(f"bertscore_greedy.seq_off: sentences of 1 .. {BERTSCORE_MAX_TOKENS} rows inside the {rows} rows")
+    if tok_weight.shape != (rows,):
+        raise RuntimeError(f"bertscore_greedy.tok_weight: expected [{rows}], got {tuple(tok_weight.shape)}")
+    dev = states.device
+    seq_off, cand_seq, ref_seq = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (seq_off, cand_seq, ref_seq))
+    n_pairs = cand_seq.numel()
+    out = torch.empty((n_pairs, 3), dtype=torch.float32, device=dev)
+    if n_pairs == 0:
+        return out
+    _lib.check(lib.hirest_bertscore_greedy(states.data_ptr(), ld, D, seq_off.data_ptr(), seq_off.numel() - 1,
+                                           _dev(tok_weight, torch.float32, "bertscore_greedy.tok_weight"), cand_seq.data_ptr(),
+                                           ref_seq.data_ptr(), n_pairs, out.data_ptr(), stream_ptr()), "hirest_bertscore_greedy")
+    return out
+
+
 def to_device(t: torch.Tensor, device) -> torch.Tensor:
     """t.to(device) that does not stall the host when it need not: a pinned CPU tensor (what DataLoader(pin_memory=True) delivers:
     hirest_dataset.py:614,624) is copied asynchronously on the current stream — the kernels that read it are behind it on the same

@@ -50,58 +50,54 @@ def _load_weights(model_dir: str) -> Dict[str, torch.Tensor]:
     raise FileNotFoundError(f"no model.safetensors / pytorch_model.bin under {model_dir}")
 
 
-class SentenceTransformer(nn.Module):
-    def __init__(self, model_name_or_path: Optional[str] = None, device: Optional[Union[str, torch.device]] = None, *,
-                 config: Optional[dict] = None, state_dict: Optional[Dict[str, torch.Tensor]] = None,
-                 vocab: Optional[Sequence[str]] = None, max_seq_length: Optional[int] = None):
-        """Either a local sentence-transformers model directory (``config.json``, ``model.safetensors`` or
-        ``pytorch_model.bin``, ``vocab.txt``, optional ``sentence_bert_config.json``) — the hub name the reference passes cannot
-        be downloaded here, so a name that is not a directory raises — or explicit ``config`` + ``state_dict`` (+ ``vocab``)."""
-        super().__init__()
-        if config is None:
-            if model_name_or_path is None or not os.path.isdir(model_name_or_path):
-                raise FileNotFoundError(f"{model_name_or_path!r} is not a local model directory (no network access: download "
-                                        "sentence-transformers/all-MiniLM-L6-v2 beforehand and pass its path)")
-            with open(os.path.join(model_name_or_path, "config.json")) as f:
-                config = json.load(f)
-            state_dict = _load_weights(model_name_or_path)
-            vocab_file = os.path.join(model_name_or_path, "vocab.txt")
-            if vocab is None and os.path.exists(vocab_file):
-                with open(vocab_file, encoding="utf-8") as f:
-                    vocab = f.readlines()
-            sb = os.path.join(model_name_or_path, "sentence_bert_config.json")
-            if max_seq_length is None and os.path.exists(sb):
-                with open(sb) as f:
-                    max_seq_length = json.load(f).get("max_seq_length")
+class PackedBertEncoder(nn.Module):
+    """The post-LN BERT / RoBERTa encoder stack over sentences packed row after row: the weights under their checkpoint names, the
+    fused per-layer operands, and the layer loop that returns the [tokens, hidden] states.  ``SentenceTransformer`` pools them into
+    sentence vectors; ``hirest_amd.bert_score.BERTScorer`` matches them token by token.
+
+    ``num_layers``: keep only the first so many layers (the later ones are neither stored nor run).  A checkpoint's ``bert.`` /
+    ``roberta.`` key prefix is dropped.  ``model_type == "roberta"`` in the config puts token i at position ``pad_token_id + 1 + i``."""
+
+    _NAME = "hirest_amd.SentenceTransformer"
+
+    def _init_encoder(self, config: dict, state_dict: Optional[Dict[str, torch.Tensor]], num_layers: Optional[int] = None):
         if config.get("hidden_act", "gelu") != "gelu" or config.get("position_embedding_type", "absolute") != "absolute":
             raise NotImplementedError("only the BERT configuration of all-MiniLM-L6-v2 (erf GELU, absolute positions) is built")
         self.config = dict(config)
         self.hidden = int(config["hidden_size"])
         self.layers = int(config["num_hidden_layers"])
+        if num_layers is not None:
+            if not 1 <= int(num_layers) <= self.layers:
+                raise ValueError(f"num_layers {num_layers} outside 1 .. {self.layers}")
+            self.layers = int(num_layers)
         self.heads = int(config["num_attention_heads"])
         self.eps = float(config.get("layer_norm_eps", 1e-12))
+        self.pos_offset = int(config.get("pad_token_id", 1)) + 1 if config.get("model_type") == "roberta" else 0
         self.dh = self.hidden // self.heads
         if self.dh > _AH_MAX or self.hidden % self.heads or self.hidden % 4:
             raise NotImplementedError(f"head width {self.dh} > {_AH_MAX}")
         self.ah = (self.dh + 3) // 4 * 4               # head width as the kernels see it (MiniLM: 32, no padding) ...
         while (self.heads * self.ah) % 16:             # ... such that the output projection's reduction length suits the GEMM
             self.ah += 4
-        self.max_seq_length = int(max_seq_length or 256)                      # all-MiniLM-L6-v2's sentence_bert_config.json
-        self.max_seq_length = min(self.max_seq_length, int(config["max_position_embeddings"]))
-        self.tokenizer = WordPieceTokenizer(vocab) if vocab is not None else None
         if state_dict is None:
             raise ValueError("state_dict required with an explicit config")
-        sd = {k[5:] if k.startswith("bert.") else k: v for k, v in state_dict.items()}
+        sd = {}
+        for k, v in state_dict.items():
+            for prefix in ("bert.", "roberta."):
+                if k.startswith(prefix):
+                    k = k[len(prefix):]
+            sd[k] = v
         self._names = []
         for k, v in sd.items():
             if k.endswith("position_ids") or k.endswith("token_type_ids"):
                 continue
+            if num_layers is not None and (k.startswith("pooler.") or k.startswith("lm_head.") or
+                                           (k.startswith("encoder.layer.") and int(k.split(".")[2]) >= self.layers)):
+                continue                               # a cut encoder: the layers after the cut and the heads are not kept
             # parameter names cannot hold dots: keep the checkpoint's name with '/' and map back in state_dict consumers
             self.register_parameter(k.replace(".", "/"), nn.Parameter(v.detach().float().clone(), requires_grad=False))
             self._names.append(k)
         self._cache = None
-        if device is not None:
-            self.to(device)
 
     # nn.Module plumbing: any move / cast invalidates the fused-weight cache
     def _apply(self, fn, *a, **k):
@@ -115,15 +111,12 @@ class SentenceTransformer(nn.Module):
     def device(self) -> torch.device:
         return self._p("embeddings.word_embeddings.weight").device
 
-    def get_sentence_embedding_dimension(self) -> int:
-        return self.hidden
-
     def _w(self):
         if self._cache is not None:
             return self._cache
         dev = self.device
         if dev.type != "cuda":
-            raise RuntimeError("hirest_amd.SentenceTransformer runs on MI355X only (no CPU fallback); move the model to a GPU")
+            raise RuntimeError(f"{self._NAME} runs on MI355X only (no CPU fallback); move the model to a GPU")
         f = lambda n: self._p(n).detach().float().contiguous()
         H, dh, D = self.heads, self.dh, self.hidden
         c = {"word": f("embeddings.word_embeddings.weight"),
@@ -168,9 +161,10 @@ class SentenceTransformer(nn.Module):
     def _ln(self, x, w, b):
         return ops.layernorm(x, w, b, self.eps, torch.empty_like(x))
 
-    def _encode_packed(self, ids: torch.Tensor, pos_ids: torch.Tensor, seq_off: torch.Tensor, n: int, max_len: int) -> torch.Tensor:
+    def _token_states(self, ids: torch.Tensor, pos_ids: torch.Tensor, seq_off: torch.Tensor, n: int, max_len: int) -> torch.Tensor:
         """n ragged sentences packed row after row (ids / pos_ids int32 [tokens], seq_off int32 [n + 1], all on the device)
-        -> [n, hidden] unit rows.  Every GEMM / LayerNorm runs once over all tokens; only attention and pooling know sentences."""
+        -> [tokens, hidden] states after the encoder's ``self.layers`` layers (the last one's output LayerNorm).  Every GEMM /
+        LayerNorm runs once over all tokens; only attention knows sentences."""
         c, lib = self._w(), _lib.load()
         D, H, rows = self.hidden, self.heads, ids.numel()
         x = torch.empty((rows, D), dtype=torch.float32, device=ids.device)
@@ -188,8 +182,80 @@ class SentenceTransformer(nn.Module):
             h = self._gemm(a, c[p + "intermediate.dense.weight"], c[p + "intermediate.dense.bias"], act=1)
             y = self._gemm(h, c[p + "output.dense.weight"], c[p + "output.dense.bias"], resid=a)
             x = self._ln(y, c[p + "output.LayerNorm.weight"], c[p + "output.LayerNorm.bias"])
-        out = torch.empty((n, D), dtype=torch.float32, device=x.device)   # mean over a sentence's tokens, then L2: Pooling + Normalize
-        _lib.check(lib.hirest_pool_l2norm_varlen(x.data_ptr(), seq_off.data_ptr(), out.data_ptr(), n, D, ops.stream_ptr()),
+        return x
+
+    def _passes(self, rows: Sequence[Sequence[int]], max_tokens_per_pass: int = 1 << 18, pipeline_tokens: int = 12288):
+        """Cut ragged token-id rows into passes and upload each: yields (s, e, ids, pos_ids, seq_off, max_len) with the three int32
+        device tensors of rows s .. e.  The caller runs inside ``torch.cuda.device(self.device)``."""
+        # Host side of a pass (flatten the ragged rows, positions, offsets) in numpy, packed into ONE pinned int32 buffer and uploaded
+        # asynchronously, and the batch cut into passes of ~pipeline_tokens so that the host prepares pass k + 1 while the GPU runs
+        # pass k (as one pass, 45 k tokens cost 3 ms of Python list work with the GPU idle: 18 % of the call).  Rows are independent
+        # and every kernel is batch-invariant, so the cut does not change a bit of the result.
+        dev = self.device
+        maxpos, vocab = self.config["max_position_embeddings"] - self.pos_offset, self.config["vocab_size"]
+        lens_all = np.fromiter(map(len, rows), dtype=np.int64, count=len(rows))
+        bad = np.nonzero((lens_all < 1) | (lens_all > maxpos))[0]
+        if bad.size:
+            raise ValueError(f"sentence {int(bad[0])}: {int(lens_all[bad[0]])} tokens (1 .. {maxpos})")
+        per_pass = min(int(max_tokens_per_pass), max(int(pipeline_tokens), maxpos))
+        s = 0
+        while s < len(rows):
+            cum = np.cumsum(lens_all[s:])
+            e = s + max(1, int(np.searchsorted(cum, per_pass, side="right")))
+            lens = lens_all[s:e]
+            tokens, n = int(cum[e - s - 1]), e - s
+            host = torch.empty((2 * tokens + n + 1,), dtype=torch.int32).pin_memory()     # ids | positions | offsets
+            buf = host.numpy()
+            buf[:tokens] = np.fromiter(itertools.chain.from_iterable(rows[s:e]), dtype=np.int64, count=tokens)
+            if int(buf[:tokens].min()) < 0 or int(buf[:tokens].max()) >= vocab:
+                raise ValueError("token id outside the vocabulary")
+            off = buf[2 * tokens:]
+            off[0] = 0
+            off[1:] = np.cumsum(lens)
+            buf[tokens:2 * tokens] = np.arange(tokens, dtype=np.int64) - np.repeat(off[:-1].astype(np.int64), lens) + self.pos_offset
+            d = host.to(dev, non_blocking=True)
+            yield s, e, d[:tokens], d[tokens:2 * tokens], d[2 * tokens:], int(lens.max())
+            s = e
+
+
+class SentenceTransformer(PackedBertEncoder):
+    def __init__(self, model_name_or_path: Optional[str] = None, device: Optional[Union[str, torch.device]] = None, *,
+                 config: Optional[dict] = None, state_dict: Optional[Dict[str, torch.Tensor]] = None,
+                 vocab: Optional[Sequence[str]] = None, max_seq_length: Optional[int] = None):
+        """Either a local sentence-transformers model directory (``config.json``, ``model.safetensors`` or
+        ``pytorch_model.bin``, ``vocab.txt``, optional ``sentence_bert_config.json``) — the hub name the reference passes cannot
+        be downloaded here, so a name that is not a directory raises — or explicit ``config`` + ``state_dict`` (+ ``vocab``)."""
+        super().__init__()
+        if config is None:
+            if model_name_or_path is None or not os.path.isdir(model_name_or_path):
+                raise FileNotFoundError(f"{model_name_or_path!r} is not a local model directory (no network access: download "
+                                        "sentence-transformers/all-MiniLM-L6-v2 beforehand and pass its path)")
+            with open(os.path.join(model_name_or_path, "config.json")) as f:
+                config = json.load(f)
+            state_dict = _load_weights(model_name_or_path)
+            vocab_file = os.path.join(model_name_or_path, "vocab.txt")
+            if vocab is None and os.path.exists(vocab_file):
+                with open(vocab_file, encoding="utf-8") as f:
+                    vocab = f.readlines()
+            sb = os.path.join(model_name_or_path, "sentence_bert_config.json")
+            if max_seq_length is None and os.path.exists(sb):
+                with open(sb) as f:
+                    max_seq_length = json.load(f).get("max_seq_length")
+        self._init_encoder(config, state_dict)
+        self.max_seq_length = int(max_seq_length or 256)                      # all-MiniLM-L6-v2's sentence_bert_config.json
+        self.max_seq_length = min(self.max_seq_length, int(config["max_position_embeddings"]) - self.pos_offset)
+        self.tokenizer = WordPieceTokenizer(vocab) if vocab is not None else None
+        if device is not None:
+            self.to(device)
+
+    def get_sentence_embedding_dimension(self) -> int:
+        return self.hidden
+
+    def _encode_packed(self, ids: torch.Tensor, pos_ids: torch.Tensor, seq_off: torch.Tensor, n: int, max_len: int) -> torch.Tensor:
+        """the packed sentences' token states -> [n, hidden] unit rows"""
+        x = self._token_states(ids, pos_ids, seq_off, n, max_len)
+        out = torch.empty((n, self.hidden), dtype=torch.float32, device=x.device)   # mean over a sentence's tokens, then L2: Pooling + Normalize
+        _lib.check(_lib.load().hirest_pool_l2norm_varlen(x.data_ptr(), seq_off.data_ptr(), out.data_ptr(), n, self.hidden, ops.stream_ptr()),
                    "hirest_pool_l2norm_varlen")
         return out
 
@@ -199,38 +265,12 @@ class SentenceTransformer(nn.Module):
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("hirest_amd.SentenceTransformer runs on MI355X only (no CPU fallback); move the model to a GPU")
-        maxpos, vocab = self.config["max_position_embeddings"], self.config["vocab_size"]
         out = torch.empty((len(rows), self.hidden), dtype=torch.float32, device=dev)
         if not len(rows):
             return out
-        # Host side of a pass (flatten the ragged rows, positions, offsets) in numpy, packed into ONE pinned int32 buffer and uploaded
-        # asynchronously, and the batch cut into passes of ~pipeline_tokens so that the host prepares pass k + 1 while the GPU runs
-        # pass k (as one pass, 45 k tokens cost 3 ms of Python list work with the GPU idle: 18 % of the call).  Rows are independent
-        # and every kernel is batch-invariant, so the cut does not change a bit of the result.
-        lens_all = np.fromiter(map(len, rows), dtype=np.int64, count=len(rows))
-        bad = np.nonzero((lens_all < 1) | (lens_all > maxpos))[0]
-        if bad.size:
-            raise ValueError(f"sentence {int(bad[0])}: {int(lens_all[bad[0]])} tokens (1 .. {maxpos})")
-        per_pass = min(int(max_tokens_per_pass), max(int(pipeline_tokens), maxpos))
         with torch.cuda.device(dev):
-            s = 0
-            while s < len(rows):
-                cum = np.cumsum(lens_all[s:])
-                e = s + max(1, int(np.searchsorted(cum, per_pass, side="right")))
-                lens = lens_all[s:e]
-                tokens, n = int(cum[e - s - 1]), e - s
-                host = torch.empty((2 * tokens + n + 1,), dtype=torch.int32).pin_memory()     # ids | positions | offsets
-                buf = host.numpy()
-                buf[:tokens] = np.fromiter(itertools.chain.from_iterable(rows[s:e]), dtype=np.int64, count=tokens)
-                if int(buf[:tokens].min()) < 0 or int(buf[:tokens].max()) >= vocab:
-                    raise ValueError("token id outside the vocabulary")
-                off = buf[2 * tokens:]
-                off[0] = 0
-                off[1:] = np.cumsum(lens)
-                buf[tokens:2 * tokens] = np.arange(tokens, dtype=np.int64) - np.repeat(off[:-1].astype(np.int64), lens)
-                d = host.to(dev, non_blocking=True)
-                out[s:e] = self._encode_packed(d[:tokens], d[tokens:2 * tokens], d[2 * tokens:], n, int(lens.max()))
-                s = e
+            for s, e, ids, pos_ids, seq_off, max_len in self._passes(rows, max_tokens_per_pass, pipeline_tokens):
+                out[s:e] = self._encode_packed(ids, pos_ids, seq_off, e - s, max_len)
         return out
 
     def tokenize(self, sentences: Sequence[str]) -> List[List[int]]:

@@ -355,6 +355,27 @@ def bert_state_dict(c: dict, seed: int) -> Dict[str, torch.Tensor]:
     return joint_state_dict(bert_shapes(c), seed)
 
 
+# BERTScore's encoder (bert_score.score(lang='en') = roberta-large cut after layer 17, evaluate.py:294-297) in the Hugging Face
+# RobertaModel checkpoint schema: BERT's layers, one token-type row, positions offset by pad_token_id + 1.  ROBERTA_WIDE has
+# roberta-large's widths with few layers; ROBERTA_LARGE only shapes tools/bertscore_bench.py.
+ROBERTA_TINY = {"model_type": "roberta", "vocab_size": 700, "hidden_size": 64, "num_hidden_layers": 4, "num_attention_heads": 4,
+                "intermediate_size": 128, "max_position_embeddings": 68, "type_vocab_size": 1, "layer_norm_eps": 1e-5,
+                "pad_token_id": 1, "bos_token_id": 0, "eos_token_id": 2}
+ROBERTA_WIDE = {"model_type": "roberta", "vocab_size": 1000, "hidden_size": 1024, "num_hidden_layers": 3, "num_attention_heads": 16,
+                "intermediate_size": 4096, "max_position_embeddings": 514, "type_vocab_size": 1, "layer_norm_eps": 1e-5,
+                "pad_token_id": 1, "bos_token_id": 0, "eos_token_id": 2}
+ROBERTA_LARGE = dict(ROBERTA_WIDE, num_hidden_layers=24)
+
+
+def roberta_state_dict(c: dict, seed: int, num_layers: int = None) -> Dict[str, torch.Tensor]:
+    """Seeded weights under a roberta checkpoint's names (``roberta.`` prefix, no pooler); ``num_layers``: only the first so many
+    layers (the values of a tensor depend on its name and the seed alone, so a cut dict equals the full one's first layers)."""
+    if num_layers is not None:
+        c = dict(c, num_hidden_layers=num_layers)
+    return {"roberta." + k: v for k, v in joint_state_dict({k: s for k, s in bert_shapes(c).items() if not k.startswith("pooler.")},
+                                                           seed).items()}
+
+
 def sentence_ids(name: str, n: int, seed: int, vocab_size: int, min_len: int = 2, max_len: int = 40,
                  cls_id: int = 101, sep_id: int = 102) -> list:
     """n ragged rows [CLS] w.. [SEP] with lengths spread over [min_len, max_len] (min_len 2 = an empty subtitle)"""

@@ -284,6 +284,23 @@ int hirest_topk_f32_ws(const float* scores, const int32_t* tie_rank, int32_t Q, 
 int hirest_clip_score(const void* img_rows, int32_t img_dtype, int32_t U, const void* txt_rows, int32_t txt_dtype,
                       const int32_t* sel, int32_t C, int32_t K, int32_t E, float* out, void* stream);
 
+/* BERTScore's greedy matching (bert_score.score with idf=False, as evaluate.py:294-297 calls it) of n_pairs sentence pairs in one
+ * launch.  states: packed [tokens, D] fp32 token states of n_seq unique sentences, row stride ld floats (ld >= D, ld % 4 == 0, base
+ * 16-byte aligned); sentence s holds rows seq_off[s] .. seq_off[s+1] (seq_off: n_seq + 1 device ints).  tok_weight: one float per
+ * row (idf=False: 1, and 0 for a sentence's first and last token).  Pair p compares sentence cand_seq[p] with ref_seq[p]; repeats
+ * and cand == ref are allowed.  Every row is divided by its L2 norm, sim[i][j] = <c_i, r_j> runs on v_mfma_f32_32x32x2_f32 (exact
+ * fp32) and is never written to memory; wp[i] = max_j sim[i][j], wr[j] = max_i sim[i][j] over the pair's real tokens only;
+ *   out[3p + 0] = P = sum_i w_i wp[i] / sum_i w_i,  out[3p + 1] = R likewise over the reference,  out[3p + 2] = F = 2PR / (P + R).
+ * A weight sum of 0 gives P (or R) = 0, and a NaN F becomes 0.  The weighted sums are added in token order without atomics: a
+ * pair's three numbers depend on its own rows only, not on n_pairs, its place in the batch or the launch shape.
+ * A sentence id outside [0, n_seq) gives three NaNs for that pair and reads nothing; so does a sentence with no rows or with more
+ * than HIREST_BERTSCORE_MAX_TOKENS rows.  HIREST_E_BADARG for a NULL pointer, D < 4, D % 4, ld < D, ld % 4, n_seq < 1 or
+ * n_pairs < 0, before anything is enqueued; n_pairs == 0 does nothing. */
+#define HIREST_BERTSCORE_MAX_TOKENS 1024
+int hirest_bertscore_greedy(const float* states, int64_t ld, int32_t D, const int32_t* seq_off, int32_t n_seq,
+                            const float* tok_weight, const int32_t* cand_seq, const int32_t* ref_seq, int32_t n_pairs,
+                            float* out /* [n_pairs, 3] = P, R, F */, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Whole-tower runners: one call = one forward of a transformer tower over a batch, all
  * kernels enqueued on `stream`.  Weights are referenced, never copied.
