@@ -23,7 +23,8 @@ import torch
 from torch import nn
 
 from . import _lib, ops
-from .eva_clip import TextTower, _Leaf, _Tower, _linear, _norm, image_transform
+from .eva_clip import (OPENAI_DATASET_MEAN, OPENAI_DATASET_STD, _NO_FOLD, _RESBLOCK, TextTower, _Leaf, _Tower, _linear, _norm,
+                       _precision_scope, image_transform)
 from .tokenizer import tokenize  # noqa: F401  (clip.tokenize)
 
 __all__ = ["available_models", "load", "tokenize", "build_model", "CLIP"]
@@ -37,6 +38,15 @@ def available_models() -> List[str]:
 class OpenAIVisionTower(_Tower):
     """model.py:216-273, parameter names identical (conv1, class_embedding, positional_embedding, ln_pre,
     transformer.resblocks.N.*, ln_post, proj)."""
+    _what = "CLIP vision tower"
+    _FIELDS = (("patch_w", "patch", "conv1.weight"), ("patch_b", None, None),                     # conv1 has no bias (model.py:220)
+               ("cls", "f32", "class_embedding"), ("pos", "f32", "positional_embedding"),
+               ("norm_g", "f32", "ln_post.weight"), ("norm_b", "f32", "ln_post.bias"), ("head_w", "wT", "proj"), ("head_b", None, None),
+               ("image_mean", "const", "image_mean"), ("image_std", "const", "image_std"),
+               ("ln_pre_g", "f32", "ln_pre.weight"), ("ln_pre_b", "f32", "ln_pre.bias"))
+    _TABLES = {"bf16": (_lib.VisionTower, _FIELDS, _lib.BlockWeights, _RESBLOCK + _NO_FOLD),
+               "fp32": (_lib.VisionTowerF32, _FIELDS, _lib.BlockWeightsF32, _RESBLOCK)}
+    image_mean, image_std = OPENAI_DATASET_MEAN, OPENAI_DATASET_STD
 
     def __init__(self, input_resolution: int, patch_size: int, width: int, layers: int, heads: int, output_dim: int):
         super().__init__()
@@ -69,105 +79,39 @@ class OpenAIVisionTower(_Tower):
         self.proj = nn.Parameter(torch.zeros(D, output_dim))
         self.max_frames_per_call = 2048
 
-    def _prepare(self, device):
-        if self._prepared is not None and self._prepared["device"] == device:
-            return self._prepared
-        if device.type != "cuda":
-            raise RuntimeError("hirest_amd: the CLIP vision tower runs on MI355X only (no CPU fallback)")
+    def _blocks(self):
+        return self.transformer.resblocks
+
+    def _scalars(self):
         D, P = self.width, self.patch_size
-        K = 3 * P * P
-        kpad = (K + 63) // 64 * 64
-        keep = []
-
-        def hold(t):
-            keep.append(t)
-            return t.data_ptr()
-        pw = torch.zeros((D, kpad), dtype=torch.float32, device=device)
-        pw[:, :K] = self.conv1.weight.detach().float().reshape(D, K)
-        blocks = (_lib.BlockWeights * self.layers)()
-        for i, b in enumerate(self.transformer.resblocks):
-            blocks[i] = _lib.BlockWeights(
-                hold(self._f32(b.ln_1.weight)), hold(self._f32(b.ln_1.bias)),
-                hold(self._bf16(b.attn.in_proj_weight)), hold(self._f32(b.attn.in_proj_bias)),
-                hold(self._bf16(b.attn.out_proj.weight)), hold(self._f32(b.attn.out_proj.bias)),
-                hold(self._f32(b.ln_2.weight)), hold(self._f32(b.ln_2.bias)),
-                hold(self._bf16(b.mlp.c_fc.weight)), hold(self._f32(b.mlp.c_fc.bias)),
-                hold(self._bf16(b.mlp.c_proj.weight)), hold(self._f32(b.mlp.c_proj.bias)))
-        mean = torch.tensor((0.48145466, 0.4578275, 0.40821073), dtype=torch.float32, device=device)
-        std = torch.tensor((0.26862954, 0.26130258, 0.27577711), dtype=torch.float32, device=device)
-        desc = _lib.VisionTower(
-            self.input_resolution, P, D, self.heads, D // self.heads, 4 * D, self.layers, self.output_dim, kpad,
-            1, 1e-5,                                                  # QuickGELU (model.py:175), nn.LayerNorm default eps
-            hold(ops.to_bf16(pw)), None,                              # conv1 has no bias (model.py:220)
-            hold(self._f32(self.class_embedding)), hold(self._f32(self.positional_embedding)),
-            blocks, hold(self._f32(self.ln_post.weight)), hold(self._f32(self.ln_post.bias)),
-            hold(self._bf16(self.proj.detach().float().t().contiguous())), None, hold(mean), hold(std),
-            hold(self._f32(self.ln_pre.weight)), hold(self._f32(self.ln_pre.bias)), 1)
-        self._prepared = {"device": device, "desc": desc, "blocks": blocks, "keep": keep}
-        return self._prepared
-
-    def _prepare_f32(self, device):
-        """The fp32 master parameters as they are (contiguous fp32 views; the zero-padded conv weight and proj^T are copies)."""
-        if self._prepared is not None and self._prepared["device"] == device and self._prepared.get("f32"):
-            return self._prepared
-        if device.type != "cuda":
-            raise RuntimeError("hirest_amd: the CLIP vision tower runs on MI355X only (no CPU fallback)")
-        D, P = self.width, self.patch_size
-        K = 3 * P * P
-        kpad = (K + 63) // 64 * 64
-        keep = []
-
-        def hold(t):
-            t = t.detach().float().contiguous()
-            keep.append(t)
-            return t.data_ptr()
-        pw = torch.zeros((D, kpad), dtype=torch.float32, device=device)
-        pw[:, :K] = self.conv1.weight.detach().float().reshape(D, K)
-        blocks = (_lib.BlockWeightsF32 * self.layers)()
-        for i, b in enumerate(self.transformer.resblocks):
-            blocks[i] = _lib.BlockWeightsF32(
-                hold(b.ln_1.weight), hold(b.ln_1.bias), hold(b.attn.in_proj_weight), hold(b.attn.in_proj_bias),
-                hold(b.attn.out_proj.weight), hold(b.attn.out_proj.bias), hold(b.ln_2.weight), hold(b.ln_2.bias),
-                hold(b.mlp.c_fc.weight), hold(b.mlp.c_fc.bias), hold(b.mlp.c_proj.weight), hold(b.mlp.c_proj.bias))
-        mean = torch.tensor((0.48145466, 0.4578275, 0.40821073), dtype=torch.float32, device=device)
-        std = torch.tensor((0.26862954, 0.26130258, 0.27577711), dtype=torch.float32, device=device)
-        desc = _lib.VisionTowerF32(
-            self.input_resolution, P, D, self.heads, D // self.heads, 4 * D, self.layers, self.output_dim, kpad,
-            1, 1e-5,                                                  # QuickGELU (model.py:175), nn.LayerNorm default eps
-            hold(pw), None,                                           # conv1 has no bias (model.py:220)
-            hold(self.class_embedding), hold(self.positional_embedding), blocks, hold(self.ln_post.weight), hold(self.ln_post.bias),
-            hold(self.proj.detach().float().t()), None, hold(mean), hold(std),
-            hold(self.ln_pre.weight), hold(self.ln_pre.bias), 1)       # ln_pre; ln_post + proj on every token (model.py:229-273)
-        self._prepared = {"device": device, "desc": desc, "blocks": blocks, "keep": keep, "f32": True}
-        return self._prepared
+        return dict(image_size=self.input_resolution, patch=P, width=D, heads=self.heads, head_dim=D // self.heads, mlp_dim=4 * D,
+                    layers=self.layers, embed_dim=self.output_dim, kpad=(3 * P * P + 63) // 64 * 64,
+                    act=1, ln_eps=1e-5,       # QuickGELU (model.py:175), nn.LayerNorm default eps
+                    out_all_tokens=1)         # ln_pre; ln_post + proj on every token (model.py:229-273)
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.dtype not in (torch.float32, torch.bfloat16, torch.uint8):
             x = x.float()
         f32 = self.precision != "bf16"
-        if self._prepared is not None and bool(self._prepared.get("f32")) != f32:
-            self._prepared = None                      # the other kernel set's descriptor
-        prep = self._prepare_f32(x.device) if f32 else self._prepare(x.device)
+        desc = C.byref(self._prepared_for("fp32" if f32 else "bf16", x.device)["desc"])
         lib = _lib.load()
         x = x.contiguous()
         B, T, E = x.shape[0], self.num_tokens, self.output_dim
         out = torch.empty((B, T, E), dtype=torch.float32, device=x.device)
-        step = max(1, int(self.max_frames_per_call))
         if B == 0:
             return out[:, 0, :] if self.pip_head else out[:, 1:, :]
-        wsb = lib.hirest_vision_workspace_bytes_f32 if f32 else lib.hirest_vision_workspace_bytes
-        ws = self._ws(wsb(C.byref(prep["desc"]), min(B, step)), x.device)
-        for s in range(0, B, step):
-            n = min(step, B - s)
+        code = ops._IN_DTYPES[x.dtype]
+
+        def call(s, n, ws):
             if f32:
-                _lib.check(lib.hirest_vision_forward_f32(C.byref(prep["desc"]), x[s:s + n].data_ptr(), ops._IN_DTYPES[x.dtype], n,
-                                                         out[s:s + n].data_ptr(), ws.data_ptr(), ws.numel(), ops.stream_ptr()),
-                           "hirest_vision_forward_f32")
-                continue
-            _lib.check(lib.hirest_vision_forward(C.byref(prep["desc"]), x[s:s + n].data_ptr(), ops._IN_DTYPES[x.dtype], n,
-                                                 out[s:s + n].data_ptr(), ws.data_ptr(), ws.numel(), 0, ops.stream_ptr()),
-                       "hirest_vision_forward")
+                _lib.check(lib.hirest_vision_forward_f32(desc, x[s:s + n].data_ptr(), code, n, out[s:s + n].data_ptr(), ws.data_ptr(),
+                                                         ws.numel(), ops.stream_ptr()), "hirest_vision_forward_f32")
+            else:
+                _lib.check(lib.hirest_vision_forward(desc, x[s:s + n].data_ptr(), code, n, out[s:s + n].data_ptr(), ws.data_ptr(),
+                                                     ws.numel(), 0, ops.stream_ptr()), "hirest_vision_forward")
+        wsb = lib.hirest_vision_workspace_bytes_f32 if f32 else lib.hirest_vision_workspace_bytes
+        self._run_calls(B, self.max_frames_per_call, False, lambda n: wsb(desc, n), call, x.device)
         if self.pip_head:
             # the pip `clip` package's head (openai/CLIP @ a9b1bf5, model.py VisionTransformer.forward: ln_post(x[:, 0, :]) @ proj):
             # LayerNorm and projection act per token, so it is row 0 of what the kernel computed for every token
@@ -218,6 +162,15 @@ class CLIP(nn.Module):
         self.visual.precision = p
         self._text.precision = p
         return self
+
+    def precision_scope(self, visual: str = None, text: str = None):
+        """``with model.precision_scope(visual='fp32'):`` runs the block with the named towers at another precision and puts back what
+        they had, also when the block raises.  Names as in ``set_precision``: 'bf16x3' runs the fp32 kernels."""
+        for precision in (visual, text):
+            if precision not in (None, "bf16", "fp32", "bf16x3"):
+                raise ValueError(f"precision must be one of ('bf16', 'fp32', 'bf16x3'), got {precision!r}")
+        to = {None: None, "bf16": "bf16", "fp32": "fp32", "bf16x3": "fp32"}
+        return _precision_scope(((self.visual, to[visual]), (self._text, to[text])))
 
     @property
     def dtype(self):

@@ -24,7 +24,9 @@ import ctypes as C
 import json
 import math
 import os
+from contextlib import contextmanager
 from copy import deepcopy
+from operator import attrgetter
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -79,14 +81,68 @@ def _norm(d):
     return _Leaf(weight=(d,), bias=(d,))
 
 
+def _struct(struct, /, **fields):
+    """A ctypes struct filled by keyword.  Every field has to be named (None: a NULL pointer) and no other name: ctypes itself
+    would leave a forgotten field zero and accept a misspelt one."""
+    names = [n for n, _ in struct._fields_]
+    if sorted(fields) != sorted(names):
+        raise TypeError(f"{struct.__name__}: fields {sorted(set(fields) ^ set(names))} missing or unknown")
+    return struct(**fields)
+
+
+@contextmanager
+def _precision_scope(towers):
+    """``towers``: (tower, precision or None = leave it) pairs.  Sets them, and restores what they had on the way out."""
+    old = [t.precision for t, _ in towers]
+    try:
+        for t, p in towers:
+            if p is not None:
+                t.precision = p
+        yield
+    finally:
+        for (t, _), p in zip(towers, old):
+            t.precision = p
+
+
+def _fold_rows(lin, weight, norm):
+    """Rows of BlockWeights.<lin>_wf / _bf / _s: LayerNorm ``norm`` folded into the Linear ``weight`` whose bias is field <lin>_b."""
+    return tuple((f"{lin}_{out}", f"fold{i}", (weight, f"{lin}_b", norm)) for i, out in enumerate(("wf", "bf", "s")))
+
+
+_NO_FOLD = tuple((f, None, None) for f in ("qkv_wf", "qkv_bf", "qkv_s", "fc1_wf", "fc1_bf", "fc1_s"))
+# the residual attention block of the CLIP text transformer and of OpenAI's ViT (eva_model.py:177-250, model.py:166-189)
+_RESBLOCK = (("ln1_g", "f32", "ln_1.weight"), ("ln1_b", "f32", "ln_1.bias"),
+             ("qkv_w", "w", "attn.in_proj_weight"), ("qkv_b", "f32", "attn.in_proj_bias"),
+             ("proj_w", "w", "attn.out_proj.weight"), ("proj_b", "f32", "attn.out_proj.bias"),
+             ("ln2_g", "f32", "ln_2.weight"), ("ln2_b", "f32", "ln_2.bias"),
+             ("fc1_w", "w", "mlp.c_fc.weight"), ("fc1_b", "f32", "mlp.c_fc.bias"),
+             ("fc2_w", "w", "mlp.c_proj.weight"), ("fc2_b", "f32", "mlp.c_proj.bias"))
+
+
 class _Tower(nn.Module):
     """Shared machinery: lazily mirrors the fp32 master parameters into kernel-ready device
     buffers (bf16 GEMM weights, fused biases, ctypes descriptor structs) and re-does so whenever
-    the parameters are moved / cast / reloaded."""
+    the parameters are moved / cast / reloaded.
+
+    A tower class states what feeds its structs as data.  ``_TABLES[kind]`` = (descriptor struct, its rows, block struct, its rows)
+    for kind 'bf16' | 'fp32' | 'x3'; a row is (struct field, form, source), the source a dotted parameter path below the tower
+    (descriptor rows) or below one block (block rows).  Forms:
+      'f32'       the parameter as a contiguous fp32 view
+      'w'         a weight matrix: the fp32 view, or its bf16 copy in the 'bf16' kind; 'wT': of the transposed matrix
+      'patch'     the patch-embedding weight as [width, kpad] rows, zero-padded to a multiple of 64 columns, cast like 'w'
+      'qkv_bias'  q_bias | zeros | v_bias of the module at the path (EVA's attention has no k bias, vit_model.py:115-119)
+      'const'     fp32 values of the tower attribute named (image mean / std)
+      'split'     bf16 hi | lo halves of the fp32 matrix (ops.split2)
+      'fold0..2'  hirest_fold_layernorm's W gamma (bf16), b + W beta, row sums of the bf16 W gamma; NULL when the tower does not fold
+      None        a NULL pointer
+    The integers and flags of a descriptor come from ``_scalars()``."""
+    _TABLES: Dict[str, tuple] = {}
+    _what = "tower"
+    fold_layernorm = False
 
     def __init__(self):
         super().__init__()
-        self._prepared = None
+        self._prepared = None     # None, or {kind: preparation}: all on one device, one kind never evicts another
         self._workspace = None
         # 'bf16': GEMMs / attention on the bf16 MFMA kernels (fp32 accumulation, residual stream, statistics): the measured hot
         # path.  'fp32': every product in exact fp32 (csrc/tower_f32.hip): the reference's own precision (eva_clip.py:90), ~16x
@@ -114,13 +170,111 @@ class _Tower(nn.Module):
     def _f32(p: torch.Tensor) -> torch.Tensor:
         return p.detach().float().contiguous()
 
+    def _prepared_for(self, kind: str, device) -> dict:
+        """The descriptor of one kernel set ('bf16' | 'fp32' | 'x3': the fp32 one plus split weights), built on first use."""
+        cache = self._prepared
+        if cache is None or any(p["device"] != device for p in cache.values()):
+            cache = self._prepared = {}
+        if kind not in cache:
+            if device.type != "cuda":
+                raise RuntimeError(f"hirest_amd: the {self._what} runs on MI355X only (no CPU fallback); move the model to a GPU")
+            desc_cls, rows, block_cls, block_rows = self._TABLES[kind]
+            keep = []   # device tensors referenced by raw pointers below
+            blocks = (block_cls * self.layers)()
+            for i, b in enumerate(self._blocks()):
+                blocks[i] = _struct(block_cls, **self._pointers(b, block_rows, kind, device, keep))
+            if kind == "x3":
+                base = self._prepared_for("fp32", device)
+                keep.append(base)
+                scalars = {"base": C.pointer(base["desc"])}
+            else:
+                scalars = self._scalars()
+            desc = _struct(desc_cls, blocks=blocks, **scalars, **self._pointers(self, rows, kind, device, keep))
+            cache[kind] = {"device": device, "desc": desc, "blocks": blocks, "keep": keep}
+        return cache[kind]
+
+    def _pointers(self, owner, rows, kind, device, keep) -> dict:
+        """{struct field: device pointer or None} of one table's rows, read below ``owner``; the tensors are appended to ``keep``."""
+        cast = ops.to_bf16 if kind == "bf16" else (lambda t: t)
+        fold = self.fold_layernorm and not self.quick_gelu
+        done, folded = {}, {}
+        for field, form, src in rows:
+            if form is None or (form.startswith("fold") and not fold):
+                t = None
+            elif form == "const":
+                t = torch.tensor(getattr(self, src), dtype=torch.float32, device=device)
+            elif form.startswith("fold"):
+                if src not in folded:
+                    weight, bias, norm = src
+                    folded[src] = self._fold(self._f32(attrgetter(weight)(owner)), done[bias], attrgetter(norm)(owner), device)
+                t = folded[src][int(form[4:])]
+            else:
+                p = attrgetter(src)(owner)
+                if form == "qkv_bias":
+                    t = torch.cat([p.q_bias.detach().float(), torch.zeros(self.width, device=device), p.v_bias.detach().float()])
+                elif form == "patch":
+                    K = p[0].numel()
+                    t = torch.zeros((self.width, self._scalars()["kpad"]), dtype=torch.float32, device=device)
+                    t[:, :K] = p.detach().float().reshape(self.width, K)
+                    t = cast(t)
+                else:
+                    t = self._f32(p.detach().float().t() if form == "wT" else p)
+                    t = ops.split2(t) if form == "split" else t if form == "f32" else cast(t)
+            done[field] = t
+        keep.extend(t for t in done.values() if t is not None)
+        return {f: None if t is None else t.data_ptr() for f, t in done.items()}
+
+    def _fold(self, w32, bias, norm, device):
+        """LayerNorm folded into the Linear that follows it (include/hirest_hip.h, HIREST_EPI_LNFOLD_*):
+        LN(x) W^T + b = rstd (x W'^T - mean s) + b',  W' = W gamma (bf16), s = row sums of the bf16 W', b' = b + W beta:
+        one kernel per Linear (hirest_fold_layernorm), once per checkpoint."""
+        N, K = w32.shape
+        wf = torch.empty((N, K), dtype=torch.bfloat16, device=device)
+        bf = torch.empty((N,), dtype=torch.float32, device=device)
+        cs = torch.empty((N,), dtype=torch.float32, device=device)
+        _lib.check(_lib.load().hirest_fold_layernorm(w32.data_ptr(), self._f32(norm.weight).data_ptr(), self._f32(norm.bias).data_ptr(),
+                                                     bias.data_ptr(), wf.data_ptr(), bf.data_ptr(), cs.data_ptr(), N, K,
+                                                     ops.stream_ptr()), "hirest_fold_layernorm")
+        return wf, bf, cs
+
     @staticmethod
-    def _bf16(p: torch.Tensor) -> torch.Tensor:
-        return ops.to_bf16(p.detach().float().contiguous())
+    def _call_size(B: int, limit, near_equal: bool) -> int:
+        """Rows per tower call for a batch of B >= 1.  ``near_equal``: the fewest calls of at most ``limit`` rows, all of nearly the
+        same size (1030 rows at limit 1024 run as 515 + 515); otherwise full calls and a remainder (1024 + 6)."""
+        limit = max(1, int(limit))
+        return -(-B // -(-B // limit)) if near_equal else min(B, limit)
+
+    def _run_calls(self, B: int, limit, near_equal: bool, ws_bytes, call, device):
+        """Run ``call(start, rows, workspace)`` over a batch of B rows in micro-batches (``_call_size``), all in one workspace that
+        ``ws_bytes(rows)`` sizes for the largest of them.  Returns the (start, rows) of the calls."""
+        if B <= 0:
+            return []
+        step = self._call_size(B, limit, near_equal)
+        ws = self._ws(ws_bytes(step), device)
+        spans = [(s, min(step, B - s)) for s in range(0, B, step)]
+        for s, n in spans:
+            call(s, n, ws)
+        return spans
 
 
 class VisionTower(_Tower):
     """EVA ViT (reference VisionTransformer, vit_model.py:248-351), parameter names identical."""
+    _what = "vision tower"
+    _FIELDS = (("patch_w", "patch", "patch_embed.proj.weight"), ("patch_b", "f32", "patch_embed.proj.bias"),
+               ("cls", "f32", "cls_token"), ("pos", "f32", "pos_embed"), ("norm_g", "f32", "norm.weight"), ("norm_b", "f32", "norm.bias"),
+               ("head_w", "w", "head.weight"), ("head_b", "f32", "head.bias"),
+               ("image_mean", "const", "image_mean"), ("image_std", "const", "image_std"), ("ln_pre_g", None, None), ("ln_pre_b", None, None))
+    _BLOCK = (("ln1_g", "f32", "norm1.weight"), ("ln1_b", "f32", "norm1.bias"),
+              ("qkv_w", "w", "attn.qkv.weight"), ("qkv_b", "qkv_bias", "attn"),
+              ("proj_w", "w", "attn.proj.weight"), ("proj_b", "f32", "attn.proj.bias"),
+              ("ln2_g", "f32", "norm2.weight"), ("ln2_b", "f32", "norm2.bias"),
+              ("fc1_w", "w", "mlp.fc1.weight"), ("fc1_b", "f32", "mlp.fc1.bias"),
+              ("fc2_w", "w", "mlp.fc2.weight"), ("fc2_b", "f32", "mlp.fc2.bias"))
+    _TABLES = {"bf16": (_lib.VisionTower, _FIELDS, _lib.BlockWeights,
+                        _BLOCK + _fold_rows("qkv", "attn.qkv.weight", "norm1") + _fold_rows("fc1", "mlp.fc1.weight", "norm2")),
+               "fp32": (_lib.VisionTowerF32, _FIELDS, _lib.BlockWeightsF32, _BLOCK),
+               # bf16x3: the fp32 descriptor plus, per block, the four linear weights split into bf16 hi | lo halves
+               "x3": (_lib.VisionTowerX3, (), _lib.BlockWeightsX3, tuple((f + "2", "split", src) for f, form, src in _BLOCK if form == "w"))}
 
     def __init__(self, image_size, patch_size, width, layers, heads, mlp_ratio, embed_dim, quick_gelu=False):
         super().__init__()
@@ -160,143 +314,31 @@ class VisionTower(_Tower):
         # array: a fifth less epilogue traffic on proj / fc2.  True (or HIREST_F32_RESIDUAL=1) keeps the fp32 array of rounds 1-3.
         self.f32_residual = os.environ.get("HIREST_F32_RESIDUAL", "0") == "1"
 
-    def _prepare(self, device):
-        if self._prepared is not None and self._prepared["device"] == device and not self._prepared.get("f32"):
-            return self._prepared
-        if device.type != "cuda":
-            raise RuntimeError("hirest_amd: the vision tower runs on MI355X only (no CPU fallback); move the model to a GPU")
-        D, P = self.width, self.patch_size
-        K = 3 * P * P
-        kpad = (K + 63) // 64 * 64
-        keep = []   # device tensors referenced by raw pointers below
+    def _blocks(self):
+        return self.blocks
 
-        def hold(t):
-            keep.append(t)
-            return t.data_ptr()
-        pw = torch.zeros((D, kpad), dtype=torch.float32, device=device)
-        pw[:, :K] = self.patch_embed.proj.weight.detach().float().reshape(D, K)
-        blocks = (_lib.BlockWeights * self.layers)()
+    def _scalars(self):
+        P = self.patch_size
+        return dict(image_size=self.image_size, patch=P, width=self.width, heads=self.heads, head_dim=self.width // self.heads,
+                    mlp_dim=self.mlp_dim, layers=self.layers, embed_dim=self.embed_dim, kpad=(3 * P * P + 63) // 64 * 64,
+                    act=1 if self.quick_gelu else 0, ln_eps=1e-6,   # norm_layer=partial(nn.LayerNorm, eps=1e-6), eva_model.py:304
+                    out_all_tokens=0)
 
-        def fold(weight, bias, norm):
-            """LayerNorm folded into the Linear that follows it (include/hirest_hip.h, HIREST_EPI_LNFOLD_*):
-            LN(x) W^T + b = rstd (x W'^T - mean s) + b',  W' = W gamma (bf16), s = row sums of the bf16 W', b' = b + W beta:
-            one kernel per Linear (hirest_fold_layernorm), once per checkpoint."""
-            w32 = self._f32(weight)
-            N, K = w32.shape
-            wf = torch.empty((N, K), dtype=torch.bfloat16, device=device)
-            bf = torch.empty((N,), dtype=torch.float32, device=device)
-            cs = torch.empty((N,), dtype=torch.float32, device=device)
-            _lib.check(_lib.load().hirest_fold_layernorm(w32.data_ptr(), self._f32(norm.weight).data_ptr(), self._f32(norm.bias).data_ptr(),
-                                                         self._f32(bias).data_ptr(), wf.data_ptr(), bf.data_ptr(), cs.data_ptr(), N, K,
-                                                         ops.stream_ptr()), "hirest_fold_layernorm")
-            return hold(wf), hold(bf), hold(cs)
-        for i, b in enumerate(self.blocks):
-            qkv_b = torch.cat([b.attn.q_bias.detach().float(), torch.zeros(D, device=device), b.attn.v_bias.detach().float()])
-            folded = (None,) * 6
-            if self.fold_layernorm and not self.quick_gelu:
-                folded = fold(b.attn.qkv.weight, qkv_b, b.norm1) + fold(b.mlp.fc1.weight, b.mlp.fc1.bias.detach().float(), b.norm2)
-            blocks[i] = _lib.BlockWeights(
-                hold(self._f32(b.norm1.weight)), hold(self._f32(b.norm1.bias)),
-                hold(self._bf16(b.attn.qkv.weight)), hold(qkv_b.contiguous()),
-                hold(self._bf16(b.attn.proj.weight)), hold(self._f32(b.attn.proj.bias)),
-                hold(self._f32(b.norm2.weight)), hold(self._f32(b.norm2.bias)),
-                hold(self._bf16(b.mlp.fc1.weight)), hold(self._f32(b.mlp.fc1.bias)),
-                hold(self._bf16(b.mlp.fc2.weight)), hold(self._f32(b.mlp.fc2.bias)), *folded)
-        mean = torch.tensor(self.image_mean, dtype=torch.float32, device=device)
-        std = torch.tensor(self.image_std, dtype=torch.float32, device=device)
-        desc = _lib.VisionTower(
-            self.image_size, P, D, self.heads, D // self.heads, self.mlp_dim, self.layers, self.embed_dim, kpad,
-            1 if self.quick_gelu else 0, 1e-6,   # norm_layer=partial(nn.LayerNorm, eps=1e-6), eva_model.py:304
-            hold(ops.to_bf16(pw)), hold(self._f32(self.patch_embed.proj.bias)),
-            hold(self._f32(self.cls_token).reshape(-1)), hold(self._f32(self.pos_embed).reshape(self.num_tokens, D)),
-            blocks, hold(self._f32(self.norm.weight)), hold(self._f32(self.norm.bias)),
-            hold(self._bf16(self.head.weight)), hold(self._f32(self.head.bias)), hold(mean), hold(std), None, None, 0)
-        self._prepared = {"device": device, "desc": desc, "blocks": blocks, "keep": keep}
-        return self._prepared
+    # precision -> preparation kind, workspace_bytes and forward of the C ABI, the attribute with the per-call limit, near-equal calls
+    _EXACT = {"fp32": ("fp32", "hirest_vision_workspace_bytes_f32", "hirest_vision_forward_f32", "max_frames_per_call_f32", False),
+              "bf16x3": ("x3", "hirest_vision_workspace_bytes_x3", "hirest_vision_forward_x3", "max_frames_per_call_x3", True)}
 
-    def _prepare_f32(self, device):
-        """fp32 master parameters as they are (contiguous fp32 views, no copies except the zero-padded patch weight)."""
-        if self._prepared is not None and self._prepared["device"] == device and self._prepared.get("f32"):
-            return self._prepared
-        if device.type != "cuda":
-            raise RuntimeError("hirest_amd: the vision tower runs on MI355X only (no CPU fallback); move the model to a GPU")
-        D, P = self.width, self.patch_size
-        K = 3 * P * P
-        kpad = (K + 63) // 64 * 64
-        keep = []
-
-        def hold(t):
-            t = t.detach().float().contiguous()
-            keep.append(t)
-            return t.data_ptr()
-        pw = torch.zeros((D, kpad), dtype=torch.float32, device=device)
-        pw[:, :K] = self.patch_embed.proj.weight.detach().float().reshape(D, K)
-        blocks = (_lib.BlockWeightsF32 * self.layers)()
-        for i, b in enumerate(self.blocks):
-            qkv_b = torch.cat([b.attn.q_bias.detach().float(), torch.zeros(D, device=device), b.attn.v_bias.detach().float()])
-            blocks[i] = _lib.BlockWeightsF32(
-                hold(b.norm1.weight), hold(b.norm1.bias), hold(b.attn.qkv.weight), hold(qkv_b),
-                hold(b.attn.proj.weight), hold(b.attn.proj.bias), hold(b.norm2.weight), hold(b.norm2.bias),
-                hold(b.mlp.fc1.weight), hold(b.mlp.fc1.bias), hold(b.mlp.fc2.weight), hold(b.mlp.fc2.bias))
-        mean = torch.tensor(self.image_mean, dtype=torch.float32, device=device)
-        std = torch.tensor(self.image_std, dtype=torch.float32, device=device)
-        desc = _lib.VisionTowerF32(
-            self.image_size, P, D, self.heads, D // self.heads, self.mlp_dim, self.layers, self.embed_dim, kpad,
-            1 if self.quick_gelu else 0, 1e-6, hold(pw), hold(self.patch_embed.proj.bias), hold(self.cls_token.reshape(-1)),
-            hold(self.pos_embed.reshape(self.num_tokens, D)), blocks, hold(self.norm.weight), hold(self.norm.bias),
-            hold(self.head.weight), hold(self.head.bias), hold(mean), hold(std), None, None, 0)
-        self._prepared = {"device": device, "desc": desc, "blocks": blocks, "keep": keep, "f32": True}
-        return self._prepared
-
-    def _prepare_x3(self, device):
-        """bf16x3: the fp32 descriptor plus, per block, the four linear weights split into bf16 hi | lo halves (ops.split2), once."""
-        prep = self._prepare_f32(device)
-        if "x3" in prep:
-            return prep
-        blocks = (_lib.BlockWeightsX3 * self.layers)()
-        keep = prep["keep"]
-
-        def split(w):
-            t = ops.split2(w.detach().float().contiguous())
-            keep.append(t)
-            return t.data_ptr()
-        for i, b in enumerate(self.blocks):
-            blocks[i] = _lib.BlockWeightsX3(split(b.attn.qkv.weight), split(b.attn.proj.weight), split(b.mlp.fc1.weight), split(b.mlp.fc2.weight))
-        prep["x3_blocks"] = blocks
-        prep["x3"] = _lib.VisionTowerX3(C.pointer(prep["desc"]), blocks)
-        return prep
-
-    def _forward_x3(self, image: torch.Tensor) -> torch.Tensor:
-        prep = self._prepare_x3(image.device)
+    def _forward_exact(self, image: torch.Tensor) -> torch.Tensor:
+        kind, ws_bytes, fwd, limit, near_equal = self._EXACT[self.precision]
+        desc = C.byref(self._prepared_for(kind, image.device)["desc"])
         lib = _lib.load()
-        B = image.shape[0]
-        out = torch.empty((B, self.embed_dim), dtype=torch.float32, device=image.device)
-        if B == 0:
-            return out
-        calls = -(-B // max(1, int(self.max_frames_per_call_x3)))
-        step = -(-B // calls)
-        ws = self._ws(lib.hirest_vision_workspace_bytes_x3(C.byref(prep["x3"]), step), image.device)
+        out = torch.empty((image.shape[0], self.embed_dim), dtype=torch.float32, device=image.device)
         code = ops._IN_DTYPES[image.dtype]
-        for s in range(0, B, step):
-            n = min(step, B - s)
-            _lib.check(lib.hirest_vision_forward_x3(C.byref(prep["x3"]), image[s:s + n].data_ptr(), code, n, out[s:s + n].data_ptr(),
-                                                    ws.data_ptr(), ws.numel(), ops.stream_ptr()), "hirest_vision_forward_x3")
-        return out
 
-    def _forward_f32(self, image: torch.Tensor) -> torch.Tensor:
-        prep = self._prepare_f32(image.device)
-        lib = _lib.load()
-        B = image.shape[0]
-        out = torch.empty((B, self.embed_dim), dtype=torch.float32, device=image.device)
-        if B == 0:
-            return out
-        step = min(B, max(1, int(self.max_frames_per_call_f32)))
-        ws = self._ws(lib.hirest_vision_workspace_bytes_f32(C.byref(prep["desc"]), step), image.device)
-        code = ops._IN_DTYPES[image.dtype]
-        for s in range(0, B, step):
-            n = min(step, B - s)
-            _lib.check(lib.hirest_vision_forward_f32(C.byref(prep["desc"]), image[s:s + n].data_ptr(), code, n, out[s:s + n].data_ptr(),
-                                                     ws.data_ptr(), ws.numel(), ops.stream_ptr()), "hirest_vision_forward_f32")
+        def call(s, n, ws):
+            _lib.check(getattr(lib, fwd)(desc, image[s:s + n].data_ptr(), code, n, out[s:s + n].data_ptr(), ws.data_ptr(), ws.numel(),
+                                         ops.stream_ptr()), fwd)
+        self._run_calls(image.shape[0], getattr(self, limit), near_equal, lambda n: getattr(lib, ws_bytes)(desc, n), call, image.device)
         return out
 
     @torch.no_grad()
@@ -313,11 +355,9 @@ class VisionTower(_Tower):
         assert H == self.image_size and W == self.image_size, \
             f"Input image size ({H}*{W}) doesn't match model ({self.image_size}*{self.image_size})."  # vit_model.py:203
         image = image.contiguous()
-        if self.precision == "fp32":
-            return self._forward_f32(image)
-        if self.precision == "bf16x3":
-            return self._forward_x3(image)
-        prep = self._prepare(image.device)
+        if self.precision in self._EXACT:
+            return self._forward_exact(image)
+        desc = C.byref(self._prepared_for("bf16", image.device)["desc"])
         lib = _lib.load()
         B = image.shape[0]
         out = torch.empty((B, self.embed_dim), dtype=torch.float32, device=image.device)
@@ -326,46 +366,47 @@ class VisionTower(_Tower):
         # Near-equal micro-batches instead of full ones + a remainder: with max_frames_per_call = 1024, 1030 frames run as
         # 515 + 515, not 1024 + 6, so a small tail never drops below the 64-frame boundary where the tower switches
         # kernels (folded LayerNorm / persistent attention) — every frame of a >= 64-frame call takes the same path.
-        calls = -(-B // max(1, int(self.max_frames_per_call)))
-        step = -(-B // calls)
-        nbytes = lib.hirest_vision_workspace_bytes(C.byref(prep["desc"]), step)
-        ws = self._ws(nbytes, image.device)
+        step = self._call_size(B, self.max_frames_per_call, True)
         code = ops._IN_DTYPES[image.dtype]
         self.last_fold_ratio = 0.0
         flags = (0 if self.prune_last_block else _lib.TOWER_NO_PRUNE) | (_lib.TOWER_F32_RESIDUAL if self.f32_residual else 0)
-        goff = lib.hirest_vision_guard_offset(C.byref(prep["desc"]), step) if self.fold_guard_ratio is not None else _NO_GUARD
-        starts = list(range(0, B, step))
+        goff = lib.hirest_vision_guard_offset(desc, step) if self.fold_guard_ratio is not None else _NO_GUARD
         # Guard of the folded LayerNorm (include/hirest_hip.h): every call reports the largest |mean| / sigma any token row had
         # in any layer, as one float in its workspace.  The workspace is reused by the next micro-batch, so the float is copied
         # (device -> device, same stream) into a per-call slot and ALL slots are read with one 4 * calls-byte copy after the
         # last micro-batch has been enqueued: the host never waits for the GPU between micro-batches.
-        guards = torch.zeros(len(starts), dtype=torch.float32, device=image.device) if goff != _NO_GUARD else None
+        guards = torch.zeros(-(-B // step), dtype=torch.float32, device=image.device) if goff != _NO_GUARD else None
 
-        def call(s, extra=0):
-            n = min(step, B - s)
-            _lib.check(lib.hirest_vision_forward(C.byref(prep["desc"]), image[s:s + n].data_ptr(), code, n, out[s:s + n].data_ptr(),
+        def call(s, n, ws, extra=0):
+            _lib.check(lib.hirest_vision_forward(desc, image[s:s + n].data_ptr(), code, n, out[s:s + n].data_ptr(),
                                                  ws.data_ptr(), ws.numel(), flags | extra, ops.stream_ptr()), "hirest_vision_forward")
-            return n
-        for i, s in enumerate(starts):
-            n = call(s)
+
+        def guarded(s, n, ws):
+            call(s, n, ws)
             if guards is not None:
-                g = lib.hirest_vision_guard_offset(C.byref(prep["desc"]), n)
+                g = lib.hirest_vision_guard_offset(desc, n)
                 if g != _NO_GUARD:
-                    guards[i:i + 1].copy_(ws[g:g + 4].view(torch.float32))
+                    guards[s // step:s // step + 1].copy_(ws[g:g + 4].view(torch.float32))
+        spans = self._run_calls(B, self.max_frames_per_call, True, lambda n: lib.hirest_vision_workspace_bytes(desc, n), guarded, image.device)
         if guards is not None:
             ratios = guards.cpu().tolist()
             self.last_fold_ratio = max(ratios)
-            for s, ratio in zip(starts, ratios):
+            for (s, n), ratio in zip(spans, ratios):
                 # Row offsets of more than `fold_guard_ratio` sigma would lose precision in the un-normalised bf16 operand: such
                 # a micro-batch is repeated with the LayerNorm passes (non-finite rows report +inf, elementwise.hip).
                 if not ratio <= self.fold_guard_ratio:
                     self.fold_fallbacks += 1
-                    call(s, _lib.TOWER_NO_LNFOLD)
+                    call(s, n, self._workspace, _lib.TOWER_NO_LNFOLD)
         return out
 
 
 class TextTower(_Tower):
     """CLIP text transformer (reference TextTransformer, eva_model.py:177-250)."""
+    _what = "text tower"
+    _FIELDS = (("tok_emb", "f32", "token_embedding.weight"), ("pos", "f32", "positional_embedding"),
+               ("lnf_g", "f32", "ln_final.weight"), ("lnf_b", "f32", "ln_final.bias"), ("proj_w", "wT", "text_projection"))
+    _TABLES = {"bf16": (_lib.TextTower, _FIELDS, _lib.BlockWeights, _RESBLOCK + _NO_FOLD),
+               "fp32": (_lib.TextTowerF32, _FIELDS, _lib.BlockWeightsF32, _RESBLOCK)}
 
     def __init__(self, vocab_size, width, layers, heads, context_length, embed_dim, quick_gelu=False):
         super().__init__()
@@ -390,57 +431,12 @@ class TextTower(_Tower):
         self.logit_scale = nn.Parameter(torch.ones([]) * math.log(1 / 0.07))
         self.max_rows_per_call = 1024
 
-    def _prepare_f32(self, device):
-        if self._prepared is not None and self._prepared["device"] == device and self._prepared.get("f32"):
-            return self._prepared
-        if device.type != "cuda":
-            raise RuntimeError("hirest_amd: the text tower runs on MI355X only (no CPU fallback); move the model to a GPU")
-        keep = []
+    def _blocks(self):
+        return self.transformer.resblocks
 
-        def hold(t):
-            t = t.detach().float().contiguous()
-            keep.append(t)
-            return t.data_ptr()
-        blocks = (_lib.BlockWeightsF32 * self.layers)()
-        for i, b in enumerate(self.transformer.resblocks):
-            blocks[i] = _lib.BlockWeightsF32(
-                hold(b.ln_1.weight), hold(b.ln_1.bias), hold(b.attn.in_proj_weight), hold(b.attn.in_proj_bias),
-                hold(b.attn.out_proj.weight), hold(b.attn.out_proj.bias), hold(b.ln_2.weight), hold(b.ln_2.bias),
-                hold(b.mlp.c_fc.weight), hold(b.mlp.c_fc.bias), hold(b.mlp.c_proj.weight), hold(b.mlp.c_proj.bias))
-        desc = _lib.TextTowerF32(
-            self.context_length, self.vocab_size, self.width, self.heads, self.layers, self.embed_dim,
-            1 if self.quick_gelu else 0, 1e-5, hold(self.token_embedding.weight), hold(self.positional_embedding), blocks,
-            hold(self.ln_final.weight), hold(self.ln_final.bias), hold(self.text_projection.detach().float().t()))
-        self._prepared = {"device": device, "desc": desc, "blocks": blocks, "keep": keep, "f32": True}
-        return self._prepared
-
-    def _prepare(self, device):
-        if self._prepared is not None and self._prepared["device"] == device and not self._prepared.get("f32"):
-            return self._prepared
-        if device.type != "cuda":
-            raise RuntimeError("hirest_amd: the text tower runs on MI355X only (no CPU fallback); move the model to a GPU")
-        keep = []
-
-        def hold(t):
-            keep.append(t)
-            return t.data_ptr()
-        blocks = (_lib.BlockWeights * self.layers)()
-        for i, b in enumerate(self.transformer.resblocks):
-            blocks[i] = _lib.BlockWeights(
-                hold(self._f32(b.ln_1.weight)), hold(self._f32(b.ln_1.bias)),
-                hold(self._bf16(b.attn.in_proj_weight)), hold(self._f32(b.attn.in_proj_bias)),
-                hold(self._bf16(b.attn.out_proj.weight)), hold(self._f32(b.attn.out_proj.bias)),
-                hold(self._f32(b.ln_2.weight)), hold(self._f32(b.ln_2.bias)),
-                hold(self._bf16(b.mlp.c_fc.weight)), hold(self._f32(b.mlp.c_fc.bias)),
-                hold(self._bf16(b.mlp.c_proj.weight)), hold(self._f32(b.mlp.c_proj.bias)))
-        desc = _lib.TextTower(
-            self.context_length, self.vocab_size, self.width, self.heads, self.layers, self.embed_dim,
-            1 if self.quick_gelu else 0, 1e-5,   # LayerNorm default eps (eva_model.py:19-25)
-            hold(self._f32(self.token_embedding.weight)), hold(self._f32(self.positional_embedding)), blocks,
-            hold(self._f32(self.ln_final.weight)), hold(self._f32(self.ln_final.bias)),
-            hold(self._bf16(self.text_projection.detach().float().t().contiguous())))
-        self._prepared = {"device": device, "desc": desc, "blocks": blocks, "keep": keep}
-        return self._prepared
+    def _scalars(self):
+        return dict(context=self.context_length, vocab=self.vocab_size, width=self.width, heads=self.heads, layers=self.layers,
+                    embed_dim=self.embed_dim, act=1 if self.quick_gelu else 0, ln_eps=1e-5)   # LayerNorm default eps (eva_model.py:19-25)
 
     @torch.no_grad()
     @ops.on_tensor_device
@@ -449,19 +445,17 @@ class TextTower(_Tower):
         if text.dim() != 2 or text.shape[1] != self.context_length:
             raise RuntimeError(f"encode_text expects [B,{self.context_length}] token ids, got {tuple(text.shape)}")
         f32 = self.precision == "fp32"
-        prep = self._prepare_f32(text.device) if f32 else self._prepare(text.device)
+        desc = C.byref(self._prepared_for("fp32" if f32 else "bf16", text.device)["desc"])
         lib = _lib.load()
         text = text.to(torch.int64).contiguous()
-        B = text.shape[0]
-        out = torch.empty((B, self.embed_dim), dtype=torch.float32, device=text.device)
-        step = max(1, int(self.max_rows_per_call))
+        out = torch.empty((text.shape[0], self.embed_dim), dtype=torch.float32, device=text.device)
         ws_bytes, fwd = (lib.hirest_text_workspace_bytes_f32, lib.hirest_text_forward_f32) if f32 else \
             (lib.hirest_text_workspace_bytes, lib.hirest_text_forward)
-        ws = self._ws(ws_bytes(C.byref(prep["desc"]), min(B, step)), text.device)
-        for s in range(0, B, step):
-            n = min(step, B - s)
-            _lib.check(fwd(C.byref(prep["desc"]), text[s:s + n].data_ptr(), n, out[s:s + n].data_ptr(), ws.data_ptr(), ws.numel(),
-                           ops.stream_ptr()), "hirest_text_forward_f32" if f32 else "hirest_text_forward")
+
+        def call(s, n, ws):
+            _lib.check(fwd(desc, text[s:s + n].data_ptr(), n, out[s:s + n].data_ptr(), ws.data_ptr(), ws.numel(), ops.stream_ptr()),
+                       "hirest_text_forward_f32" if f32 else "hirest_text_forward")
+        self._run_calls(text.shape[0], self.max_rows_per_call, False, lambda n: ws_bytes(desc, n), call, text.device)
         return out
 
 
@@ -488,6 +482,14 @@ class EVA_CLIP(nn.Module):
         self.visual.precision = precision
         self.text.precision = "fp32" if precision == "bf16x3" else precision
         return self
+
+    def precision_scope(self, visual: Optional[str] = None, text: Optional[str] = None):
+        """``with model.precision_scope(visual='bf16x3'):`` runs the block with the named towers at another precision and puts back what
+        they had, also when the block raises.  Names as in ``set_precision``; 'bf16x3' is the text tower's 'fp32', as there."""
+        for precision in (visual, text):
+            if precision is not None and precision not in TOWER_PRECISIONS:
+                raise ValueError(f"precision must be one of {TOWER_PRECISIONS}, got {precision!r}")
+        return _precision_scope(((self.visual, visual), (self.text, "fp32" if text == "bf16x3" else text)))
 
     @torch.no_grad()
     def init_random_(self, seed: int = 0):

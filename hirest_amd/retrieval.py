@@ -395,9 +395,12 @@ def rerank_exact(model, source, text_rows: torch.Tensor, video_rows: torch.Tenso
     """Second pass of ``run_corpus(rank_exact_k=k)``: ``video_rows`` [V, E] from the fast tower, ``text_rows`` [Q, E] from the exact
     text tower -> (rows with every rank-ambiguous video re-encoded at ``exact_precision``, report).
 
-    ``eps`` (bound of |fast score - exact score|): measured here when None — ``sample`` videos spread over the corpus are encoded at
-    both precisions, eps = ``safety`` x the largest score difference over all queries x sampled videos.  The sampled videos are part
-    of the re-encoded set, so measuring costs nothing extra.  Identical on every rank (all inputs are replicated)."""
+    ``eps`` stands for a bound of |fast score - exact score|.  When None it is measured here: ``sample`` videos spread over the corpus
+    are encoded at both precisions, eps = ``safety`` x the largest score difference over all queries x sampled videos.  That makes the
+    guarantee empirical: the top-k lists equal the exact towers' as long as no video outside the sample errs by more than eps, which
+    ``sample`` videos make likely and do not prove (the report's ``eps_measured_on`` says how many there were); pass a proven ``eps``
+    where one is known.  The sampled videos are part of the re-encoded set, so measuring costs nothing extra.  Identical on every rank
+    (all inputs are replicated)."""
     device = torch.device(device) if device is not None else video_rows.device
     V, Q = video_rows.shape[0], text_rows.shape[0]
     names = list(source.video_ids)
@@ -405,11 +408,9 @@ def rerank_exact(model, source, text_rows: torch.Tensor, video_rows: torch.Tenso
     if V == 0 or Q == 0 or k <= 0:
         report.update({"reencoded": 0, "reencoded_fraction": 0.0, "eps": float(eps or 0.0)})
         return video_rows, report
-    fast_precision = model.visual.precision
     out = video_rows.clone()
     done = np.zeros((0,), dtype=np.int64)
-    try:
-        model.visual.precision = exact_precision
+    with model.precision_scope(visual=exact_precision):
         if eps is None:
             sample_ids = np.unique(np.linspace(0, V - 1, min(sample, V)).astype(np.int64))
             exact_s = _rows_of(model, source, sample_ids.tolist(), n_model_frames, device, group, gather)
@@ -437,8 +438,6 @@ def rerank_exact(model, source, text_rows: torch.Tensor, video_rows: torch.Tenso
             out.index_copy_(0, torch.from_numpy(todo).to(device), rows)
         n_re = int(np.union1d(amb, done).size)
         report.update({"eps": float(eps), "ambiguous": int(amb.size), "reencoded": n_re, "reencoded_fraction": n_re / V, "window": int(W)})
-    finally:
-        model.visual.precision = fast_precision
     return out, report
 
 
@@ -475,12 +474,8 @@ def run_corpus(model, source, prompts: Sequence[str], n_model_frames: Optional[i
     # rank_exact_k = k: the top-k lists of the PRECISE towers at close to the fast tower's speed — the text tower runs exact (2 % of the work),
     # the corpus fast, and only the videos whose place in some query's top k is within twice the measured score error are encoded again
     # precisely (rerank_exact).  Every rank computes the same set and re-encodes its share of it; one more all-gather merges the rows.
-    text_precision = model.text.precision
-    try:
-        model.text.precision = "fp32"
+    with model.precision_scope(text="fp32"):
         text_rows = encode_prompts(model, prompts, device, tokenizer=tokenizer)
-    finally:
-        model.text.precision = text_precision
     if world > 1:
         video_rows = video_rows.clone()                    # (the gather buffer is reused by the second pass)
     rows, report = rerank_exact(model, source, text_rows, video_rows, rank_exact_k, n_model_frames, group, device,
