@@ -225,9 +225,10 @@ def graph_beam_search(s: BeamSearch, enc_kv_all, return_ids):
     return s.readout(return_ids)
 
 
-def decoder_last_logprob(model, ids: torch.Tensor, enc_kv: List[torch.Tensor], row_add: torch.Tensor) -> torch.Tensor:
-    """DecoderModel.forward on the whole prefix (no KV cache, like the reference), then log_softmax of the LAST
-    position + row_add (train.py:547-566, beam.py:76).  ids [R,t] int64, enc_kv[i] [R,20,1536] -> [R, vocab]."""
+def decoder_hidden(model, ids: torch.Tensor, enc_kv: List[torch.Tensor]) -> torch.Tensor:
+    """DecoderModel.forward on whole sequences (no KV cache, like the reference; module_decoder.py:380-406 with the causal penalty
+    alone, i.e. no padded key in front of a position that matters): ids [R, t] int64, enc_kv[i] [R, F, 1536] -> the last layer's
+    hidden states [R * t, 768], every position."""
     c, lib = model._w(), _lib.load()
     Dp = "clip4cap_model.decoder."
     lin = lambda a, k, **kw: model._gemm(a, c[k + ".weight"], c[k + ".bias"], **kw)
@@ -253,9 +254,25 @@ def decoder_last_logprob(model, ids: torch.Tensor, enc_kv: List[torch.Tensor], r
                                                 R, t, kv.shape[1], H, Dm // H, scale, -10000.0, 0.0, ops.stream_ptr()), "cross attention")
         d = ln(lin(ctx, p + "enc_attn.output.dense", resid=s1), p + "enc_attn.output")
         x = ln(lin(lin(d, p + "intermediate.dense", act=1), p + "output.dense", resid=d), p + "output")
-    last = x.reshape(R, t, Dm)[:, -1, :].contiguous()                     # dec_output[:, -1, :] (train.py:562)
-    cp = Dp + "classifier.cls.predictions."
-    hh = ln(lin(last, cp + "transform.dense", act=1), cp + "transform")
+    return x
+
+
+def lm_head_transform(model, rows: torch.Tensor) -> torch.Tensor:
+    """BertPredictionHeadTransform (dense, GELU, LayerNorm) in front of the LM head: [n, 768] -> [n, 768]."""
+    c = model._w()
+    cp = "clip4cap_model.decoder.classifier.cls.predictions.transform."
+    t = model._gemm(rows, c[cp + "dense.weight"], c[cp + "dense.bias"], act=1)
+    return model._ln(t, c[cp + "LayerNorm.weight"], c[cp + "LayerNorm.bias"], 1e-12)
+
+
+def decoder_last_logprob(model, ids: torch.Tensor, enc_kv: List[torch.Tensor], row_add: torch.Tensor) -> torch.Tensor:
+    """DecoderModel.forward on the whole prefix (no KV cache, like the reference), then log_softmax of the LAST
+    position + row_add (train.py:547-566, beam.py:76).  ids [R,t] int64, enc_kv[i] [R,20,1536] -> [R, vocab]."""
+    c, lib = model._w(), _lib.load()
+    R, t = ids.shape
+    x = decoder_hidden(model, ids, enc_kv)
+    last = x.reshape(R, t, x.shape[1])[:, -1, :].contiguous()             # dec_output[:, -1, :] (train.py:562)
+    hh = lm_head_transform(model, last)
     logits = model._gemm(hh, c["lm_w"], c["lm_b"])
     V = logits.shape[1]
     out = torch.empty_like(logits)

@@ -441,6 +441,97 @@ class MomentModel(nn.Module):
             else:
                 raise NotImplementedError
 
+    # ------------------------------------------------------------------ validation pass (run.py:546-571)
+    @torch.no_grad()
+    def valid_step(self, batch, **gen_kwargs):
+        """What ``Trainer.predict(has_target=True)`` takes from a batch (run.py:548-571: ``train_step`` under ``eval()`` and ``no_grad``, then
+        ``test_step``), from ONE forward: ``{'loss': 0-dim fp32 device tensor, 'prediction': ...}`` plus whatever else ``test_step`` returns.
+        The loss is the reference's training loss with dropout off, whatever ``self.training`` says; the prediction is ``test_step``'s,
+        bit for bit.  The text feature, the fusion and the encoder run once, on the inference path (``set_precision`` applies).
+
+        moment_retrieval: both results from the same head logits in one launch (hirest_moment_valid_f32).  step_captioning: one encoder
+        pass and one cross-attention K / V projection feed a teacher-forced decoder pass over the target prefix — only the rows with a
+        target go through the LM head, whose logits are never stored (hirest_lm_head_ce_f32) — and the beam search (``search=False``:
+        the loss alone; hirest_amd.predict then captions several batches with one search).
+        moment_segmentation: the teacher-forced loss reads ``prev_boundary_mask`` inputs the iterative inference never sees, so with
+        targets in the batch it is ``train_step``'s loss beside ``test_step``'s prediction; without them, ``test_step``'s result alone."""
+        from . import train
+        task = batch["tasks"][0]
+        dev = self.clip_g_map.weight.device
+        with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+            if task == "moment_retrieval":
+                return self._valid_moment_retrieval(batch)
+            elif task == "moment_segmentation":
+                res = self.test_moment_segmentation(batch, **gen_kwargs)
+                if "moment_segmentation_target" in batch and "prev_boundary_mask" in batch:
+                    res = {"loss": train.eval_loss(self, batch), **res}
+                return res
+            elif task == "step_captioning":
+                return self._valid_step_captioning(batch, **gen_kwargs)
+            else:
+                raise NotImplementedError
+
+    def _valid_moment_retrieval(self, batch):
+        dev = self._w()["dev"]
+        i32 = lambda t: ops.to_device(t, dev).to(torch.int32).contiguous()
+        vis, vmask, mmask = ops.to_device(batch["vis_feats"], dev).float().contiguous(), i32(batch["vis_mask"]), i32(batch["moment_mask"])
+        asr = ops.to_device(batch["asr_feats"], dev).float().contiguous() if self.use_asr else None
+        B, T = vmask.shape
+        base = self._fusion_base(vis, self._text_feat(batch, dev), asr, vmask)
+        logits = self._heads(self._features(base, mmask, None, B, T), ["start", "end"])              # [2, B * T]
+        pred, loss = ops.moment_valid(logits, vmask, mmask, i32(batch["moment_retrieval_start_target"]).reshape(-1),
+                                      i32(batch["moment_retrieval_end_target"]).reshape(-1))
+        return {"loss": loss, "prediction": pred.cpu().tolist()}
+
+    @staticmethod
+    def _caption_targets(batch):
+        """The teacher-forcing triples of ``batch['target_text']`` (fields 5, 6, 7 of the reference's 9-tuples) as [B, max_words] int64
+        host arrays: decoder input ids, decoder mask, output ids (-1 = ignored)."""
+        row = lambda f: np.asarray(f, dtype=np.int64).reshape(-1)
+        tt = batch["target_text"]
+        return tuple(np.stack([row(t[k]) for t in tt]) for k in (5, 6, 7))
+
+    def _caption_loss(self, enc_kv_all, input_ids, output_ids):
+        """CrossEntropyLoss(ignore_index=-1) of the teacher-forced decoder (modeling.py:516-521) on the K / V rows of the inference
+        encoder.  The prefix is cut to the longest valid length of the batch (a later position cannot reach an earlier one through the
+        causal mask), the rows with a target are gathered, and only those go through the LM-head transform and hirest_lm_head_ce_f32.
+        input_ids / output_ids: [B, L] int64 host arrays.  Without any target the loss is 0, as train_step's is."""
+        c = self._w()
+        dev = c["dev"]
+        b_idx, p_idx = np.nonzero(output_ids >= 0)
+        if b_idx.size == 0:
+            return torch.zeros((), dtype=torch.float32, device=dev)
+        L = int(p_idx.max()) + 1
+        ids = torch.from_numpy(np.ascontiguousarray(input_ids[:, :L])).to(dev)
+        rows = torch.from_numpy(b_idx.astype(np.int64) * L + p_idx).to(dev)
+        target = torch.from_numpy(output_ids[b_idx, p_idx].astype(np.int32)).to(dev)
+        hidden = caption_search.decoder_hidden(self, ids, enc_kv_all).index_select(0, rows)
+        return ops.lm_head_ce(caption_search.lm_head_transform(self, hidden), c["lm_w"], c["lm_b"], target)[1]
+
+    @staticmethod
+    def _causal_mask_is_exact(decoder_mask, output_ids) -> bool:
+        """The reference masks padded keys as well as future keys (module_decoder.py:388-397).  Where every position with a target has
+        no padded key at or before it — the loader's masks: ones, then zeros — the causal penalty alone gives its scores."""
+        L = decoder_mask.shape[1]
+        last = np.where(output_ids >= 0, np.arange(L)[None, :], -1).max(axis=1)                     # last position with a target, -1: none
+        first_pad = np.where(decoder_mask == 0, np.arange(L)[None, :], L).min(axis=1)               # first padded key, L: none
+        return bool((first_pad > last).all())
+
+    def _valid_step_captioning(self, batch, num_beams=5, return_ids=False, search=True, **kwargs):
+        """`search=False`: the loss alone (hirest_amd.predict captions several loader batches with ONE beam search afterwards)."""
+        from . import train
+        dev = self._w()["dev"]
+        input_ids, decoder_mask, output_ids = self._caption_targets(batch)
+        enc_kv_all = self._caption_encoder_kv(*self._caption_inputs(batch, dev))
+        if self._causal_mask_is_exact(decoder_mask, output_ids):
+            loss = self._caption_loss(enc_kv_all, input_ids, output_ids)
+        else:                                   # a padded key in front of a target: the training forward applies the full mask
+            loss = train.eval_loss(self, batch)
+        if not search:
+            return {"loss": loss}
+        res = caption_search.search(self, enc_kv_all, num_beams, self._caption_limits()[1], return_ids, kwargs.get("graph_slot"))
+        return {"loss": loss, **res}
+
     @torch.no_grad()
     def forward_moment_retrieval(self, video_feats, text_feat, video_mask=None, moment_mask=None, asr_feats=None):
         """modeling.py:212-224: returns {'start_logits','end_logits'} [B,T] (fp32, unmasked)."""
@@ -608,16 +699,20 @@ class MomentModel(nn.Module):
         a = self._trim(batch["asr_feats"].to(dev).float(), None, max_frames, idx=rows) if self.use_asr else None
         return v, a, self._text_feat(batch, dev)
 
-    def _caption_trimmed(self, v, a, text, num_beams, return_ids, **kwargs):
-        """test_step_captioning behind trim_feats: v [B, max_frames, D] (a [B, max_frames, Da] or None) already trimmed, text [B, 1024]."""
+    def _caption_encoder_kv(self, v, a, text):
+        """The fusion and the encoder on the trimmed frames, then the cross-attention K / V of every decoder layer ([B, max_frames, 1536]
+        each): loop invariant for the beam search, and shared with the teacher-forced loss by valid_step."""
         c, (B, max_frames) = self._w(), v.shape[:2]
         ones = torch.ones((B, max_frames), dtype=torch.long, device=c["dev"])
         base = self._fusion_base(v, text, a, ones)
         enc = self._features(base, ones.to(torch.int32).contiguous(), None, B, max_frames)          # [B*F, 768]
-        # encoder-side K/V of the cross-attention are loop invariant: once per layer, [B, F, 1536]
-        enc_kv_all = [self._gemm(enc, c[f"dec_kv_w.{i}"], c[f"dec_kv_b.{i}"]).reshape(B, max_frames, -1)
-                      for i in range(len(self.clip4cap_model.decoder.decoder.layer))]
-        return caption_search.search(self, enc_kv_all, num_beams, self._caption_limits()[1], return_ids, kwargs.get("graph_slot"))
+        return [self._gemm(enc, c[f"dec_kv_w.{i}"], c[f"dec_kv_b.{i}"]).reshape(B, max_frames, -1)
+                for i in range(len(self.clip4cap_model.decoder.decoder.layer))]
+
+    def _caption_trimmed(self, v, a, text, num_beams, return_ids, **kwargs):
+        """test_step_captioning behind trim_feats: v [B, max_frames, D] (a [B, max_frames, Da] or None) already trimmed, text [B, 1024]."""
+        return caption_search.search(self, self._caption_encoder_kv(v, a, text), num_beams, self._caption_limits()[1], return_ids,
+                                     kwargs.get("graph_slot"))
 
     @torch.no_grad()
     def caption_batches(self, batches, num_beams=5, streams=1, return_ids=False, graphs=True, merge=True, rows_in_flight=None):

@@ -325,6 +325,54 @@ def bertscore_greedy(states: torch.Tensor, seq_off, tok_weight: torch.Tensor, ca
     return out
 
 
+@on_tensor_device
+def moment_valid(logits: torch.Tensor, vis_mask: torch.Tensor, moment_mask: torch.Tensor, start_target: torch.Tensor,
+                 end_target: torch.Tensor, fill: float = -1e10):
+    """(pred [B, 2] int32, loss 0-dim fp32) of moment retrieval's validation pass (hirest_moment_valid_f32): logits [2, B * T] fp32 (start
+    head, end head), vis_mask / moment_mask [B, T] int32, start_target / end_target [B] int32 — all on the GPU."""
+    lib = _lib.load()
+    if vis_mask.dim() != 2 or moment_mask.shape != vis_mask.shape:
+        raise ValueError(f"moment_valid: masks must be [B, T], got {tuple(vis_mask.shape)} and {tuple(moment_mask.shape)}")
+    B, T = vis_mask.shape
+    if B < 1 or T < 1 or tuple(logits.shape) != (2, B * T) or tuple(start_target.shape) != (B,) or tuple(end_target.shape) != (B,):
+        raise ValueError(f"moment_valid: expected logits [2, {B * T}] and targets [{B}], got {tuple(logits.shape)}, "
+                         f"{tuple(start_target.shape)}, {tuple(end_target.shape)}")
+    pred = torch.empty((B, 2), dtype=torch.int32, device=logits.device)
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    _lib.check(lib.hirest_moment_valid_f32(_dev(logits, torch.float32, "moment_valid.logits"), _dev(vis_mask, torch.int32, "moment_valid.vis_mask"),
+                                           _dev(moment_mask, torch.int32, "moment_valid.moment_mask"),
+                                           _dev(start_target, torch.int32, "moment_valid.start_target"),
+                                           _dev(end_target, torch.int32, "moment_valid.end_target"), B, T, float(fill), pred.data_ptr(),
+                                           loss.data_ptr(), stream_ptr()), "hirest_moment_valid_f32")
+    return pred, loss
+
+
+@on_tensor_device
+def lm_head_ce(h: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, target: torch.Tensor, n_valid: Optional[int] = None):
+    """(nll [R] fp32, loss 0-dim fp32): CrossEntropyLoss(ignore_index=-1) of h @ w.T + bias without a stored logit
+    (hirest_lm_head_ce_f32).  h [R, 768], w [V, 768], bias [V] fp32, target [R] int32 on the GPU; n_valid = the number of rows with
+    target >= 0 (default R: every row counts), known to the caller from its host copy of the targets."""
+    lib = _lib.load()
+    if h.dim() != 2 or w.dim() != 2 or h.shape[0] < 1 or w.shape[0] < 1 or h.shape[1] != w.shape[1]:
+        raise ValueError(f"lm_head_ce: expected h [R, K] and w [V, K], got {tuple(h.shape)} and {tuple(w.shape)}")
+    R, K = h.shape
+    V = w.shape[0]
+    if tuple(bias.shape) != (V,) or tuple(target.shape) != (R,):
+        raise ValueError(f"lm_head_ce: expected bias [{V}] and target [{R}], got {tuple(bias.shape)} and {tuple(target.shape)}")
+    n_valid = R if n_valid is None else int(n_valid)
+    if n_valid < 0 or n_valid > R:
+        raise ValueError(f"lm_head_ce: n_valid must lie in [0, {R}], got {n_valid}")
+    need = lib.hirest_lm_head_ce_workspace_bytes(R, V)
+    ws = torch.empty(need, dtype=torch.uint8, device=h.device)
+    nll = torch.empty((R,), dtype=torch.float32, device=h.device)
+    loss = torch.empty((), dtype=torch.float32, device=h.device)
+    _lib.check(lib.hirest_lm_head_ce_f32(_dev(h, torch.float32, "lm_head_ce.h"), K, _dev(w, torch.float32, "lm_head_ce.w"), K,
+                                         _dev(bias, torch.float32, "lm_head_ce.bias"), _dev(target, torch.int32, "lm_head_ce.target"),
+                                         R, V, K, n_valid, nll.data_ptr(), loss.data_ptr(), ws.data_ptr(), need, stream_ptr()),
+               "hirest_lm_head_ce_f32")
+    return nll, loss
+
+
 def to_device(t: torch.Tensor, device) -> torch.Tensor:
     """t.to(device) that does not stall the host when it need not: a pinned CPU tensor (what DataLoader(pin_memory=True) delivers:
     hirest_dataset.py:614,624) is copied asynchronously on the current stream — the kernels that read it are behind it on the same

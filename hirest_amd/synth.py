@@ -454,6 +454,34 @@ def caption_targets(name, B, max_words, seed):
     return out
 
 
+def valid_batches(case, max_words=48):
+    """The three loader-shaped batches of one TRAIN_CASES case for the validation pass (tests/golden/valid_*.json): the inputs and
+    targets of the training fixtures plus the per-sample lists run.py's predict() collects (``tasks``, ``prompts``, ``video_fnames``,
+    ``video_duration``).  Durations sit just above each video's valid frames (one bin per second), except one segmentation sample
+    whose duration is shorter than its moment — its timestamps raise, which is the short-``bounds`` case of run.py:766-774 — and two
+    captioning samples share a video name."""
+    B, T = TRAIN_CASES[case]
+    vis, asr, text, vis_mask, moment_mask, bounds = joint_inputs(f"train.{case}", B, T, 53)
+    st, et, seg, prev = train_targets(f"train.{case}", B, T, 53, bounds)
+    lens = vis_mask.sum(1).tolist()
+    videos = [f"video_{case}{b}" for b in range(B)]
+    common = {"vis_feats": vis, "vis_mask": vis_mask, "asr_feats": asr, "text_feat": text, "prompts": [f"prompt {case}{b % 2}" for b in range(B)],
+              "video_fnames": videos, "video_duration": [n + 0.25 for n in lens]}
+    retrieval = dict(common, tasks=["moment_retrieval"] * B, moment_mask=moment_mask, moment_retrieval_start_target=st,
+                     moment_retrieval_end_target=et)
+    short = list(common["video_duration"])
+    short[B - 1] = float(int(bounds[B - 1, 0]) + 3)
+    segmentation = dict(common, tasks=["moment_segmentation"] * B, moment_mask=moment_mask, prev_boundary_mask=prev,
+                        moment_segmentation_target=seg, moment_bound_frames=bounds, video_duration=short,
+                        all_bound_frames=[[int(bounds[b, 0]), int(seg[b]), int(bounds[b, 1])] for b in range(B)])
+    cap_mask = torch.zeros(B, T, dtype=torch.long)
+    for b, n in enumerate([7, 20, 37][:B]):
+        cap_mask[b, 5 + b:5 + b + n] = 1
+    captioning = dict(common, tasks=["step_captioning"] * B, moment_mask=cap_mask, target_text=caption_targets(f"train.{case}", B, max_words, 53),
+                      target_text_raw=[f"step {case}{b}" for b in range(B)], video_fnames=[videos[0]] + videos[:B - 1])
+    return {"moment_retrieval": retrieval, "moment_segmentation": segmentation, "step_captioning": captioning}
+
+
 def moment_eval_inputs():
     """Seeded synthetic gt / predictions in evaluate.py's JSON layouts (shared with tests/test_evaluation.py)."""
     cats = ["Food", "Hobbies", "Home"]

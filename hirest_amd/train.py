@@ -1027,7 +1027,9 @@ def _parameters_by_name(model, names: List[str]):
     return out
 
 
-def _train(model, batch, task) -> Dict[str, torch.Tensor]:
+def _train(model, batch, task, dropout=None) -> Dict[str, torch.Tensor]:
+    """`dropout` None: 0.1 in train mode, off in eval mode (the reference's modules); a number: that rate whatever the mode, with a
+    fixed seed — no draw from torch's generator (eval_loss)."""
     dev = model.clip_g_map.weight.device
     if dev.type != "cuda":
         raise RuntimeError("hirest_amd.MomentModel trains on MI355X only (no CPU fallback); move the model to a GPU")
@@ -1035,7 +1037,8 @@ def _train(model, batch, task) -> Dict[str, torch.Tensor]:
         text = model._text_feat(batch, dev)
     inp = {"task": task, "vis": ops.to_device(batch["vis_feats"], dev), "text": text, "vis_mask": ops.to_device(batch["vis_mask"], dev),
            "moment_mask": ops.to_device(batch["moment_mask"], dev),
-           "dropout": 0.1 if model.training else 0.0, "seed": _dropout_seed()}
+           "dropout": (0.1 if model.training else 0.0) if dropout is None else float(dropout),
+           "seed": _dropout_seed() if dropout is None else 0}
     if model.use_asr:
         inp["asr"] = ops.to_device(batch["asr_feats"], dev)
     fn = MomentLoss
@@ -1064,6 +1067,14 @@ def _train(model, batch, task) -> Dict[str, torch.Tensor]:
         fn = CaptionLoss
     names = task_param_names(model, task)
     return {"loss": fn.apply(model, inp, names, *_parameters_by_name(model, names))}
+
+
+def eval_loss(model, batch) -> torch.Tensor:
+    """The loss of ``train_step(batch)`` as the reference computes it under ``model.eval()`` and ``no_grad`` (run.py:548-562): dropout
+    off whatever ``model.training`` says, nothing recorded for a backward.  MomentModel.valid_step uses it where the loss cannot
+    share the inference forward."""
+    with torch.no_grad():
+        return _train(model, batch, batch["tasks"][0], dropout=0.0)["loss"]
 
 
 def train_moment_retrieval(model, batch) -> Dict[str, torch.Tensor]:

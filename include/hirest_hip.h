@@ -774,6 +774,28 @@ int hirest_heads_bwd_f32(const float* dlogits, int64_t rows, int32_t D, int32_t 
 /* out[b] = argmax_t (mask[b,t] ? logits[b,t] : fill), first maximum (modeling.py:294-298) */
 int hirest_masked_argmax(const float* logits, const int32_t* mask, float fill, int32_t B, int32_t T, int32_t* out,
                          void* stream);
+/* The validation pass of moment retrieval (modeling.py:226-310) from the [2, B T] start / end head logits in ONE launch:
+ *   pred[2 b + h] = argmax_t (vis_mask[b,t] ? logits[h][b,t] : fill), first maximum — what hirest_masked_argmax gives per head;
+ *   *loss = (BCE_start + BCE_end) / 2, BCE_h = sum(moment_mask * bce_with_logits(logits[h], onehot(target_h))) / max(sum moment_mask, 1)
+ * over the whole batch (*loss is written, not accumulated).  Per-sample partial sums (double), then one pass in sample order; no
+ * atomics, so repeated calls give the same bits, and a sample's indices do not depend on the other samples.
+ * HIREST_E_BADARG for a NULL pointer, B <= 0, T <= 0 or B > 1024, before anything is enqueued. */
+int hirest_moment_valid_f32(const float* logits, const int32_t* vis_mask, const int32_t* moment_mask, const int32_t* start_target,
+                            const int32_t* end_target, int32_t B, int32_t T, float fill, int32_t* pred /* [B, 2] */, float* loss,
+                            void* stream);
+/* CrossEntropyLoss(ignore_index = -1) of h W^T + bias over V columns without storing a logit (modeling.py:519 behind the LM head).
+ * h [R, K] (row stride ldh), W [V, K] (row stride ldw), bias [V], target [R] (a row with target < 0 gives nll 0 and does not count;
+ * a target >= V is the caller's error: its logit reads as 0).  Exact fp32 products (v_mfma_f32_32x32x2_f32).  Columns whose bias is
+ * a large negative number (the padded rows of a weight cache) vanish in the sum without an inf or a NaN.  Outputs: nll [R] and
+ * *loss = sum(nll) / max(n_valid, 1) added in row order (written, not accumulated).  A block owns 32 rows and one 512-column slice and
+ * writes one (max, sum exp, target logit) partial per (row, slice) into `workspace` (hirest_lm_head_ce_workspace_bytes); a second
+ * kernel merges a row's slices in index order.  nll[r] depends on row r only, not on R.
+ * HIREST_E_BADARG: NULL pointer, R, V, K <= 0, n_valid < 0, ldh / ldw < K or not a multiple of 4 (rows must be 16-byte aligned);
+ * HIREST_E_SHAPE: K != 768; HIREST_E_WORKSPACE: workspace too small.  Nothing is enqueued on an error. */
+size_t hirest_lm_head_ce_workspace_bytes(int32_t R, int32_t V);
+int hirest_lm_head_ce_f32(const float* h, int64_t ldh, const float* W, int64_t ldw, const float* bias, const int32_t* target, int32_t R,
+                          int32_t V, int32_t K, int32_t n_valid, float* nll, float* loss, void* workspace, size_t workspace_bytes,
+                          void* stream);
 /* one iteration of test_moment_segmentation's loop body for all samples, on device (modeling.py:393-433).  A sample whose
  * nsteps[b] has reached max_steps still has its masks updated; nothing is appended to its steps [B, max_steps, 2].
  * 1 <= T <= 16384 (the row's probabilities are staged in 64 KiB of LDS), else HIREST_E_BADARG. */
