@@ -29,7 +29,7 @@ struct AttnCfg {
 
 template <int DH, int DP, int NT>
 __global__ __launch_bounds__(512) void attention_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                       int N, int H, float scale_log2e, int causal) {
+                                                       int N, int H, float scale_log2e, int causal, int nq) {
     using C = AttnCfg<DH, DP, NT>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(512) void attention_kernel(const bf16_t* __restrict
     __syncthreads();
 
     const int g = lane >> 4, c16 = lane & 15;
-    const int nqt = (N + 15) >> 4;
+    const int nqt = (nq + 15) >> 4;   // the leading query tiles only (hirest_attention_bf16_rows); nq <= N
     for (int qt = wave; qt < nqt; qt += 8) {
         const int q = qt * 16 + c16;
         const bool qvalid = q < N;
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(512) void attention_kernel(const bf16_t* __restrict
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[s], acc, 0, 0, 0);
             }
             const int d = dt * 16 + 4 * g;
-            if (qvalid && d < DH) {
+            if (q < nq && d < DH) {                             // (nq <= N) rows from nq on are left alone
                 bf16x4 o;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) o[i] = (bf16_t)(acc[i] * inv);
@@ -146,12 +146,12 @@ __global__ __launch_bounds__(512) void attention_kernel(const bf16_t* __restrict
 }
 
 template <int DH, int DP, int NT>
-int launch(const bf16_t* qkv, bf16_t* out, int B, int N, int H, float scale, int causal, hipStream_t s) {
+int launch(const bf16_t* qkv, bf16_t* out, int B, int N, int H, float scale, int causal, int nq, hipStream_t s) {
     using C = AttnCfg<DH, DP, NT>;
     static HirestDevCfg cfg;
     auto kern = attention_kernel<DH, DP, NT>;
     if (int e = hirest_configure(kern, C::LDS_BYTES, cfg)) return e;
-    hipLaunchKernelGGL(kern, dim3(B * H), dim3(512), C::LDS_BYTES, s, qkv, out, N, H, scale * 1.44269504088896340736f, causal);
+    hipLaunchKernelGGL(kern, dim3(B * H), dim3(512), C::LDS_BYTES, s, qkv, out, N, H, scale * 1.44269504088896340736f, causal, nq);
     return hirest_launch_status();
 }
 
@@ -192,7 +192,7 @@ __device__ __forceinline__ void wait_vm_le(int n) {   // s_waitcnt vmcnt(n) for 
 
 template <int DH, int DP, int NT>
 __global__ __launch_bounds__(512) void attention_kernel_v2(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                          int N, int H, float scale_log2e, int causal) {
+                                                          int N, int H, float scale_log2e, int causal, int nq) {
     using C = AttnCfg2<DH, DP, NT>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(512) void attention_kernel_v2(const bf16_t* __restr
 
     const int g = lane >> 4, c16 = lane & 15;
     const int gk = g ^ ((-(c16 >> 2)) & 3);   // swizzled chunk-in-group for this lane's K rows
-    const int nqt = (N + 15) >> 4;
+    const int nqt = (nq + 15) >> 4;   // the leading query tiles only (hirest_attention_bf16_rows); nq <= N
     bool v_ready = false;
     for (int qt = wave; qt < nqt; qt += 8) {
         const int q = qt * 16 + c16;
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(512) void attention_kernel_v2(const bf16_t* __restr
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[s], acc, 0, 0, 0);
             }
             const int d = dt * 16 + 4 * g;
-            if (qvalid && d < DH) {
+            if (q < nq && d < DH) {                             // (nq <= N) rows from nq on are left alone
                 bf16x4 o;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) o[i] = (bf16_t)(acc[i] * inv);
@@ -705,7 +705,7 @@ __global__ __launch_bounds__((NW + (PROD ? 1 : 0)) * 64) void attention_kernel_v
                 union { bf16x8 v; unsigned u[4]; } w;
                 w.u[0] = s0[0]; w.u[1] = s1[0]; w.u[2] = s0[1]; w.u[3] = s1[1];
                 const int d = (2 * dp + (g & 1)) * 16 + (g >> 1) * 8;
-                if (qvalid && d < DH && !(dbg & 16)) *reinterpret_cast<bf16x8*>(out + ((int64_t)(b0 + h * bstep) * N + q) * D + (h0 + h * hstep) * DH + d) = w.v;
+                if (qvalid && q < nq && d < DH && !(dbg & 16)) *reinterpret_cast<bf16x8*>(out + ((int64_t)(b0 + h * bstep) * N + q) * D + (h0 + h * hstep) * DH + d) = w.v;
             }
         };
         // De-phasing (hirest_attention_set_skew): all waves leave barrier A together and would run S^T (MFMA), softmax (VALU) and P.V
@@ -764,12 +764,12 @@ int launch3(const bf16_t* qkv, bf16_t* out, int B, int N, int H, float scale, in
 
 
 template <int DH, int DP, int NT>
-int launch2(const bf16_t* qkv, bf16_t* out, int B, int N, int H, float scale, int causal, hipStream_t s) {
+int launch2(const bf16_t* qkv, bf16_t* out, int B, int N, int H, float scale, int causal, int nq, hipStream_t s) {
     using C = AttnCfg2<DH, DP, NT>;
     static HirestDevCfg cfg;
     auto kern = attention_kernel_v2<DH, DP, NT>;
     if (int e = hirest_configure(kern, C::LDS_BYTES, cfg)) return e;
-    hipLaunchKernelGGL(kern, dim3(B * H), dim3(512), C::LDS_BYTES, s, qkv, out, N, H, scale * 1.44269504088896340736f, causal);
+    hipLaunchKernelGGL(kern, dim3(B * H), dim3(512), C::LDS_BYTES, s, qkv, out, N, H, scale * 1.44269504088896340736f, causal, nq);
     return hirest_launch_status();
 }
 
@@ -834,20 +834,20 @@ extern "C" int hirest_attention_bf16_rows(const hirest_bf16* qkv, hirest_bf16* o
     }
     if (g_attn_variant >= 2) {
         if (dh == 88) {
-            if (N <= 80) return launch2<88, 96, 5>(q, o, B, N, H, scale, causal, s);
-            if (N <= 272) return launch2<88, 96, 17>(q, o, B, N, H, scale, causal, s);
+            if (N <= 80) return launch2<88, 96, 5>(q, o, B, N, H, scale, causal, nq, s);
+            if (N <= 272) return launch2<88, 96, 17>(q, o, B, N, H, scale, causal, nq, s);
         } else if (dh == 64) {
-            if (N <= 80) return launch2<64, 64, 5>(q, o, B, N, H, scale, causal, s);
-            if (N <= 272) return launch2<64, 64, 17>(q, o, B, N, H, scale, causal, s);
+            if (N <= 80) return launch2<64, 64, 5>(q, o, B, N, H, scale, causal, nq, s);
+            if (N <= 272) return launch2<64, 64, 17>(q, o, B, N, H, scale, causal, nq, s);
         }
         return HIREST_E_SHAPE;
     }
     if (dh == 88) {
-        if (N <= 80) return launch<88, 96, 5>(q, o, B, N, H, scale, causal, s);
-        if (N <= 272) return launch<88, 96, 17>(q, o, B, N, H, scale, causal, s);
+        if (N <= 80) return launch<88, 96, 5>(q, o, B, N, H, scale, causal, nq, s);
+        if (N <= 272) return launch<88, 96, 17>(q, o, B, N, H, scale, causal, nq, s);
     } else if (dh == 64) {
-        if (N <= 80) return launch<64, 64, 5>(q, o, B, N, H, scale, causal, s);
-        if (N <= 272) return launch<64, 64, 17>(q, o, B, N, H, scale, causal, s);
+        if (N <= 80) return launch<64, 64, 5>(q, o, B, N, H, scale, causal, nq, s);
+        if (N <= 272) return launch<64, 64, 17>(q, o, B, N, H, scale, causal, nq, s);
     }
     return HIREST_E_SHAPE;
 }

@@ -1780,6 +1780,7 @@ extern "C" int hirest_gemm_bf16(const hirest_gemm_args* a, void* stream) {
     if (a->flags & ~(HIREST_GEMM_REVERSE | HIREST_GEMM_X3 | HIREST_GEMM_X3_T128)) return HIREST_E_BADARG;
     if ((a->flags & HIREST_GEMM_X3_T128) && !(a->flags & HIREST_GEMM_X3)) return HIREST_E_BADARG;      // (a retired flag, e.g. round 4's K-blocked operands, must not be read as row-major)
     if (a->K % BK != 0 || a->K % T_BK != 0 || a->N % 4 != 0 || a->lda % 8 != 0 || a->ldw % 8 != 0) return HIREST_E_SHAPE;
+    if (a->ldo % 4 != 0) return HIREST_E_SHAPE;              // every epilogue stores 4 or 8 consecutive elements at out + m * ldo + n, n % 4 == 0
     const GemmChoice c = gemm_choose(*a);
     const int word = g_gemm_dbg;
     GemmP p;

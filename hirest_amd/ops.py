@@ -85,7 +85,11 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: to
 
 
 def gemm_select_kernel(which: int):
-    """0 = automatic, 1 = force the 128x128 kernel, 2 = force the 256x256 ping-pong kernel."""
+    """Which bf16 GEMM kernel hirest_gemm_bf16 launches (include/hirest_hip.h: hirest_gemm_select_kernel; tests and A/B timing):
+    0 = automatic (pq256 for M * N >= 2^21 with M >= 512 and N >= 256 and for every LN-fold epilogue, the 128x128 kernel below that),
+    1 = the 128x128 kernel (t128), 2 / 3 = the 256x256 ping-pong kernel with a 4- / 5-slot LDS ring (t256), 4 = t256p (32-deep slabs),
+    5 = t256q (64-deep steps), 6 / 7 = the persistent 256x256 kernel with 8 / 4 waves (p256), 8 = the persistent ping-pong kernel (pp256),
+    9 = pp256 with two phases per 64-deep step (pq256, and pq256x3 for HIREST_GEMM_X3).  Same bits for every selection."""
     _lib.check(_lib.load().hirest_gemm_select_kernel(int(which)), "hirest_gemm_select_kernel")
 
 

@@ -48,7 +48,8 @@ const char* hirest_build_info(void);
  * on MFMA).  W is a torch nn.Linear weight as stored ([out_features, in_features]).
  * Replaces F.linear / nn.Linear / `x @ proj` on the path (vit_model.py:56-62,124-127,148;
  * eva_model.py:137-142,249; nn.MultiheadAttention in/out projections).
- * Requirements: K % 64 == 0, N % 4 == 0, lda/ldw multiples of 8, pointers 16-B aligned.
+ * Requirements: K % 64 == 0, N % 4 == 0, lda/ldw multiples of 8, ldo a multiple of 4 (HIREST_E_SHAPE otherwise),
+ * pointers 16-B aligned.
  * ------------------------------------------------------------------------------------ */
 enum hirest_epilogue {
     HIREST_EPI_BIAS_BF16 = 0,        /* out bf16 [M,ldo]  = acc + bias                        */
@@ -162,9 +163,9 @@ int hirest_layernorm(const float* x, int64_t ldx, const int32_t* row_index,
 int hirest_attention_bf16(const hirest_bf16* qkv, hirest_bf16* out,
                           int32_t B, int32_t N, int32_t H, int32_t dh,
                           float scale, int32_t causal, void* stream);
-/* The same, but only the output rows of queries [0, q_rows) of every sequence are guaranteed to be written (the
- * persistent kernel computes the leading ceil(q_rows / 16) query tiles and still streams all keys / values; the other
- * kernels compute everything).  Rows that are written are bit-identical to hirest_attention_bf16's.  The last
+/* The same, but only the output rows of queries [0, q_rows) of every sequence are written; rows from q_rows on are left
+ * untouched (every kernel computes the leading ceil(q_rows / 16) query tiles, still streams all keys / values, and stores
+ * the rows below q_rows of them).  Rows that are written are bit-identical to hirest_attention_bf16's.  The last
  * block of the vision tower uses q_rows = 1: vit_model.py:340-351 reads only x[:, 0] after it. */
 int hirest_attention_bf16_rows(const hirest_bf16* qkv, hirest_bf16* out,
                                int32_t B, int32_t N, int32_t H, int32_t dh,

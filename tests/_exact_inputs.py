@@ -1,0 +1,317 @@
+"""Inputs whose results are known without a tolerance, and the fp64 references that go with them, for tests/test_gpu_gemm_exact.py and
+tests/test_gpu_attention_edges.py.  tests/test_exact_inputs_host.py checks every precondition stated here on the CPU, so a wrong
+generator cannot make a GPU test pass vacuously.  Not a test module.
+
+"Exact inputs" for the bf16 GEMM: operands are small integers (or integers times a power of two), so every product and every
+partial sum is an integer multiple of one power of two and smaller than 2^24 times it: fp32 accumulation is exact in ANY order, and
+the result of every kernel, tile walk and split-K order is one known bit pattern."""
+import math
+
+import numpy as np
+import torch
+
+F32_EXACT = 2 ** 24          # integers of magnitude up to 2^24 are fp32 numbers
+
+# (M, N, K) of tests/test_gpu_gemm_exact.py: tile-edge neighbours of the 128 and 256 tiles, one row, a deep K, and more 256 x 256 tiles
+# (18 x 17 = 306) than the 256 CUs so the persistent kernels walk more than one tile per workgroup
+GEMM_SHAPES = [(1, 4, 64), (63, 260, 448), (127, 124, 64), (128, 128, 64), (129, 132, 128), (255, 252, 192), (256, 256, 192),
+               (257, 260, 192), (385, 644, 128), (257, 260, 6144), (4360, 4100, 64)]
+GEMM_BIG = (4360, 4100, 64)
+GEMM_STRIDED_SHAPES = [(129, 132, 128), (257, 260, 192)]
+GEMM_GELU_SHAPES = [(129, 132, 128), (257, 260, 192)]
+GEMM_LNSTATS_SHAPES = [(64, 256, 64), (129, 264, 192)]
+# M = B * P of the patch-embed epilogue, per M above
+PATCH_FRAMES = {1: 1, 63: 3, 127: 1, 128: 2, 129: 3, 255: 5, 256: 4, 257: 1, 385: 5, 4360: 8}
+# split-operand cases: (M, N, original K); the GEMM's K argument is twice that
+X3_SHAPES = [(131, 132, 64), (1, 4, 32), (2060, 2048, 32), (4360, 4100, 32), (300, 260, 512)]
+X3_GELU_SHAPE = (257, 288, 64)
+X3_FRAC = 2.0 ** -10
+
+
+def _rng(*key):
+    return np.random.default_rng([int(k) for k in key])
+
+
+def _ints(rng, shape, lo, hi):
+    return torch.from_numpy(rng.integers(lo, hi + 1, size=shape).astype(np.float32))
+
+
+_GEMM_CACHE = {}
+
+
+def gemm_exact(M, N, K):
+    """a [M, K], w [N, K] bf16 integers in [-3, 3]; bias [N], resid [M, N], pos [P + 1, N] fp32 integers in [-8, 8]; ref = a w^T (fp32,
+    exact).  Every 16th row of a is all 3 and two of every 8 rows of w are non-negative, so some sums exceed 256 at every K: there bf16 keeps
+    fewer bits than the integer has, and odd values are exact ties of the bf16 rounding."""
+    key = (M, N, K)
+    if key not in _GEMM_CACHE:
+        if len(_GEMM_CACHE) >= 2:
+            _GEMM_CACHE.pop(next(iter(_GEMM_CACHE)))
+        rng = _rng(11, M, N, K)
+        a, w = _ints(rng, (M, K), -3, 3), _ints(rng, (N, K), -3, 3)
+        a[0::16] = 3.0
+        w[0::8] = w[0::8].abs()
+        w[1::8] = w[1::8].abs()
+        P = M // PATCH_FRAMES.get(M, 1)
+        bias, ref = _ints(rng, (N,), -8, 8), a @ w.t()
+        # (in [256, 512) bf16 keeps even integers: 1 mod 4 is a tie that rounds down, 3 mod 4 one that rounds up; the one-row shape gets both)
+        for col, residue in ((0, 1), (1, 3)):
+            if 256 <= ref[0, col] < 500:
+                bias[col] = (residue - ref[0, col]) % 4
+        d = {"a": a.to(torch.bfloat16), "w": w.to(torch.bfloat16), "bias": bias, "resid": _ints(rng, (M, N), -8, 8),
+             "pos": _ints(rng, (P + 1, N), -8, 8), "P": P, "ref": ref}
+        _GEMM_CACHE[key] = d
+    return _GEMM_CACHE[key]
+
+
+def gemm_lnstats(M, N, K):
+    """The same integers for the LN-statistics producer, with a milder structure (every 16th row of a and every 8th row of w non-negative; all-3 rows
+    only at K <= 64): x = resid + a w^T + bias still passes 256, where bf16 rounds, but the sum of x^2 over a row stays below 2^24."""
+    rng = _rng(14, M, N, K)
+    a, w = _ints(rng, (M, K), -3, 3), _ints(rng, (N, K), -3, 3)
+    a[0::16] = 3.0 if K <= 64 else a[0::16].abs()                  # (sums of about 330 at K = 64 and about 560 at K = 192)
+    w[0::8] = w[0::8].abs()
+    return {"a": a.to(torch.bfloat16), "w": w.to(torch.bfloat16), "bias": _ints(rng, (N,), -8, 8), "resid": _ints(rng, (M, N), -8, 8), "ref": a @ w.t()}
+
+
+def bf16_ties(t):
+    """Elements of the fp32 tensor t that lie exactly halfway between two bf16 numbers."""
+    return (t.contiguous().view(torch.int32) & 0xFFFF) == 0x8000
+
+
+def gelu_shift(K):
+    """s with the pre-activation's standard deviation sqrt(4 K / 9) 2^-s nearest 3 (a, w uniform on {-1, 0, 1}: variance 2/3 each)."""
+    return max(0, round(0.5 * math.log2(4.0 * K / 81.0)))
+
+
+def gemm_gelu(M, N, K):
+    """a in {-1, 0, 1}, w in {-1, 0, 1} * 2^-s (bf16), bias in multiples of 1/8 in [-2, 2]: x = a w^T + bias is exact in fp32."""
+    rng = _rng(12, M, N, K)
+    s = gelu_shift(K)
+    a, w = _ints(rng, (M, K), -1, 1), _ints(rng, (N, K), -1, 1) * 2.0 ** -s
+    bias = _ints(rng, (N,), -16, 16) / 8.0
+    return {"a": a.to(torch.bfloat16), "w": w.to(torch.bfloat16), "bias": bias, "x": a @ w.t() + bias, "s": s}
+
+
+def gelu_ref(x):
+    """nn.GELU() (erf form) in fp64: x Phi(x)."""
+    x = x.double()
+    return x * 0.5 * torch.erfc(-x / math.sqrt(2.0))
+
+
+def qgelu_ref(x):
+    x = x.double()
+    return x * torch.sigmoid(1.702 * x)
+
+
+def ulp_bf16(g):
+    """Spacing of the bf16 numbers around g (fp64 tensor): 2^(floor(log2 |g|) - 7); 0 at 0."""
+    m, e = torch.frexp(g.double().abs())              # |g| = m 2^e, m in [0.5, 1)
+    return torch.where(g == 0, torch.zeros_like(m), torch.ldexp(torch.ones_like(m), e - 1 - 7))
+
+
+def gelu_bound(g):
+    """|out - g| allowed for a bf16 store of an fp32 GELU: half a bf16 ulp, plus twice the fp32 error csrc/common.h documents for gelu_erf
+    (2e-5 relative, 1.1e-6 absolute).  Worst error / bound observed on the MI355X: GELU 0.963, QuickGELU 0.958."""
+    return ulp_bf16(g) / 2 + 4e-5 * g.abs() + 2e-6
+
+
+def split2_cpu(x):
+    """[rows, D] fp32 -> [rows, 2 D] bf16 in the format ops.split2 documents: per 64 output columns, the hi parts of 32 consecutive input
+    columns, then their lo parts (hi = bf16(x), lo = bf16(x - hi))."""
+    rows, D = x.shape
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.float()).to(torch.bfloat16)
+    out = torch.empty((rows, D // 32, 2, 32), dtype=torch.bfloat16)
+    out[:, :, 0] = hi.reshape(rows, D // 32, 32)
+    out[:, :, 1] = lo.reshape(rows, D // 32, 32)
+    return out.reshape(rows, 2 * D)
+
+
+def unsplit2_cpu(x2):
+    """hi + lo of a split operand, in fp32."""
+    rows, D2 = x2.shape
+    return x2.reshape(rows, D2 // 64, 2, 32).float().sum(dim=2).reshape(rows, D2 // 2)
+
+
+def gemm_x3(M, N, K, frac_in_a):
+    """Split-operand case: one operand integer + integer * 2^-10 (both in [-3, 3]), the other integer: its lo part is 0, so the lo * lo
+    product the kernel drops is 0 and hi-hi + hi-lo + lo-hi is the whole product.  a, w fp32 values; a2, w2 their split forms."""
+    rng = _rng(13, M, N, K, int(frac_in_a))
+    a, w = _ints(rng, (M, K), -3, 3), _ints(rng, (N, K), -3, 3)
+    if frac_in_a:
+        a = a + _ints(rng, (M, K), -3, 3) * X3_FRAC
+    else:
+        w = w + _ints(rng, (N, K), -3, 3) * X3_FRAC
+    return {"a": a, "w": w, "a2": split2_cpu(a), "w2": split2_cpu(w), "bias": _ints(rng, (N,), -8, 8), "resid": _ints(rng, (M, N), -8, 8),
+            "ref": (a.double() @ w.double().t()).float()}
+
+
+def gemm_x3_gelu(M, N, K):
+    """The GELU inputs as split operands (both lo parts 0)."""
+    d = gemm_gelu(M, N, K)
+    d["a2"], d["w2"] = split2_cpu(d["a"].float()), split2_cpu(d["w"].float())
+    return d
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# attention
+# ------------------------------------------------------------------------------------------------------------------------------
+ATTN_N = [1, 15, 16, 17, 64, 79, 80, 81, 96, 255, 256, 257, 271, 272]
+ATTN_H = 2
+
+
+def pack_qkv(q, k, v):
+    """q, k, v [B, N, H, dh] -> the packed activation [B * N, 3 * H * dh] (columns: which, head, dh), bf16."""
+    B, N, H, dh = q.shape
+    return torch.stack([q, k, v], dim=2).reshape(B * N, 3 * H * dh).to(torch.bfloat16)
+
+
+def unpack_qkv(qkv, B, N, H, dh):
+    q, k, v = qkv.reshape(B, N, 3, H, dh).unbind(2)
+    return q, k, v
+
+
+def admitted(N, causal):
+    """[N queries, N keys] bool: key j is visible to query i."""
+    m = torch.ones((N, N), dtype=torch.bool)
+    return m.tril() if causal else m
+
+
+def attention_logits(qkv, B, N, H, dh):
+    """Natural-unit logits scale * q . k in fp64, [B, H, N, N]."""
+    q, k, _ = unpack_qkv(qkv.double(), B, N, H, dh)
+    return torch.einsum("bihd,bjhd->bhij", q, k) * dh ** -0.5
+
+
+def attention_ref(qkv, B, N, H, dh, causal):
+    """softmax(scale q k^T [+ causal mask]) v in fp64, [B * N, H * dh]."""
+    s = attention_logits(qkv, B, N, H, dh).masked_fill(~admitted(N, causal), float("-inf"))
+    v = unpack_qkv(qkv.double(), B, N, H, dh)[2]
+    return torch.einsum("bhij,bjhd->bihd", torch.softmax(s, -1), v).reshape(B * N, H * dh)
+
+
+def column_max_admitted(qkv, B, N, H, dh, causal):
+    """max over the keys j visible to query i of |v[b, j, h, d]|, [B * N, H * dh] fp64: the scale of the per-element bound."""
+    v = unpack_qkv(qkv.double(), B, N, H, dh)[2].abs()
+    m = torch.cummax(v, dim=1).values if causal else v.amax(dim=1, keepdim=True).expand_as(v)
+    return m.reshape(B * N, H * dh)
+
+
+def _distinct_v(rng, shape):
+    """Non-zero bf16 values with random sign, exponent in {-1, 0, 1} and a random 7-bit significand: two different (frame, head, key)
+    rows agree in all dh columns with probability 2^-9dh."""
+    bits = (rng.integers(0, 2, size=shape) << 15) | (rng.integers(126, 129, size=shape) << 7) | rng.integers(0, 128, size=shape)
+    return torch.from_numpy(bits.astype(np.uint16).view(np.int16)).view(torch.bfloat16)
+
+
+def attn_selector(B, N, H, dh, causal, seed):
+    """Family 1.  k_j are random +-1 rows and q_i = 32 k_pi(i): the selected logit 32 sqrt(dh) exceeds every other by more than 64, so its p is
+    exactly 1, every other p is below 2^-92 and vanishes against it in fp32: out[b, i, h] == v[b, pi(i), h] bit for bit.  pi is a random
+    permutation per (frame, head), or a random pi(i) <= i when causal with pi(i) = i at i % 3 == 0 and pi(i) = 0 at i % 3 == 1."""
+    rng = _rng(21, B, N, H, dh, int(causal), seed)
+    k = torch.from_numpy(rng.integers(0, 2, size=(B, N, H, dh)).astype(np.float32) * 2 - 1)
+    if causal:
+        pi = rng.integers(0, np.arange(N)[None, None, :] + 1, size=(B, H, N))
+        pi[:, :, 0::3] = np.arange(N)[0::3]
+        pi[:, :, 1::3] = 0
+    else:
+        pi = np.stack([np.stack([rng.permutation(N) for _ in range(H)]) for _ in range(B)])
+    pi = torch.from_numpy(pi.astype(np.int64))                                        # [B, H, N]
+    idx = pi.permute(0, 2, 1)[..., None].expand(B, N, H, dh)                          # gather along the key axis
+    q = 32.0 * torch.gather(k, 1, idx)
+    v = _distinct_v(rng, (B, N, H, dh))
+    want = torch.gather(v.view(torch.int16), 1, idx).view(torch.bfloat16).reshape(B * N, H * dh)
+    return {"qkv": pack_qkv(q, k, v.float()), "pi": pi, "want": want}
+
+
+def selector_gap(d, B, N, H, dh, causal):
+    """Smallest (selected logit - largest other visible logit) over all rows, in natural units, from the fp64 logits."""
+    s = attention_logits(d["qkv"], B, N, H, dh).masked_fill(~admitted(N, causal), float("-inf"))
+    sel = torch.gather(s, 3, d["pi"][..., None])
+    rest = s.scatter(3, d["pi"][..., None], float("-inf")).amax(-1, keepdim=True)
+    return (sel - rest).min().item() if N > 1 else float("inf")
+
+
+def attn_uniform(B, N, H, dh, causal, seed):
+    """Family 2.  q = 0: every visible p is exactly 1.  V[j, d] = 1 if j % dh == d else 0, so out[i, d] = (visible keys j with j % dh == d) /
+    (visible keys): one key too many or too few moves some column by at least 1 / (count + 1) >= 20 %."""
+    rng = _rng(22, B, N, H, dh, int(causal), seed)
+    k = torch.from_numpy(rng.standard_normal((B, N, H, dh)).astype(np.float32))
+    q = torch.zeros((B, N, H, dh))
+    v = ((torch.arange(N)[:, None] % dh) == torch.arange(dh)[None, :]).float()[None, :, None, :].expand(B, N, H, dh)
+    adm = admitted(N, causal).double()
+    keys = adm.sum(1)                                                                  # [N]
+    ref = (adm @ v[0, :, 0].double()) / keys[:, None]                                  # [N, dh]
+    ref = ref[None, :, None, :].expand(B, N, H, dh).reshape(B * N, H * dh)
+    return {"qkv": pack_qkv(q, k, v), "ref": ref, "keys": keys.long()}
+
+
+def uniform_bound(ref):
+    """out = bf16(count * fl(1 / keys)): half a bf16 ulp of the quotient, plus 2^-19 relative and 2^-24 absolute for the two fp32 roundings
+    before it (they can also move the value across a rounding midpoint).
+    The first term was first written as 2^-9 |ref|.  That is half an ulp only for significands near 2: bf16 keeps 8 significant bits, so half an
+    ulp is between 2^-9 |ref| and 2^-8 |ref| (1 / 15 = 1.0667 * 2^-4 rounds with an error of 1.87 * 2^-9 |ref| in every kernel and in
+    torch's own bf16 cast).  The term is the rounding of the bf16 store itself; the kernels are right and the derivation was corrected.
+    The slack terms are the original ones (2^-9 * 2^-10 = 2^-19).  Worst error / bound observed on the MI355X: 0.995 (against the first form
+    of the bound: 1.98)."""
+    return ulp_bf16(ref) / 2 + 2.0 ** -19 * ref.abs() + 2.0 ** -24
+
+
+def attn_isolation(B, N, H, dh, causal, seed):
+    """Family 3.  Within a frame every logit is about -200: q = -c s_b u and k = s_b (u + small) with u a +-1 vector per head, c = 200 /
+    sqrt(dh) and s_b = +1 / -1 in even / odd frames.  A key borrowed from the neighbouring frame meets q with the other sign: logit +200,
+    400 above the real ones, so it would take the whole softmax."""
+    rng = _rng(23, B, N, H, dh, int(causal), seed)
+    u = torch.from_numpy(rng.integers(0, 2, size=(1, 1, H, dh)).astype(np.float32) * 2 - 1)
+    sgn = torch.tensor([1.0, -1.0]).repeat((B + 1) // 2)[:B].reshape(B, 1, 1, 1)
+    small = torch.from_numpy(rng.standard_normal((B, N, H, dh)).astype(np.float32)) * 2.0 ** -4
+    c = 200.0 / math.sqrt(dh)
+    q = (-c * sgn * u).expand(B, N, H, dh)
+    k = sgn * (u + small)
+    v = torch.from_numpy(rng.standard_normal((B, N, H, dh)).astype(np.float32))
+    return {"qkv": pack_qkv(q, k, v)}
+
+
+def attn_random(B, N, H, dh, causal, qscale):
+    """Family 4: the inputs of test_gpu_parity.py::test_attention, with V column 1 of every head scaled by 64 and column 2 by 1 / 64 (a
+    bound relative to the tensor's maximum would be blind to the small column)."""
+    from hirest_amd import synth
+    D = H * dh
+    x = synth.tensor(f"at.{N}.{dh}", (B * N, 3 * D), 1.0, 9).to(torch.bfloat16).float()
+    x[:, :D] *= qscale
+    vv = x[:, 2 * D:].reshape(B * N, H, dh)
+    vv[:, :, 1] *= 64.0
+    vv[:, :, 2] /= 64.0
+    return {"qkv": x.to(torch.bfloat16)}
+
+
+def attention_bound(colmax):
+    """|out - ref| per element: three bf16 roundings of at most 2^-9 each relative to the column maximum over the visible keys (P, the
+    fp32 normaliser's mismatch with the rounded P, the output) and a fourth 2^-9 for the fp32 score and exp2 error.  Worst error / bound
+    observed on the MI355X: 0.605 on random inputs, 0.598 on the isolation inputs."""
+    return 2 * 2.0 ** -8 * colmax
+
+
+# Which launcher of csrc/attention.hip a call reaches: copied from the dispatch in hirest_attention_bf16_rows.
+def attention_launcher(variant, B, N, dh, causal):
+    """(launcher, DH, NT, FAST, causal[, variant]) — the template instantiation and the causal flag it runs with."""
+    if variant >= 3 and 80 < N <= 272 and B >= 64:
+        return ("launch3", dh, 17, (not causal) and N > 256, bool(causal), variant)
+    nt = 5 if N <= 80 else 17
+    return ("launch2" if variant >= 2 else "launch", dh, nt, None, bool(causal))
+
+
+def attention_launchers_all():
+    """Every instantiation the entry can reach, with both causal settings where the instantiation takes both (FAST is non-causal only)."""
+    out = set()
+    for dh in (64, 88):
+        for nt in (5, 17):
+            for c in (False, True):
+                out.add(("launch", dh, nt, None, c))
+                out.add(("launch2", dh, nt, None, c))
+        for variant in (3, 4, 5, 6, 7):
+            out.add(("launch3", dh, 17, True, False, variant))
+            out.add(("launch3", dh, 17, False, False, variant))
+            out.add(("launch3", dh, 17, False, True, variant))
+    return out

@@ -1,0 +1,236 @@
+"""The preconditions of tests/_exact_inputs.py, checked on the CPU: the GPU tests that use these generators (test_gpu_gemm_exact.py,
+test_gpu_attention_edges.py) assert bit equality or derived bounds that only mean something while these hold."""
+import ctypes
+
+import pytest
+import torch
+
+import _exact_inputs as X
+
+
+@pytest.mark.parametrize("M,N,K", X.GEMM_SHAPES)
+def test_gemm_integer_inputs_are_exact_in_fp32(M, N, K):
+    d = X.gemm_exact(M, N, K)
+    a, w = d["a"].float(), d["w"].float()
+    assert a.abs().max() <= 3 and w.abs().max() <= 3 and torch.equal(a, a.round()) and torch.equal(w, w.round())
+    for t in (d["bias"], d["resid"], d["pos"]):
+        assert t.abs().max() <= 8 and torch.equal(t, t.round())
+    # every partial sum is an integer of magnitude <= 9 K (+ 16 for bias and residual): far below 2^24, so fp32 holds it in any order
+    assert 9 * K + 16 < X.F32_EXACT and K <= 6144
+    ref64 = a.double() @ w.double().t()
+    assert torch.equal(d["ref"].double(), ref64)                        # fp32 matmul == fp64 matmul
+    assert ref64.abs().max().item() + 16 < X.F32_EXACT
+    assert d["pos"].shape == (d["P"] + 1, N) and M % d["P"] == 0
+    # the bf16 epilogue must round to nearest even: the data holds exact ties (halfway between two bf16 numbers) whose two neighbours
+    # differ, so round-half-away and truncation both give other bits somewhere
+    t = d["ref"] + d["bias"]
+    ties = X.bf16_ties(t)
+    assert ties.any(), "no exact bf16 tie in a w^T + bias"
+    rne = t.to(torch.bfloat16).float()
+    trunc = (t.view(torch.int32) & ~0xFFFF).view(torch.float32)
+    away = torch.where(ties, trunc + (t - trunc) * 2, rne)
+    assert (ties & (rne != trunc)).any() and (ties & (rne != away)).any()      # ties that round up, and ties that round down
+    assert (ref64 + d["resid"].double() + d["bias"].double()).abs().max().item() < X.F32_EXACT
+
+
+@pytest.mark.parametrize("M,N,K", X.GEMM_LNSTATS_SHAPES)
+def test_lnstats_row_sums_are_exact(M, N, K):
+    """Sums of x and x^2 over a row of the bf16-rounded stream stay integers below 2^24, and the stream holds bf16 ties."""
+    d = X.gemm_lnstats(M, N, K)
+    assert M >= 64 and N >= 256 and N % 8 == 0
+    ref64 = d["a"].double() @ d["w"].double().t()
+    assert torch.equal(d["ref"].double(), ref64)
+    x = d["ref"] + d["bias"] + d["resid"]
+    assert torch.equal(x.double(), ref64 + d["bias"].double() + d["resid"].double())
+    assert X.bf16_ties(x).any()
+    xb = x.to(torch.bfloat16).double()
+    assert torch.equal(xb, xb.round())
+    assert (xb * xb).sum(1).max().item() < X.F32_EXACT and xb.abs().sum(1).max().item() < X.F32_EXACT
+    var = (xb * xb).mean(1) - xb.mean(1) ** 2
+    assert (var / (xb * xb).mean(1)).min().item() >= 2.0 ** -20        # (no cancellation in E x^2 - mean^2 worth speaking of)
+
+
+@pytest.mark.parametrize("M,N,K", X.GEMM_GELU_SHAPES + [X.X3_GELU_SHAPE])
+def test_gelu_pre_activation_is_exact_and_spread(M, N, K):
+    d = X.gemm_gelu(M, N, K)
+    a, w = d["a"].float(), d["w"].float()
+    assert set(a.unique().tolist()) <= {-1.0, 0.0, 1.0} and set((w * 2.0 ** d["s"]).unique().tolist()) <= {-1.0, 0.0, 1.0}
+    assert torch.equal(d["bias"] * 8, (d["bias"] * 8).round())
+    x64 = a.double() @ w.double().t() + d["bias"].double()
+    assert torch.equal(d["x"].double(), x64)
+    # multiples of 2^-s (s <= 3 with the bias) of magnitude <= K + 2: exact in fp32 in any order
+    assert d["s"] <= 3 and (K + 2) * 8 < X.F32_EXACT
+    assert 2.0 <= x64.std().item() <= 4.5
+    ax = x64.abs()
+    assert ((ax >= 0.25) & (ax <= 6)).double().mean().item() >= 0.25
+    assert (x64 < -6).any() and (x64 > 6).any()
+
+
+def test_gelu_bound_terms():
+    g = torch.tensor([0.0, 1.0, 1.5, 2.0, -0.17, 255.0, 1e-9], dtype=torch.float64)
+    assert X.ulp_bf16(g).tolist() == [0.0, 2.0 ** -7, 2.0 ** -7, 2.0 ** -6, 2.0 ** -10, 1.0, 2.0 ** -37]
+    for v in (1.0, 1.5, -0.17, 255.0):
+        b = torch.tensor([v], dtype=torch.bfloat16)
+        nxt = (b.view(torch.int16) + 1).view(torch.bfloat16)
+        assert abs(nxt.item() - b.item()) == X.ulp_bf16(b.double()).item()
+    x = torch.linspace(-8, 8, 4001, dtype=torch.float64)
+    assert (X.gelu_ref(x) - torch.nn.functional.gelu(x)).abs().max().item() < 1e-15
+
+
+@pytest.mark.parametrize("M,N,K", X.X3_SHAPES)
+@pytest.mark.parametrize("frac_in_a", [True, False])
+def test_x3_inputs_split_exactly(M, N, K, frac_in_a):
+    d = X.gemm_x3(M, N, K, frac_in_a)
+    for name in ("a", "w"):
+        x, x2 = d[name], d[name + "2"]
+        assert x2.shape == (x.shape[0], 2 * K) and x2.dtype == torch.bfloat16
+        assert torch.equal(X.unsplit2_cpu(x2), x)                        # hi + lo is the fp32 value, exactly
+        blocks = x2.reshape(x.shape[0], K // 32, 2, 32)
+        assert torch.equal(blocks[:, :, 0].reshape(x.shape), x.to(torch.bfloat16))
+    frac, whole = ("a", "w") if frac_in_a else ("w", "a")
+    lo = lambda t: t.reshape(t.shape[0], K // 32, 2, 32)[:, :, 1]
+    assert lo(d[whole + "2"]).float().abs().max().item() == 0            # one operand has lo == 0: the dropped lo * lo term is 0
+    assert lo(d[frac + "2"]).float().abs().max().item() > 0              # ... and the other one exercises the hi * lo path
+    # everything is a multiple of 2^-10; |sum| * 2^10 < 2^24 keeps every partial sum an fp32 number
+    bound = (d["a"].double().abs() @ d["w"].double().abs().t()).max().item() + 16
+    assert bound * 2 ** 10 < X.F32_EXACT
+    assert torch.equal(d["ref"].double(), d["a"].double() @ d["w"].double().t())
+    assert torch.equal(d["ref"] * 2 ** 10, (d["ref"] * 2 ** 10).round())
+
+
+@pytest.mark.parametrize("dh", [64, 88])
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("N", X.ATTN_N)
+def test_selector_gap(N, dh, causal):
+    B, H = 3, X.ATTN_H
+    d = X.attn_selector(B, N, H, dh, causal, 0)
+    assert X.selector_gap(d, B, N, H, dh, causal) >= 64
+    pi = d["pi"]
+    if causal:
+        assert (pi <= torch.arange(N)).all() and (pi[:, :, 0::3] == torch.arange(N)[0::3]).all() and (pi[:, :, 1::3] == 0).all()
+    else:
+        assert torch.equal(pi.sort(-1).values, torch.arange(N).expand(B, H, N))
+    _, _, v = X.unpack_qkv(d["qkv"], B, N, H, dh)
+    assert (v.float() != 0).all()
+    rows = v.permute(0, 2, 1, 3).reshape(B * H * N, dh).view(torch.int16)
+    assert torch.unique(rows, dim=0).shape[0] == B * H * N               # no two (frame, head, key) rows of v agree
+    # the fp64 reference agrees: softmax puts everything on pi(i)
+    ref = X.attention_ref(d["qkv"], B, N, H, dh, causal)
+    assert torch.equal(ref.to(torch.bfloat16).view(torch.int16), d["want"].view(torch.int16))
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_selector_keys_are_nearly_orthogonal(seed):
+    """+-1 keys at N = 272, dh = 64, 3 frames: max off-diagonal |k_i . k_j| <= 40, i.e. every other logit <= 32 * 40 / 8 = 160 = 256 - 96.
+    The 64-frame cases have 20 times as many pairs and reach 44 or so; what they need is the gap of 64 (|k_i . k_j| <= 48)."""
+    N, H, dh = 272, X.ATTN_H, 64
+    d = X.attn_selector(3, N, H, dh, False, seed)
+    _, k, _ = X.unpack_qkv(d["qkv"].float(), 3, N, H, dh)
+    g = torch.einsum("bihd,bjhd->bhij", k, k)
+    g.diagonal(dim1=-2, dim2=-1).zero_()
+    assert g.abs().max().item() <= 40
+    for dh in (64, 88):
+        for causal in (False, True):
+            d = X.attn_selector(64, N, H, dh, causal, seed)
+            assert X.selector_gap(d, 64, N, H, dh, causal) >= 64
+
+
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("N,dh", [(1, 64), (17, 64), (80, 88), (257, 64), (272, 88)])
+def test_uniform_reference_and_sensitivity(N, dh, causal):
+    B, H = 2, X.ATTN_H
+    d = X.attn_uniform(B, N, H, dh, causal, 0)
+    q, _, v = X.unpack_qkv(d["qkv"].float(), B, N, H, dh)
+    assert q.abs().max().item() == 0 and set(v.unique().tolist()) <= {0.0, 1.0}
+    ref = X.attention_ref(d["qkv"], B, N, H, dh, causal)
+    assert (ref - d["ref"]).abs().max().item() < 1e-15
+    assert torch.equal(d["keys"], torch.arange(1, N + 1) if causal else torch.full((N,), N))
+    # one more copy of the last visible key (the clamped duplicate of row N - 1 left unmasked) turns count / keys into (count + 1) /
+    # (keys + 1) in that key's column: far outside the bound wherever it changes anything (count < keys)
+    rows = torch.arange(N)
+    r = d["ref"].reshape(B, N, H, dh)[0, :, 0]                           # [N, dh]
+    keys = d["keys"].double()
+    col = (rows if causal else torch.full((N,), N - 1)) % dh
+    have = r[rows, col]
+    cnt = have * keys
+    delta = ((cnt + 1) / (keys + 1) - have).abs()
+    sees = cnt < keys - 0.5
+    assert (delta[sees] > 4 * X.uniform_bound(have)[sees]).all() and (sees.any() or N == 1)
+    assert (delta[sees] >= 0.19 * have[sees]).all()
+
+
+@pytest.mark.parametrize("dh", [64, 88])
+def test_isolation_logits(dh):
+    B, N, H = 3, 81, X.ATTN_H
+    d = X.attn_isolation(B, N, H, dh, False, 0)
+    s = X.attention_logits(d["qkv"], B, N, H, dh)
+    assert s.max().item() < -150 and s.min().item() > -250
+    # a key of the neighbouring frame against this frame's queries: about +200
+    q, k, _ = X.unpack_qkv(d["qkv"].double(), B, N, H, dh)
+    cross = torch.einsum("bihd,bjhd->bhij", q[:-1], k[1:]) * dh ** -0.5
+    assert cross.min().item() > 150
+    cross = torch.einsum("bihd,bjhd->bhij", q[1:], k[:-1]) * dh ** -0.5
+    assert cross.min().item() > 150
+
+
+def test_random_family_has_a_small_and_a_large_column():
+    B, N, H, dh = 3, 96, X.ATTN_H, 64
+    d = X.attn_random(B, N, H, dh, True, 6.0)
+    cm = X.column_max_admitted(d["qkv"], B, N, H, dh, True).reshape(B, N, H, dh)
+    assert cm[:, -1, :, 1].min().item() > 64 and cm[:, -1, :, 2].max().item() < 0.1
+    assert (cm[:, 1:] >= cm[:, :-1]).all()                               # causal: the visible set only grows
+    full = X.column_max_admitted(d["qkv"], B, N, H, dh, False).reshape(B, N, H, dh)
+    assert torch.equal(full[:, 0], cm[:, -1])
+
+
+def test_attention_launcher_table_covers_every_instantiation():
+    """The (variant, B, N) grid of test_gpu_attention_edges.py reaches every launcher instantiation of hirest_attention_bf16_rows."""
+    reached = set()
+    for dh in (64, 88):
+        for causal in (False, True):
+            for N in X.ATTN_N:
+                for v in (1, 2, 7):
+                    reached.add(X.attention_launcher(v, 3, N, dh, causal))
+                if N > 80:
+                    for v in (3, 4, 5, 6, 7):
+                        reached.add(X.attention_launcher(v, 64, N, dh, causal))
+    assert reached == X.attention_launchers_all()
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from hirest_amd import _lib, build
+    build.build(verbose=False)
+    return _lib.load()
+
+
+def test_attention_rejects_unsupported_shapes_before_any_launch(lib):
+    """N = 273 and dh = 80 give HIREST_E_SHAPE for every variant: the entry returns before a launch, the placeholder pointers are never
+    dereferenced."""
+    X_PTR, SHAPE = 1 << 20, -2
+    try:
+        for variant in range(1, 8):
+            assert lib.hirest_attention_select_kernel(variant) == 0
+            for B in (3, 64):
+                assert lib.hirest_attention_bf16(X_PTR, X_PTR, B, 273, 2, 64, 0.125, 0, None) == SHAPE
+                assert lib.hirest_attention_bf16(X_PTR, X_PTR, B, 273, 2, 88, 0.1, 1, None) == SHAPE
+                assert lib.hirest_attention_bf16(X_PTR, X_PTR, B, 96, 2, 80, 0.1, 0, None) == SHAPE
+                assert lib.hirest_attention_bf16(X_PTR, X_PTR, B, 16, 2, 80, 0.1, 1, None) == SHAPE
+                assert lib.hirest_attention_bf16_rows(X_PTR, X_PTR, B, 273, 2, 64, 0.125, 0, 1, None) == SHAPE
+    finally:
+        lib.hirest_attention_select_kernel(7)
+
+
+def test_gemm_rejects_output_strides_the_epilogues_cannot_store_to(lib):
+    """The epilogues store 4 (fp32) or 4 / 8 (bf16) consecutive elements per lane at out + m * ldo + n with n % 4 == 0: ldo % 4 != 0 would
+    misalign them.  Rejected with HIREST_E_SHAPE before any launch."""
+    from hirest_amd import _lib
+    X_PTR = 1 << 20
+    for epi in (_lib.EPI_BIAS_BF16, _lib.EPI_BIAS_GELU_BF16, _lib.EPI_BIAS_QGELU_BF16, _lib.EPI_BIAS_RESID_F32, _lib.EPI_BIAS_F32):
+        for flags in (0, _lib.GEMM_REVERSE):
+            for ldo in (133, 134, 135, 138):
+                a = _lib.GemmArgs.make(X_PTR, 64, X_PTR, 64, None, X_PTR, ldo, 129, 132, 64, epi, None, 0, None, None, flags)
+                assert lib.hirest_gemm_bf16(ctypes.byref(a), None) == -2, (epi, ldo)
+    for epi in (_lib.EPI_BIAS_F32, _lib.EPI_BIAS_RESID_F32):             # the split-operand kernels share the fp32 epilogue
+        a = _lib.GemmArgs.make(X_PTR, 64, X_PTR, 64, None, X_PTR, 134, 129, 132, 64, epi, None, 0, None, None, _lib.GEMM_X3)
+        assert lib.hirest_gemm_bf16(ctypes.byref(a), None) == -2
