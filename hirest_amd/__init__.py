@@ -10,6 +10,7 @@ from .bert_score import BERTScorer  # noqa: F401
 from .evaluation import evaluate_bert_score  # noqa: F401
 from . import optim  # noqa: F401
 from . import cascade  # noqa: F401
+from . import whisper  # noqa: F401
 from .cascade import run_end_to_end, end_to_end_results  # noqa: F401
 # (the function takes the submodule's name in this namespace; its helpers: ``from hirest_amd.predict import merge_rank_results``)
 from .predict import predict  # noqa: F401

@@ -608,3 +608,94 @@ def c3_device_names(V: int) -> list:
     """Unique file names whose string order is not the corpus order (the tie rule of evaluate.py:58-60 sorts by name)."""
     assert V <= 10007
     return [f"video_{(v * 7919) % 10007:05d}.mp4" for v in range(V)]
+
+
+# ----------------------------------------------------------------------------------
+# Whisper's audio encoder (extraction/whisper_ASR/extract_ASR.py:  whisper.load_model('small.en')) in the Hugging Face WhisperEncoder
+# checkpoint schema, config keys as in its config.json.  WHISPER_SMALL_EN only shapes tools/whisper_bench.py; the lettered configs are the
+# cases of tests/golden/whisper_enc_*.npz (a: odd ctx, ragged in every tile, 64-wide heads; b: 32-wide heads; c: Whisper-tiny's width,
+# whose second convolution takes the fp32 GEMM's split form, M > 256 and K >= 1024); WHISPER_E2E has the real 1500-token context.
+# ----------------------------------------------------------------------------------
+
+WHISPER_SMALL_EN = {"num_mel_bins": 80, "d_model": 768, "encoder_attention_heads": 12, "encoder_layers": 12, "encoder_ffn_dim": 3072,
+                    "max_source_positions": 1500}
+WHISPER_TINY_A = {"num_mel_bins": 80, "d_model": 128, "encoder_attention_heads": 2, "encoder_layers": 2, "encoder_ffn_dim": 512,
+                  "max_source_positions": 33}
+WHISPER_TINY_B = {"num_mel_bins": 80, "d_model": 128, "encoder_attention_heads": 4, "encoder_layers": 2, "encoder_ffn_dim": 512,
+                  "max_source_positions": 97}
+WHISPER_TINY_C = {"num_mel_bins": 80, "d_model": 384, "encoder_attention_heads": 6, "encoder_layers": 1, "encoder_ffn_dim": 1536,
+                  "max_source_positions": 261}
+WHISPER_E2E = {"num_mel_bins": 80, "d_model": 128, "encoder_attention_heads": 2, "encoder_layers": 1, "encoder_ffn_dim": 512,
+               "max_source_positions": 1500}
+WHISPER_CASES = {"a": (WHISPER_TINY_A, 3), "b": (WHISPER_TINY_B, 2), "c": (WHISPER_TINY_C, 1)}      # case -> (config, clips)
+
+
+def whisper_encoder_shapes(c: dict) -> Dict[str, Tuple[int, ...]]:
+    D, F, M = c["d_model"], c["encoder_ffn_dim"], c["num_mel_bins"]
+    s = {"conv1.weight": (D, M, 3), "conv1.bias": (D,), "conv2.weight": (D, D, 3), "conv2.bias": (D,),
+         "embed_positions.weight": (c["max_source_positions"], D)}
+    for i in range(c["encoder_layers"]):
+        p = f"layers.{i}."
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            s[p + f"self_attn.{n}.weight"] = (D, D)
+            if n != "k_proj":                                   # Whisper's key projection has no bias
+                s[p + f"self_attn.{n}.bias"] = (D,)
+        s.update({p + "self_attn_layer_norm.weight": (D,), p + "self_attn_layer_norm.bias": (D,),
+                  p + "fc1.weight": (F, D), p + "fc1.bias": (F,), p + "fc2.weight": (D, F), p + "fc2.bias": (D,),
+                  p + "final_layer_norm.weight": (D,), p + "final_layer_norm.bias": (D,)})
+    s.update({"layer_norm.weight": (D,), "layer_norm.bias": (D,)})
+    return s
+
+
+def whisper_encoder_state_dict(c: dict, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded encoder weights under WhisperEncoder's names: LayerNorm weights spread around 1, query / key weights wide enough for a
+    non-uniform attention, every bias non-zero."""
+    out = {}
+    for name, shape in whisper_encoder_shapes(c).items():
+        leaf = name.split(".")[-1]
+        if "layer_norm" in name:
+            std, mean = (0.1, 1.0) if leaf == "weight" else (0.05, 0.0)
+        elif leaf == "bias":
+            std, mean = 0.02, 0.0
+        elif "q_proj" in name or "k_proj" in name:
+            std, mean = 0.06, 0.0
+        elif name.startswith("embed_positions") or name.startswith("conv1"):
+            std, mean = 0.05, 0.0
+        else:
+            std, mean = 0.03, 0.0
+        out[name] = tensor("whisper." + name, shape, std, seed, mean)
+    return out
+
+
+def whisper_mel_input(c: dict, clips: int, seed: int) -> torch.Tensor:
+    """A mel-like encoder input [clips, num_mel_bins, 2 * max_source_positions], uniform in [-0.7, 1.3) (a log-mel spectrogram's range)."""
+    shape = (clips, c["num_mel_bins"], 2 * c["max_source_positions"])
+    return torch.from_numpy((uniform_pm1("whisper.mel", int(np.prod(shape)), seed) + 0.3).astype(np.float32).reshape(shape))
+
+
+# the log-mel cases of tests/golden/whisper_mel.npz: case -> (kind, samples, padding)
+AUDIO_CASES = {"silence": ("silence", 1600, 0), "tone_noise": ("tone_noise", 1000, 0), "noise": ("noise", 16000, 0),
+               "click": ("click", 8000, 0), "mixed": ("mixed", 330000, 150000)}
+
+
+def audio_clip(kind: str, n: int, seed: int) -> np.ndarray:
+    """n seeded float32 samples of 16 kHz mono audio.  The sine of the tone is rounded to the PCM16 grid, so a last-bit difference between
+    two libm builds cannot reach the samples; everything else is exact arithmetic on uniform_pm1."""
+    t = np.arange(n, dtype=np.float64)
+    noise = uniform_pm1(f"audio.{kind}", n, seed)
+    tone = np.round(0.5 * np.sin(2.0 * np.pi * 440.0 * t / 16000.0) * 32768.0) / 32768.0
+    if kind == "silence":
+        x = np.zeros(n)
+    elif kind == "tone_noise":
+        x = tone + 0.1 * noise
+    elif kind == "noise":
+        x = 0.3 * noise
+    elif kind == "click":                      # one full-scale sample in noise so low that most of the spectrogram sits on the max - 8 clamp
+        x = 5e-6 * noise
+        x[n // 2] = 1.0
+    elif kind == "mixed":                      # 7 s of tone, then noise, then near-silence
+        a, b = min(n, 7 * 16000), min(n, 14 * 16000)
+        x = np.concatenate([tone[:a] + 0.01 * noise[:a], 0.2 * noise[a:b], 1e-4 * noise[b:]])
+    else:
+        raise ValueError(f"unknown audio kind {kind!r}")
+    return x.astype(np.float32)

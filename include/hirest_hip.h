@@ -1214,6 +1214,25 @@ typedef struct hirest_batch_args {
 } hirest_batch_args;
 int hirest_batch_assemble(const hirest_batch_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Whisper audio path (csrc/audio.hip, hirest_amd/whisper.py): everything in front of the encoder's first block.  The blocks themselves
+ * are hirest_gemm_f32 / hirest_gemm_f32_ln / hirest_attention_f32 / hirest_layernorm calls.
+ * ------------------------------------------------------------------------------------ */
+/* whisper/audio.py::log_mel_spectrogram on a mono 16 kHz fp32 waveform of n device samples followed by `padding` zeros: frames of 400
+ * samples at hop 160, centred with 200 samples of reflect padding (n + padding > 200), periodic Hann window, 400-point real DFT, power
+ * over 201 bins, filters [n_mels, 201] fp32, log10(max(x, 1e-10)), clamp at the maximum of the WHOLE call - 8, (x + 4) / 4.
+ * out [n_mels, (n + padding) / 160] fp32 (the transform's last frame is dropped, as Whisper does).  tables: 1200 device doubles, cos(2 pi i / 400)
+ * [400] | sin(2 pi i / 400) [400] | 0.5 - 0.5 cos(2 pi i / 400) [400], computed in double on the host.  The DFT and mel sums are
+ * accumulated in double and rounded to fp32 at the log.  The workspace holds one maximum per block of frames; results are the same bits
+ * on every run (no atomics). */
+size_t hirest_log_mel_workspace_bytes(int64_t n, int64_t padding);
+int hirest_log_mel(const float* audio, int64_t n, int64_t padding, const float* filters, int32_t n_mels, const double* tables,
+                   float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* mel [B, n_mels, T] -> rows [B, T + 2, n_mels]: channel-last, one zero row before and one after each clip (the padding of Whisper's two
+ * k = 3 convolutions, which then are hirest_gemm_f32 products over an overlapping view of the rows: A[m, k] = rows[m * stride * C + k],
+ * K = 3 C). */
+int hirest_mel_to_rows(const float* mel, float* rows, int32_t B, int32_t n_mels, int32_t T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

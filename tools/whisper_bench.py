@@ -1,0 +1,95 @@
+#!/usr/bin/env python3
+"""Throughput of the Whisper audio path at small.en's shape (768 wide, 12 heads, 12 layers, 1500 tokens; synthetic weights): 30 s
+windows per second through ``log_mel_spectrogram`` + ``AudioEncoder.forward`` for 1 and 8 windows per call, the split between the
+front end, the convolution stem and the blocks (each timed on its own, a device synchronise closing every timed window), and the
+encoder's rate as a fraction of the 157-TFLOP/s fp32 MFMA peak DESIGN.md uses for the joint model.  Operations are counted from the
+shapes.  Each figure is the median with the min .. max spread over the repeats.
+
+    python tools/whisper_bench.py [--repeats 7] [--warmup 2] [--batches 1 8]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from hirest_amd import synth, whisper  # noqa: E402
+
+FP32_MFMA_PEAK = 157e12
+
+
+def spread(xs, scale=1e3, unit="ms"):
+    return f"{statistics.median(xs) * scale:.3f} {unit} ({min(xs) * scale:.3f} .. {max(xs) * scale:.3f})"
+
+
+def encoder_flop(c):
+    """(stem, blocks) multiply-adds x 2 of one window, from the shapes"""
+    D, F, L, H, ctx, M = (c[k] for k in ("d_model", "encoder_ffn_dim", "encoder_layers", "encoder_attention_heads", "max_source_positions",
+                                         "num_mel_bins"))
+    stem = 2 * (2 * ctx) * (3 * M) * D + 2 * ctx * (3 * D) * D
+    block = 2 * ctx * D * 3 * D + 2 * 2 * ctx * ctx * D + 2 * ctx * D * D + 2 * 2 * ctx * D * F
+    return stem, L * block
+
+
+def timed(fn, repeats, warmup, min_window=0.25):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    inner = max(1, int(min_window / max(time.perf_counter() - t0, 1e-6)))      # enough calls per window to time the kernels, not the clock
+    out = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        for _ in range(inner):
+            fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) / inner)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 8])
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("whisper_bench needs an MI355X: there is nothing to measure without one")
+    dev = torch.device("cuda:0")
+    cfg = synth.WHISPER_SMALL_EN
+    enc = whisper.AudioEncoder(cfg, synth.whisper_encoder_state_dict(cfg, 73)).to(dev)
+    audio = torch.from_numpy(synth.audio_clip("mixed", whisper.N_SAMPLES, 71)).to(dev)
+    stem_flop, block_flop = encoder_flop(cfg)
+    front = timed(lambda: whisper.log_mel_spectrogram(audio), a.repeats, a.warmup)
+    print(f"{torch.cuda.get_device_name(0)}, small.en's encoder shape, {a.repeats} repeats after {a.warmup} warm-up calls")
+    print(f"front end, one 30 s window (resident waveform -> [80, 3000])   {spread(front)}")
+    result = {"device": torch.cuda.get_device_name(0), "front_end_ms": [round(x * 1e3, 4) for x in front], "batches": {}}
+    mel1 = whisper.log_mel_spectrogram(audio)
+    for B in a.batches:
+        mel = mel1[None].expand(B, -1, -1).contiguous()
+        stem = timed(lambda: enc(mel, return_stem=True), a.repeats, a.warmup)
+        whole = timed(lambda: enc(mel), a.repeats, a.warmup)
+        t_front, t_stem, t_whole = (statistics.median(x) for x in (front, stem, whole))
+        t_blocks = t_whole - t_stem
+        per_window = t_front + t_whole / B
+        print(f"B = {B}: encoder {spread(whole)}, of which stem {spread(stem)}")
+        print(f"        windows/s {1.0 / per_window:.1f} with one front-end call per window; shares: front end {t_front / per_window:.3f}, "
+              f"stem {t_stem / B / per_window:.3f}, blocks {t_blocks / B / per_window:.3f}")
+        print(f"        encoder {B * (stem_flop + block_flop) / t_whole / 1e12:.1f} TFLOP/s = {B * (stem_flop + block_flop) / t_whole / FP32_MFMA_PEAK:.3f} of the "
+              f"fp32 MFMA peak (stem {B * stem_flop / t_stem / 1e12:.1f}, blocks {B * block_flop / t_blocks / 1e12:.1f} TFLOP/s); a whole-call "
+              "rate, launches and row operations included")
+        result["batches"][str(B)] = {"encoder_ms": [round(x * 1e3, 4) for x in whole], "stem_ms": [round(x * 1e3, 4) for x in stem],
+                                     "windows_per_s": 1.0 / per_window, "front_end_share": t_front / per_window,
+                                     "encoder_tflops": B * (stem_flop + block_flop) / t_whole / 1e12,
+                                     "fraction_of_fp32_mfma_peak": B * (stem_flop + block_flop) / t_whole / FP32_MFMA_PEAK}
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
