@@ -99,6 +99,29 @@ class CaptionDecoder(C.Structure):
                [(n, C.c_void_p) for n in ("tr_w", "tr_b", "tr_ln_g", "tr_ln_b", "lm_w", "lm_b", "lm_w2")]
 
 
+class WhisperLayer(C.Structure):
+    """hirest_whisper_layer (include/hirest_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("attn_ln_g", "attn_ln_b", "qkv_w", "qkv_b", "so_w", "so_b", "cross_ln_g", "cross_ln_b", "cq_w", "cq_b",
+                                          "co_w", "co_b", "mlp_ln_g", "mlp_ln_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+
+
+class WhisperDecoder(C.Structure):
+    """hirest_whisper_decoder (include/hirest_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("layers", "heads", "hidden", "inter", "vocab_padded", "max_pos")] + \
+               [(n, C.c_void_p) for n in ("tok_emb", "pos_emb")] + [("layer", C.POINTER(WhisperLayer))] + \
+               [(n, C.c_void_p) for n in ("ln_g", "ln_b", "lm_b")]
+
+
+class WhisperTailParams(C.Structure):
+    """hirest_whisper_tail_params (include/hirest_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_vocab", "eot", "no_speech", "no_timestamps", "timestamp_begin", "max_initial_timestamp_index",
+                                         "sample_begin", "blank", "suppress_blank", "timestamp_rules", "monotonic")] + \
+               [("temperature", C.c_float), ("seed", C.c_uint32), ("serial", C.c_uint32), ("suppress_mask", C.c_void_p)]
+
+
+WHISPER_ROW_STATE_WORDS = 8      # hirest_whisper_row_state: n_sampled, last, penult, last_timestamp, completed | sum_logprobs, no_speech_prob, last_logprob
+
+
 class JointLayerX3(C.Structure):
     """hirest_joint_layer_x3 (include/hirest_hip.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("qkv_w2", "qkv_b", "ao_w2", "ao_b", "ln1_g", "ln1_b", "fc1_w2", "fc1_b", "fc2_w2", "fc2_b", "ln2_g", "ln2_b")]
@@ -407,6 +430,19 @@ _SIGNATURES = {
     "hirest_log_mel": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),
     "hirest_mel_to_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "hirest_attention_f32_decode_inplace": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                                      C.c_float, C.c_void_p]),
+    "hirest_attention_f32_cross_decode_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "hirest_attention_f32_cross_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                                    C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hirest_whisper_step_tail": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(WhisperTailParams),
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hirest_whisper_gumbel_bits": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "hirest_whisper_step_workspace_bytes": (C.c_size_t, [C.POINTER(WhisperDecoder), C.c_int32, C.c_int32]),
+    "hirest_whisper_decode_step": (C.c_int, [C.POINTER(WhisperDecoder), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hirest_vision_workspace_bytes": (C.c_size_t, [C.POINTER(VisionTower), C.c_int32]),
     "hirest_vision_forward": (C.c_int, [C.POINTER(VisionTower), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),

@@ -109,3 +109,12 @@ class ByteBPETokenizer:
 
     def encode_batch(self, texts: Sequence[str], max_seq_length: int = 512) -> List[List[int]]:
         return [self.encode(t, max_seq_length) for t in texts]
+
+    def decode(self, ids: Iterable[int]) -> str:
+        """ids -> text: the symbols' characters mapped back to bytes, decoded as UTF-8 (malformed sequences become U+FFFD).  Ids without
+        a symbol raise KeyError."""
+        if not hasattr(self, "_sym"):
+            self._sym = {i: s for s, i in self.vocab.items()}
+            self._unbyte = {c: b for b, c in self._byte.items()}
+        chars = "".join(self._sym[int(i)] for i in ids)
+        return bytes(self._unbyte[c] for c in chars).decode("utf-8", errors="replace")

@@ -1405,8 +1405,13 @@ struct AttnDec {
     float* k_out; float* v_out;
     float* out;
     int H; float scale, add_const, causal_penalty;
+    int64_t hist_row;          // floats between two rows' histories: t_hist * ld_hist when packed, T_max * ld_hist for a preallocated cache
 };
 
+// INPLACE: the history is a preallocated [R, T_max, ld_hist] cache (parent unused, k_out / v_out = the cache itself): the newest key /
+// value is appended at position t_hist instead of the whole history being written out again.  Position t_hist is read from k_new /
+// v_new only, never from the cache, and a block writes its own (row, head) slice: no ordering between the append and any read.
+template <bool INPLACE>
 __global__ __launch_bounds__(64) void attention_f32_decode_kernel(AttnDec p) {
     constexpr int KLD = 68;
     __shared__ __attribute__((aligned(16))) float Ks[64 * KLD];
@@ -1414,7 +1419,7 @@ __global__ __launch_bounds__(64) void attention_f32_decode_kernel(AttnDec p) {
     const int lane = threadIdx.x;
     const int r = blockIdx.x / p.H, h = blockIdx.x - r * p.H;
     const int D = p.H * 64, T = p.t_hist + (p.k_new ? 1 : 0);
-    const int64_t src = p.parent ? p.parent[r] : r;
+    const int64_t src = !INPLACE && p.parent ? p.parent[r] : r;
     Qs[lane] = p.q[(int64_t)r * p.ldq + h * 64 + lane];
     float mrun = -3.0e38f, lrun = 0.f, o = 0.f;
     for (int k0 = 0; k0 < T; k0 += 64) {
@@ -1427,18 +1432,28 @@ __global__ __launch_bounds__(64) void attention_f32_decode_kernel(AttnDec p) {
 #pragma unroll
         for (int ps = 0; ps < 16; ++ps) {
             const int key = k0 + ps * 4 + (lane >> 4), kk = key < T ? key : T - 1;
-            const float* kp = kk < p.t_hist ? p.k_hist + (src * p.t_hist + kk) * p.ld_hist : p.k_new + (int64_t)r * p.ld_new;
+            const float* kp = kk < p.t_hist ? p.k_hist + src * p.hist_row + kk * p.ld_hist : p.k_new + (int64_t)r * p.ld_new;
             kreg[ps] = *reinterpret_cast<const f32x4*>(kp + h * 64 + 4 * (lane & 15));
         }
 #pragma unroll
         for (int j = 0; j < 64; ++j) {
             const int key = k0 + j, kk = key < T ? key : T - 1;
-            const float* vp = kk < p.t_hist ? p.v_hist + (src * p.t_hist + kk) * p.ld_hist : p.v_new + (int64_t)r * p.ld_new;
+            const float* vp = kk < p.t_hist ? p.v_hist + src * p.hist_row + kk * p.ld_hist : p.v_new + (int64_t)r * p.ld_new;
             vv[j] = vp[h * 64 + lane];
         }
 #pragma unroll
         for (int ps = 0; ps < 16; ++ps) *reinterpret_cast<f32x4*>(Ks + (ps * 4 + (lane >> 4)) * KLD + 4 * (lane & 15)) = kreg[ps];
-        if (p.k_out) {
+        if (INPLACE) {
+            if (p.t_hist >= k0 && p.t_hist < k0 + 64) {       // (uniform) the chunk that holds the newest position
+#pragma unroll
+                for (int ps = 0; ps < 16; ++ps)
+                    if (k0 + ps * 4 + (lane >> 4) == p.t_hist)
+                        *reinterpret_cast<f32x4*>(p.k_out + (int64_t)r * p.hist_row + (int64_t)p.t_hist * p.ld_hist + h * 64 + 4 * (lane & 15)) = kreg[ps];
+#pragma unroll
+                for (int j = 0; j < 64; ++j)
+                    if (k0 + j == p.t_hist) p.v_out[(int64_t)r * p.hist_row + (int64_t)p.t_hist * p.ld_hist + h * 64 + lane] = vv[j];
+            }
+        } else if (p.k_out) {
 #pragma unroll
             for (int ps = 0; ps < 16; ++ps) {
                 const int key = k0 + ps * 4 + (lane >> 4);
@@ -1957,8 +1972,21 @@ extern "C" int hirest_attention_f32_decode(const float* q, int64_t ldq, const fl
     if (!q || !out || R <= 0 || H <= 0 || t_hist < 0 || (t_hist > 0 && (!k_hist || !v_hist)) || (!k_new != !v_new) || (!k_out != !v_out)) return HIREST_E_BADARG;
     if (t_hist == 0 && !k_new) return HIREST_E_BADARG;
     if (ldq % 4 != 0 || ld_hist % 4 != 0 || ld_new % 4 != 0) return HIREST_E_SHAPE;
-    AttnDec p{q, ldq, k_hist, v_hist, ld_hist, parent, t_hist, k_new, v_new, ld_new, k_out, v_out, out, H, scale, add_const, causal_penalty};
-    hipLaunchKernelGGL(attention_f32_decode_kernel, dim3(R * H), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), p);
+    AttnDec p{q, ldq, k_hist, v_hist, ld_hist, parent, t_hist, k_new, v_new, ld_new, k_out, v_out, out, H, scale, add_const, causal_penalty,
+              (int64_t)t_hist * ld_hist};
+    hipLaunchKernelGGL(attention_f32_decode_kernel<false>, dim3(R * H), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), p);
+    return hirest_launch_status();
+}
+
+extern "C" int hirest_attention_f32_decode_inplace(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ld_cache, int64_t row_stride,
+                                                   int32_t t, int32_t T_max, const float* k_new, const float* v_new, int64_t ld_new, float* out,
+                                                   int32_t R, int32_t H, float scale, float add_const, float causal_penalty, void* stream) {
+    if (!q || !out || !k_cache || !v_cache || !k_new || !v_new || R <= 0 || H <= 0 || t < 0 || T_max <= 0) return HIREST_E_BADARG;
+    if (t >= T_max || ld_cache < (int64_t)H * 64 || row_stride < (int64_t)T_max * ld_cache) return HIREST_E_SHAPE;
+    if (ldq % 4 != 0 || ld_cache % 4 != 0 || ld_new % 4 != 0 || row_stride % 4 != 0) return HIREST_E_SHAPE;
+    AttnDec p{q, ldq, k_cache, v_cache, ld_cache, nullptr, t, k_new, v_new, ld_new, k_cache, v_cache, out, H, scale, add_const, causal_penalty,
+              row_stride};
+    hipLaunchKernelGGL(attention_f32_decode_kernel<true>, dim3(R * H), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), p);
     return hirest_launch_status();
 }
 

@@ -16,7 +16,7 @@ into the reference modules via ``load_state_dict`` and into this package's tower
 from __future__ import annotations
 
 import math
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -699,3 +699,122 @@ def audio_clip(kind: str, n: int, seed: int) -> np.ndarray:
     else:
         raise ValueError(f"unknown audio kind {kind!r}")
     return x.astype(np.float32)
+
+
+# ----------------------------------------------------------------------------------
+# Whisper's text decoder in the Hugging Face WhisperDecoder schema (tests/golden/whisper_dec_*.npz).  The vocabularies follow small.en's
+# layout: text ids, then eot, sot, the task and marker tokens, <|notimestamps|>, and the timestamp tokens up to the end.
+# p: one ragged key chunk; q: several chunks with a ragged last one; r: the real key count and vocabulary width, one layer.
+# ----------------------------------------------------------------------------------
+
+def _dec_config(d, heads, layers, audio_ctx, vocab, text_ctx):
+    return {"num_mel_bins": 80, "d_model": d, "encoder_attention_heads": heads, "encoder_layers": 1, "encoder_ffn_dim": 4 * d,
+            "max_source_positions": audio_ctx, "decoder_attention_heads": heads, "decoder_layers": layers, "decoder_ffn_dim": 4 * d,
+            "vocab_size": vocab, "max_target_positions": text_ctx}
+
+
+def whisper_special_tokens(eot: int) -> Dict[str, int]:
+    """small.en's special-token layout shifted to a vocabulary whose text ids end at ``eot`` (50256 there): 99 language slots are kept only at
+    the real size, so timestamp_begin = eot + 107 at 50256 and eot + 12 otherwise."""
+    base = eot + 1 + (99 if eot == 50256 else 4)
+    return {"<|endoftext|>": eot, "<|startoftranscript|>": eot + 1, "<|translate|>": base + 1, "<|transcribe|>": base + 2,
+            "<|startoflm|>": base + 3, "<|startofprev|>": base + 4, "<|nospeech|>": base + 5, "<|notimestamps|>": base + 6}
+
+
+WHISPER_DEC_P = _dec_config(128, 2, 2, 33, 200, 48)
+WHISPER_DEC_Q = _dec_config(128, 2, 2, 261, 200, 48)
+WHISPER_DEC_R = _dec_config(256, 4, 1, 1500, 51864, 32)
+# case -> (config, eot, decoder seed, windows)
+WHISPER_DEC_CASES = {"p": (WHISPER_DEC_P, 100, 81, 1), "q": (WHISPER_DEC_Q, 100, 82, 2), "r": (WHISPER_DEC_R, 50256, 83, 1)}
+
+
+def whisper_decoder_shapes(c: dict) -> Dict[str, Tuple[int, ...]]:
+    D, F = c["d_model"], c["decoder_ffn_dim"]
+    s = {"embed_tokens.weight": (c["vocab_size"], D), "embed_positions.weight": (c["max_target_positions"], D)}
+    for i in range(c["decoder_layers"]):
+        p = f"layers.{i}."
+        for a in ("self_attn", "encoder_attn"):
+            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+                s[p + f"{a}.{n}.weight"] = (D, D)
+                if n != "k_proj":
+                    s[p + f"{a}.{n}.bias"] = (D,)
+            s[p + f"{a}_layer_norm.weight"] = s[p + f"{a}_layer_norm.bias"] = (D,)
+        s.update({p + "fc1.weight": (F, D), p + "fc1.bias": (F,), p + "fc2.weight": (D, F), p + "fc2.bias": (D,),
+                  p + "final_layer_norm.weight": (D,), p + "final_layer_norm.bias": (D,)})
+    s.update({"layer_norm.weight": (D,), "layer_norm.bias": (D,)})
+    return s
+
+
+def whisper_decoder_state_dict(c: dict, seed: int, eot: Optional[int] = None, eot_bias: float = 0.0) -> Dict[str, torch.Tensor]:
+    """Seeded decoder weights under ``decoder.`` + WhisperDecoder's names.  The embedding (also the LM head) is wide enough for logits
+    that differ by whole units.  ``eot_bias`` adds that multiple of the final LayerNorm's bias direction to the eot embedding, which moves
+    the eot logit of every position by about the same amount: how a fixture is made to end by eot."""
+    out = {}
+    for name, shape in whisper_decoder_shapes(c).items():
+        leaf = name.split(".")[-1]
+        if "layer_norm" in name:
+            std, mean = (0.1, 1.0) if leaf == "weight" else (0.05, 0.0)
+        elif leaf == "bias":
+            std, mean = 0.02, 0.0
+        elif "q_proj" in name or "k_proj" in name:
+            std, mean = 0.06, 0.0
+        elif name.startswith("embed_tokens"):
+            std, mean = 0.08, 0.0
+        elif name.startswith("embed_positions"):
+            std, mean = 0.05, 0.0
+        else:
+            std, mean = 0.03, 0.0
+        out["decoder." + name] = tensor("whisper.dec." + name, shape, std, seed, mean)
+    if eot is not None and eot_bias != 0.0:
+        b = out["decoder.layer_norm.bias"]
+        out["decoder.embed_tokens.weight"][eot] += eot_bias * b / float((b * b).sum())
+    return out
+
+
+def whisper_audio_states(c: dict, windows: int, seed: int) -> torch.Tensor:
+    """Encoder-state-like decoder input [windows, max_source_positions, d_model] (LayerNorm output scale)"""
+    return tensor("whisper.dec.xa", (windows, c["max_source_positions"], c["d_model"]), 1.0, seed)
+
+
+def whisper_vocab(eot: int) -> Tuple[Dict[str, int], list]:
+    """A byte-level vocabulary of ``eot`` text ids for the tokenizer tests: the 256 byte symbols first when they fit (else the printable
+    ASCII ones), then a few merges."""
+    from .bytebpe import bytes_to_unicode
+    alphabet = list(bytes_to_unicode().values())
+    if eot < 300:
+        table = bytes_to_unicode()
+        alphabet = [table[b] for b in list(range(32, 127))]
+    vocab = {s: i for i, s in enumerate(alphabet)}
+    sp = bytes_to_unicode()[ord(" ")]
+    merges = []
+    for a, b in ((sp, "-"), (sp, "'"), ("t", "h"), ("th", "e"), (sp, "the"), (sp, "a"), ("i", "n")):
+        if a in vocab and b in vocab and a + b not in vocab and len(vocab) < eot:
+            vocab[a + b] = len(vocab)
+            merges.append(f"{a} {b}")
+    return vocab, merges
+
+
+# added to the eot embedding along the final LayerNorm's bias (whisper_decoder_state_dict): case p's greedy fixtures end by eot, case q's
+# run to sample_len
+WHISPER_DEC_EOT_BIAS = {"p": 0.5, "q": 0.0, "r": 0.0}
+
+
+def token_ids(name: str, n: int, vocab: int, seed: int) -> np.ndarray:
+    """n seeded ids in [0, vocab)"""
+    return np.minimum(((uniform_pm1(name, n, seed) + 1.0) * 0.5 * vocab).astype(np.int64), vocab - 1)
+
+
+def whisper_tokenizer(eot: int):
+    """The synthetic Whisper tokenizer of a decoder case: whisper_vocab + whisper_special_tokens"""
+    from .whisper import Tokenizer
+    vocab, merges = whisper_vocab(eot)
+    return Tokenizer(vocab, merges, whisper_special_tokens(eot))
+
+
+def whisper_tail_consts(c: dict, eot: int) -> dict:
+    """What decode() derives from that tokenizer and the default options: the ids the logit filters use"""
+    tok = whisper_tokenizer(eot)
+    suppress = sorted(set(tok.non_speech_tokens) | {tok.transcribe, tok.translate, tok.sot, tok.sot_prev, tok.sot_lm, tok.no_speech})
+    return {"n_vocab": c["vocab_size"], "eot": tok.eot, "no_speech": tok.no_speech, "no_timestamps": tok.no_timestamps,
+            "timestamp_begin": tok.timestamp_begin, "max_initial_timestamp_index": int(round(1.0 / (30.0 / c["max_source_positions"]))),
+            "blank": tok.encode(" ")[0], "suppress": suppress}

@@ -1,4 +1,5 @@
-"""Whisper's audio path on MI355X: the log-mel front end and the audio encoder, under Whisper's own names.
+"""Whisper on MI355X under Whisper's own names: the log-mel front end and the audio encoder, and (further down) the text
+decoder, the tokenizer, ``decode()``, ``transcribe()`` and ``.srt`` writing.
 
 The reference transcribes every video's audio with ``whisper.load_model('small.en')`` (extraction/whisper_ASR/extract_ASR.py) before
 the subtitles are embedded.  This module is the lower half of that stage, the part with the arithmetic (12 pre-LN layers over 1500
@@ -7,7 +8,8 @@ tokens, 0.34 TFLOP per 30 s window) and the part Whisper's users call directly::
     whisper.load_audio / pad_or_trim / log_mel_spectrogram        ->  the same names here
     model.embed_audio(mel) / model.encoder(mel)                   ->  AudioEncoder.embed_audio / AudioEncoder.forward
 
-The text decoder, the tokenizer, ``transcribe()`` with its temperature fallback and ``.srt`` writing are not built.
+    whisper.load_model / model.decode / whisper.transcribe / utils.write_srt  ->  the same names here (sampling branch; no beam search)
+
 Whisper is not under the reference tree; the front end restates ``whisper/audio.py`` and the encoder ``whisper/model.py::AudioEncoder``
 from the published definitions, pinned against ``transformers``' WhisperFeatureExtractor / WhisperEncoder (tests/golden/whisper_*.npz).
 
@@ -21,17 +23,23 @@ the positional embedding in its epilogue, after the GELU.  The blocks run on the
 """
 from __future__ import annotations
 
+import ctypes as C
+import dataclasses
 import functools
 import json
 import os
+import re
+import types
 import wave
-from typing import Dict, Optional, Union
+import zlib
+from typing import Dict, Iterable, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from .bytebpe import ByteBPETokenizer
 from .sentence_encoder import _AH_MAX, _load_weights
 
 SAMPLE_RATE = 16000
@@ -42,6 +50,7 @@ N_SAMPLES = CHUNK_LENGTH * SAMPLE_RATE          # 480000 samples in a 30-second 
 N_FRAMES = N_SAMPLES // HOP_LENGTH              # 3000 frames in a mel spectrogram input
 
 _NAME = "hirest_amd.whisper"
+_TIMESTAMP = re.compile(r"<\|\d+\.\d\d\|>")
 
 
 def load_audio(path: str, sr: int = SAMPLE_RATE) -> np.ndarray:
@@ -419,3 +428,762 @@ def encode_file(path: str, encoder: AudioEncoder) -> torch.Tensor:
     n_windows = max(1, -(-content // N_FRAMES))
     windows = torch.stack([mel[:, w * N_FRAMES:(w + 1) * N_FRAMES] for w in range(n_windows)])
     return encoder(windows)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the text decoder
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+_CAUSAL_PENALTY = -1.0e30      # added to scores of future keys in prefill: exp() of it is exactly 0 against any fp32 score, no overflow
+
+
+def _dec_dims(d) -> Dict[str, int]:
+    """OpenAI ``ModelDimensions`` (n_vocab, n_text_ctx, n_text_state, n_text_head, n_text_layer) or a Hugging Face Whisper ``config.json``
+    dict -> the decoder's sizes."""
+    get = (lambda k, default=None: d.get(k, default)) if isinstance(d, dict) else (lambda k, default=None: getattr(d, k, default))
+    if get("n_text_state") is not None:
+        width = int(get("n_text_state"))
+        return {"vocab": int(get("n_vocab")), "ctx": int(get("n_text_ctx")), "width": width, "heads": int(get("n_text_head")),
+                "layers": int(get("n_text_layer")), "ffn": 4 * width}
+    if get("d_model") is not None:
+        if get("activation_function", "gelu") != "gelu":
+            raise NotImplementedError(f"activation {get('activation_function')!r}: Whisper's erf GELU is what is built")
+        width = int(get("d_model"))
+        return {"vocab": int(get("vocab_size")), "ctx": int(get("max_target_positions")), "width": width,
+                "heads": int(get("decoder_attention_heads")), "layers": int(get("decoder_layers")),
+                "ffn": int(get("decoder_ffn_dim", 4 * width))}
+    raise ValueError("neither Whisper's ModelDimensions (n_text_state ...) nor a Hugging Face Whisper config (d_model ...)")
+
+
+# the decoder's table beside the encoder's (_HF_TO_OPENAI): Hugging Face WhisperDecoder names -> OpenAI's, applied in this order
+_HF_TO_OPENAI_DEC = (("embed_tokens.weight", "token_embedding.weight"), ("embed_positions.weight", "positional_embedding"),
+                     ("layers.", "blocks."), ("encoder_attn_layer_norm", "cross_attn_ln"), ("self_attn_layer_norm", "attn_ln"),
+                     ("final_layer_norm", "mlp_ln"), ("encoder_attn.q_proj", "cross_attn.query"), ("encoder_attn.k_proj", "cross_attn.key"),
+                     ("encoder_attn.v_proj", "cross_attn.value"), ("encoder_attn.out_proj", "cross_attn.out"),
+                     ("self_attn.q_proj", "attn.query"), ("self_attn.k_proj", "attn.key"), ("self_attn.v_proj", "attn.value"),
+                     ("self_attn.out_proj", "attn.out"), ("fc1", "mlp.0"), ("fc2", "mlp.2"))
+
+
+def _canonical_decoder(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Either schema's decoder tensors under OpenAI's names without the ``decoder.`` prefix; everything else is dropped."""
+    out = {}
+    for k, v in state_dict.items():
+        if k.startswith("model."):
+            k = k[len("model."):]
+        if not k.startswith("decoder."):
+            continue
+        k = k[len("decoder."):]
+        if k.startswith("layers.") or k.startswith("embed_") or k.startswith("layer_norm."):
+            for a, b in _HF_TO_OPENAI_DEC:
+                k = k.replace(a, b)
+            if k.startswith("layer_norm."):
+                k = "ln." + k[len("layer_norm."):]
+        out[k] = v
+    return out
+
+
+class KVCache:
+    """What a decoding loop keeps between steps: per layer the preallocated self-attention cache ``[R, T_max, D]`` (key, value), the
+    cross-attention ``key(xa) | value(xa)`` rows ``[n_windows, Tk, 2 D]``, ``row_window [R]`` and the number of filled positions."""
+
+    def __init__(self, decoder: "TextDecoder", xa: torch.Tensor, row_window: torch.Tensor, T_max: Optional[int] = None):
+        dev, D = xa.device, decoder.width
+        self.R, self.T_max, self.length = int(row_window.numel()), int(T_max or decoder.ctx), 0
+        self.n_windows, self.Tk = int(xa.shape[0]), int(xa.shape[1])
+        self.row_window = row_window.to(dev, torch.int32).contiguous()
+        self.self_k = [torch.empty((self.R, self.T_max, D), dtype=torch.float32, device=dev) for _ in range(decoder.layers)]
+        self.self_v = [torch.empty((self.R, self.T_max, D), dtype=torch.float32, device=dev) for _ in range(decoder.layers)]
+        self.cross_kv = decoder.cross_kv(xa)
+        P = C.c_void_p * decoder.layers
+        self.k_ptrs, self.v_ptrs = P(*(t.data_ptr() for t in self.self_k)), P(*(t.data_ptr() for t in self.self_v))
+        self.x_ptrs = P(*(t.data_ptr() for t in self.cross_kv))
+        self.logits = torch.empty((self.R, decoder.vocab_padded), dtype=torch.float32, device=dev)
+        need = _lib.load().hirest_whisper_step_workspace_bytes(C.byref(decoder._w()["desc"]), self.R, self.Tk)
+        self.ws = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=dev)
+
+
+class TextDecoder(nn.Module):
+    """``whisper.model.TextDecoder``: token + learned positional embedding, pre-LN blocks (self-attention, cross-attention over the audio
+    encoder's states, MLP), ``ln``, the tied-embedding LM head.  ``dims_or_config`` / ``state_dict`` as ``AudioEncoder``'s (either schema).
+
+    ``forward(tokens, xa)`` runs whole sequences (teacher forcing, a window's prompt) through the full-sequence kernels.  With a
+    ``KVCache`` it fills the cache from a prompt shared by all rows (``tokens [1, T]`` or ``[T]``; the cache rows are broadcast) or, once
+    the cache holds positions, takes one new token per row (``tokens [R, 1]``) through ``hirest_whisper_decode_step``."""
+
+    def __init__(self, dims_or_config, state_dict: Dict[str, torch.Tensor]):
+        super().__init__()
+        self.dims = _dec_dims(dims_or_config)
+        d = self.dims
+        self.vocab, self.ctx, self.width, self.heads, self.layers, self.ffn = (d[k] for k in ("vocab", "ctx", "width", "heads", "layers", "ffn"))
+        if self.width != 64 * self.heads:
+            raise NotImplementedError(f"width {self.width} / heads {self.heads}: 64-wide heads (every Whisper size) are what is built")
+        if self.ffn % 16:
+            raise NotImplementedError(f"ffn {self.ffn}: a multiple of 16 expected")
+        self.vocab_padded = (self.vocab + 3) // 4 * 4
+        self.eps = 1e-5
+        sd = _canonical_decoder(state_dict)
+        D, I = self.width, self.ffn
+        want = {"token_embedding.weight": (self.vocab, D), "positional_embedding": (self.ctx, D), "ln.weight": (D,), "ln.bias": (D,)}
+        for i in range(self.layers):
+            p = f"blocks.{i}."
+            for a in ("attn", "cross_attn"):
+                for n in ("query", "key", "value", "out"):
+                    want[p + f"{a}.{n}.weight"] = (D, D)
+                    if n != "key":
+                        want[p + f"{a}.{n}.bias"] = (D,)
+                want[p + f"{a}_ln.weight"] = want[p + f"{a}_ln.bias"] = (D,)
+            want.update({p + "mlp_ln.weight": (D,), p + "mlp_ln.bias": (D,), p + "mlp.0.weight": (I, D), p + "mlp.0.bias": (I,),
+                         p + "mlp.2.weight": (D, I), p + "mlp.2.bias": (D,)})
+        for k, shape in want.items():
+            if k not in sd:
+                raise KeyError(f"TextDecoder: {k} missing from the state dict")
+            if tuple(sd[k].shape) != shape:
+                raise ValueError(f"TextDecoder: {k} has shape {tuple(sd[k].shape)}, expected {shape}")
+            self.register_parameter(k.replace(".", "/"), nn.Parameter(sd[k].detach().float().clone(), requires_grad=False))
+        self._cache = None
+
+    def _apply(self, fn, *a, **k):
+        self._cache = None
+        return super()._apply(fn, *a, **k)
+
+    def _p(self, name: str) -> torch.Tensor:
+        return self._parameters[name.replace(".", "/")]
+
+    @property
+    def device(self) -> torch.device:
+        return self._p("ln.weight").device
+
+    def prepared_weights(self) -> Dict[str, object]:
+        """The operands the kernels read: fused query | key | value (zero key bias), fused cross key | value, the embedding zero-padded to a
+        multiple of 4 rows (also the LM head) with a zero bias, and the C descriptor over them (``desc``)."""
+        f = lambda n: self._p(n).detach().float().contiguous()
+        D, dev = self.width, self.device
+        z = torch.zeros(D, device=dev)
+        emb = torch.zeros((self.vocab_padded, D), device=dev)
+        emb[:self.vocab] = f("token_embedding.weight")
+        c = {"tok": emb, "pos": f("positional_embedding"), "ln_g": f("ln.weight"), "ln_b": f("ln.bias"),
+             "lm_b": torch.zeros(self.vocab_padded, device=dev)}
+        layers = (_lib.WhisperLayer * self.layers)()
+        for i in range(self.layers):
+            p = f"blocks.{i}."
+            c[f"qkv_w.{i}"] = torch.cat([f(p + f"attn.{n}.weight") for n in ("query", "key", "value")], 0).contiguous()
+            c[f"qkv_b.{i}"] = torch.cat([f(p + "attn.query.bias"), z, f(p + "attn.value.bias")], 0).contiguous()
+            c[f"ckv_w.{i}"] = torch.cat([f(p + "cross_attn.key.weight"), f(p + "cross_attn.value.weight")], 0).contiguous()
+            c[f"ckv_b.{i}"] = torch.cat([z, f(p + "cross_attn.value.bias")], 0).contiguous()
+            for n in ("attn.out.weight", "attn.out.bias", "attn_ln.weight", "attn_ln.bias", "cross_attn_ln.weight", "cross_attn_ln.bias",
+                      "cross_attn.query.weight", "cross_attn.query.bias", "cross_attn.out.weight", "cross_attn.out.bias", "mlp_ln.weight",
+                      "mlp_ln.bias", "mlp.0.weight", "mlp.0.bias", "mlp.2.weight", "mlp.2.bias"):
+                c[p + n] = f(p + n)
+            L = layers[i]
+            for field, key in (("attn_ln_g", p + "attn_ln.weight"), ("attn_ln_b", p + "attn_ln.bias"), ("qkv_w", f"qkv_w.{i}"), ("qkv_b", f"qkv_b.{i}"),
+                               ("so_w", p + "attn.out.weight"), ("so_b", p + "attn.out.bias"), ("cross_ln_g", p + "cross_attn_ln.weight"),
+                               ("cross_ln_b", p + "cross_attn_ln.bias"), ("cq_w", p + "cross_attn.query.weight"),
+                               ("cq_b", p + "cross_attn.query.bias"), ("co_w", p + "cross_attn.out.weight"), ("co_b", p + "cross_attn.out.bias"),
+                               ("mlp_ln_g", p + "mlp_ln.weight"), ("mlp_ln_b", p + "mlp_ln.bias"), ("fc1_w", p + "mlp.0.weight"),
+                               ("fc1_b", p + "mlp.0.bias"), ("fc2_w", p + "mlp.2.weight"), ("fc2_b", p + "mlp.2.bias")):
+                setattr(L, field, c[key].data_ptr())
+        desc = _lib.WhisperDecoder()
+        desc.layers, desc.heads, desc.hidden, desc.inter, desc.vocab_padded, desc.max_pos = (self.layers, self.heads, D, self.ffn, self.vocab_padded,
+                                                                                               self.ctx)
+        desc.tok_emb, desc.pos_emb, desc.layer = c["tok"].data_ptr(), c["pos"].data_ptr(), layers
+        desc.ln_g, desc.ln_b, desc.lm_b = c["ln_g"].data_ptr(), c["ln_b"].data_ptr(), c["lm_b"].data_ptr()
+        c["layers"], c["desc"] = layers, desc
+        return c
+
+    def _w(self):
+        if self._cache is None:
+            if self.device.type != "cuda":
+                raise RuntimeError(f"{_NAME}.TextDecoder runs on MI355X only (no CPU fallback); move the model to a GPU")
+            self._cache = self.prepared_weights()
+        return self._cache
+
+    def _linear(self, x, w, bias, act=0, resid=None):
+        out = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
+        AudioEncoder._gemm(x.data_ptr(), x.shape[1], w, bias, out.data_ptr(), w.shape[0], x.shape[0], x.device, act=act, resid=resid)
+        return out
+
+    def _ln_linear(self, x, gamma, beta, w, bias, act=0):
+        M, K = x.shape
+        N = w.shape[0]
+        if M <= 256 and K % 256 == 0 and K <= 1024 and (N < 8192 or (K == 768 and M <= 32)):
+            out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+            _lib.check(_lib.load().hirest_gemm_f32_ln(x.data_ptr(), K, None, None, None, gamma.data_ptr(), beta.data_ptr(), self.eps, None, 0,
+                                                      w.data_ptr(), K, bias.data_ptr(), None, 0, out.data_ptr(), N, M, N, K, act,
+                                                      ops.stream_ptr()), "hirest_gemm_f32_ln")
+            return out
+        return self._linear(ops.layernorm(x, gamma, beta, self.eps, torch.empty_like(x)), w, bias, act=act)
+
+    @torch.no_grad()
+    def cross_kv(self, xa: torch.Tensor):
+        """``xa [n_windows, Tk, D]`` -> per layer ``[n_windows, Tk, 2 D]``: the layer's ``key(xa) | value(xa)``, computed once per window"""
+        c = self._w()
+        W, Tk, D = xa.shape
+        rows = xa.to(self.device, torch.float32).contiguous().view(W * Tk, D)
+        with torch.cuda.device(self.device):
+            return [self._linear(rows, c[f"ckv_w.{i}"], c[f"ckv_b.{i}"]).view(W, Tk, 2 * D) for i in range(self.layers)]
+
+    def _sequences(self, tokens: torch.Tensor, cross_kv, Tk: int, keep=None):
+        """[B, T] tokens (sequence b against window b of cross_kv) -> [B * T, D] states before ``ln``; ``keep(i, qkv)`` sees every layer's
+        packed q | k | v rows (the prefill takes its cache rows from them)"""
+        c, lib = self._w(), _lib.load()
+        B, T = tokens.shape
+        D, H, dev = self.width, self.heads, self.device
+        ids = tokens.to(dev, torch.int32).contiguous().view(-1)
+        x = torch.empty((B * T, D), dtype=torch.float32, device=dev)
+        _lib.check(lib.hirest_embedding_fwd_f32(ids.data_ptr(), c["tok"].data_ptr(), c["pos"].data_ptr(), x.data_ptr(), B * T, T, D,
+                                                ops.stream_ptr()), "hirest_embedding_fwd_f32")
+        for i in range(self.layers):
+            p = f"blocks.{i}."
+            qkv = self._ln_linear(x, c[p + "attn_ln.weight"], c[p + "attn_ln.bias"], c[f"qkv_w.{i}"], c[f"qkv_b.{i}"])
+            if keep is not None:
+                keep(i, qkv)
+            att = torch.empty((B * T, D), dtype=torch.float32, device=dev)
+            _lib.check(lib.hirest_attention_f32_qkv(qkv.data_ptr(), 3 * D, qkv.data_ptr() + 4 * D, qkv.data_ptr() + 8 * D, 3 * D, att.data_ptr(), B, T,
+                                                    T, H, 64, 0.125, 0.0, _CAUSAL_PENALTY, ops.stream_ptr()), "hirest_attention_f32_qkv")
+            x = self._linear(att, c[p + "attn.out.weight"], c[p + "attn.out.bias"], resid=x)
+            q = self._ln_linear(x, c[p + "cross_attn_ln.weight"], c[p + "cross_attn_ln.bias"], c[p + "cross_attn.query.weight"],
+                                c[p + "cross_attn.query.bias"])
+            kv = cross_kv[i]
+            _lib.check(lib.hirest_attention_f32_qkv(q.data_ptr(), D, kv.data_ptr(), kv.data_ptr() + 4 * D, 2 * D, att.data_ptr(), B, T, Tk, H, 64,
+                                                    0.125, 0.0, 0.0, ops.stream_ptr()), "hirest_attention_f32_qkv")
+            x = self._linear(att, c[p + "cross_attn.out.weight"], c[p + "cross_attn.out.bias"], resid=x)
+            hid = self._ln_linear(x, c[p + "mlp_ln.weight"], c[p + "mlp_ln.bias"], c[p + "mlp.0.weight"], c[p + "mlp.0.bias"], act=1)
+            x = self._linear(hid, c[p + "mlp.2.weight"], c[p + "mlp.2.bias"], resid=x)
+        return x
+
+    def _head(self, x: torch.Tensor) -> torch.Tensor:
+        c = self._w()
+        return self._ln_linear(x, c["ln_g"], c["ln_b"], c["tok"], c["lm_b"])
+
+    @torch.no_grad()
+    def forward(self, tokens: torch.Tensor, xa: Optional[torch.Tensor], kv_cache: Optional[KVCache] = None) -> torch.Tensor:
+        """``tokens [B, T]``, ``xa [B, Tk, D]`` -> logits ``[B, T, n_vocab]``.  With ``kv_cache`` (``xa`` is then the cache's own): an empty
+        cache takes the shared prompt ``[1, T]`` and returns ``[1, T, n_vocab]``; a filled one takes ``[R, 1]`` and returns ``[R, 1, n_vocab]``."""
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{_NAME}.TextDecoder runs on MI355X only (no CPU fallback); move the model to a GPU")
+        if tokens.ndim == 1:
+            tokens = tokens[None]
+        B, T = tokens.shape
+        with torch.cuda.device(self.device):
+            if kv_cache is None:
+                if xa is None or xa.ndim != 3 or xa.shape[0] != B or xa.shape[2] != self.width:
+                    raise ValueError(f"xa of shape {None if xa is None else tuple(xa.shape)}: [{B}, Tk, {self.width}] expected")
+                if T > self.ctx:
+                    raise ValueError(f"{T} tokens: the decoder has {self.ctx} positions")
+                x = self._sequences(tokens, self.cross_kv(xa), int(xa.shape[1]))
+                return self._head(x).view(B, T, self.vocab_padded)[..., :self.vocab]
+            kc = kv_cache
+            if kc.length == 0:
+                if B != 1:
+                    raise ValueError("an empty cache is filled from ONE prompt shared by its rows: tokens [1, T]")
+                return self.prefill(tokens, kc).view(1, T, self.vocab_padded)[..., :self.vocab]
+            if T != 1 or B != kc.R:
+                raise ValueError(f"a filled cache takes one new token per row: tokens [{kc.R}, 1]")
+            self.step(tokens.to(self.device, torch.int32).contiguous().view(-1), kc)
+            return kc.logits.view(B, 1, self.vocab_padded)[..., :self.vocab]
+
+    @torch.no_grad()
+    def prefill(self, tokens: torch.Tensor, kc: KVCache) -> torch.Tensor:
+        """The prompt ``[1, T]`` shared by every row of an empty cache, once: fills positions 0 .. T - 1 of all rows' caches (broadcast) and
+        returns the prompt's logits ``[T, vocab_padded]``."""
+        T = int(tokens.shape[-1])
+        if kc.length != 0:
+            raise ValueError("prefill of a cache that already holds positions")
+        if kc.n_windows != 1:
+            raise NotImplementedError("prefill of rows over several windows: one window per cache is what decode() drives")
+        if T > min(kc.T_max, self.ctx):
+            raise ValueError(f"a prompt of {T} tokens does not fit the cache's {kc.T_max} positions")
+        D = self.width
+
+        def keep(i, qkv):          # the prompt's keys / values, the same for every candidate row of the window
+            kc.self_k[i][:, :T] = qkv[:, D:2 * D]
+            kc.self_v[i][:, :T] = qkv[:, 2 * D:]
+        with torch.cuda.device(self.device):
+            x = self._sequences(tokens.view(1, T), kc.cross_kv, kc.Tk, keep)
+            kc.length = T
+            return self._head(x)
+
+    def step(self, ids: torch.Tensor, kc: KVCache) -> torch.Tensor:
+        """one position for every row of the cache: ``ids`` int32 ``[R]`` on the device -> ``kc.logits [R, vocab_padded]``"""
+        if kc.length >= min(kc.T_max, self.ctx):
+            raise ValueError(f"position {kc.length}: the cache holds {kc.T_max} positions, the decoder {self.ctx}")
+        _lib.check(_lib.load().hirest_whisper_decode_step(C.byref(self._w()["desc"]), kc.R, kc.length, ids.data_ptr(), kc.k_ptrs, kc.v_ptrs, kc.T_max,
+                                                          kc.x_ptrs, kc.n_windows, kc.Tk, kc.row_window.data_ptr(), kc.logits.data_ptr(),
+                                                          kc.ws.data_ptr(), kc.ws.numel(), ops.stream_ptr()), "hirest_whisper_decode_step")
+        kc.length += 1
+        return kc.logits
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the tokenizer
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+class Tokenizer:
+    """Whisper's tokenizer over the project's byte-level BPE (``bytebpe.ByteBPETokenizer``): GPT-2's vocabulary and merges plus
+    Whisper's special tokens; the 1501 timestamp tokens ``<|0.00|>`` .. ``<|30.00|>`` follow ``<|notimestamps|>``.
+
+    ``specials``: special-token string -> id.  ``<|endoftext|>``, ``<|startoftranscript|>``, ``<|startofprev|>`` and
+    ``<|notimestamps|>`` are required; ``<|nospeech|>`` (``<|nocaptions|>`` in older files), ``<|startoflm|>``, ``<|transcribe|>``,
+    ``<|translate|>`` and the language tokens (``<|en|>`` ...) are used when present."""
+
+    def __init__(self, vocab: Dict[str, int], merges, specials: Dict[str, int], language: Optional[str] = None, task: Optional[str] = None):
+        self.specials = {str(k): int(v) for k, v in specials.items()}
+        for need in ("<|endoftext|>", "<|startoftranscript|>", "<|startofprev|>", "<|notimestamps|>"):
+            if need not in self.specials:
+                raise ValueError(f"the special-token table has no {need}")
+        full = dict(vocab)
+        full.update(self.specials)
+        self.bpe = ByteBPETokenizer(full, merges, bos_token="<|endoftext|>", eos_token="<|endoftext|>", pad_token="<|endoftext|>",
+                                    unk_token="<|no unknown token|>")     # every byte has a symbol in a real vocabulary
+        self._special_ids = {i: s for s, i in self.specials.items()}
+        self.language, self.task = language, task
+        self.eot = self.specials["<|endoftext|>"]
+        self.sot = self.specials["<|startoftranscript|>"]
+        self.sot_prev = self.specials["<|startofprev|>"]
+        self.sot_lm = self.specials.get("<|startoflm|>")
+        self.no_speech = self.specials.get("<|nospeech|>", self.specials.get("<|nocaptions|>"))
+        self.no_timestamps = self.specials["<|notimestamps|>"]
+        self.transcribe, self.translate = self.specials.get("<|transcribe|>"), self.specials.get("<|translate|>")
+        self.timestamp_begin = self.no_timestamps + 1
+
+    @classmethod
+    def from_dir(cls, model_dir: str, **kw) -> "Tokenizer":
+        """A Hugging Face Whisper directory: ``vocab.json``, ``merges.txt`` and the added tokens (``added_tokens.json``, else the
+        ``added_tokens`` of ``tokenizer.json``); ids of ``vocab.json`` that are special tokens are picked up from there."""
+        with open(os.path.join(model_dir, "vocab.json"), encoding="utf-8") as f:
+            vocab = json.load(f)
+        with open(os.path.join(model_dir, "merges.txt"), encoding="utf-8") as f:
+            merges = f.read().split("\n")
+        specials = {k: v for k, v in vocab.items() if k.startswith("<|") and k.endswith("|>")}
+        added = os.path.join(model_dir, "added_tokens.json")
+        if os.path.isfile(added):
+            with open(added, encoding="utf-8") as f:
+                specials.update(json.load(f))
+        elif os.path.isfile(os.path.join(model_dir, "tokenizer.json")):
+            with open(os.path.join(model_dir, "tokenizer.json"), encoding="utf-8") as f:
+                specials.update({t["content"]: t["id"] for t in json.load(f).get("added_tokens", [])})
+        specials = {k: v for k, v in specials.items() if not _TIMESTAMP.fullmatch(k)}
+        return cls(vocab, merges, specials, **kw)
+
+    @property
+    def sot_sequence(self):
+        seq = [self.sot]
+        if self.language is not None:
+            seq.append(self.specials[f"<|{self.language}|>"])
+        if self.task is not None:
+            seq.append(self.transcribe if self.task == "transcribe" else self.translate)
+        return tuple(seq)
+
+    def encode(self, text: str) -> List[int]:
+        return self.bpe.tokenize_ids(text)
+
+    def _decode(self, ids, stamps: bool) -> str:
+        out, run = [], []
+        for t in ids:
+            t = int(t)
+            if t >= self.timestamp_begin or t in self._special_ids:
+                if run:
+                    out.append(self.bpe.decode(run))
+                    run = []
+                if t >= self.timestamp_begin:
+                    if stamps:
+                        out.append(f"<|{(t - self.timestamp_begin) * 0.02:.2f}|>")
+                else:
+                    out.append(self._special_ids[t])
+            else:
+                run.append(t)
+        if run:
+            out.append(self.bpe.decode(run))
+        return "".join(out)
+
+    def decode(self, ids) -> str:
+        """text of the ids, timestamp tokens dropped (Whisper's ``decode``)"""
+        return self._decode(ids, False)
+
+    def decode_with_timestamps(self, ids) -> str:
+        """timestamp tokens rendered as ``<|1.08|>`` (0.02 s per token)"""
+        return self._decode(ids, True)
+
+    @functools.cached_property
+    def non_speech_tokens(self):
+        """What ``suppress_tokens="-1"`` stands for: tokens of speaker tags and non-speech annotations (``♪♪♪``, ``( SPEAKING FOREIGN
+        LANGUAGE )``, ``[DAVID] Hey there``) — the listed symbols where they are one token, with and without a leading space; of the
+        musical symbols the first token even where they take several; `` -`` and `` '`` so that they do not open a line."""
+        symbols = list("\"#()*+/:;<=>@[\\]^_`{|}~「」『』")
+        symbols += "<< >> <<< >>> -- --- -( -[ (' (\" (( )) ((( ))) [[ ]] {{ }} ♪♪ ♪♪♪".split()
+        misc = set("♩♪♫♬♭♮♯")
+        result = {self.encode(" -")[0], self.encode(" '")[0]}
+        for sym in symbols + sorted(misc):
+            for text in (sym, " " + sym):
+                try:
+                    toks = self.encode(text)
+                except KeyError:                                      # a reduced vocabulary without that byte: nothing to suppress
+                    continue
+                if len(toks) == 1 or sym in misc:
+                    result.add(toks[0])
+        return tuple(sorted(result))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# decoding
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+@dataclasses.dataclass(frozen=True)
+class DecodingOptions:
+    task: str = "transcribe"
+    language: Optional[str] = None
+    temperature: float = 0.0
+    sample_len: Optional[int] = None          # maximum number of tokens to sample (default: half the text context)
+    best_of: Optional[int] = None             # independent candidates when temperature > 0
+    beam_size: Optional[int] = None           # not built: beam search
+    patience: Optional[float] = None          # not built: beam search
+    length_penalty: Optional[float] = None    # None: rank candidates by sum_logprobs / length
+    prompt: Optional[Union[str, List[int]]] = None
+    prefix: Optional[Union[str, List[int]]] = None      # not built
+    suppress_blank: bool = True
+    suppress_tokens: Optional[Union[str, Iterable[int]]] = "-1"
+    without_timestamps: bool = False
+    max_initial_timestamp: Optional[float] = 1.0
+    fp16: bool = True                         # accepted and ignored: this path is exact fp32
+    seed: int = 0                             # of the counter-based generator the categorical draws come from (not Whisper's: it draws from torch's)
+    monotonic_timestamps: bool = True         # current Whisper's rule that timestamps do not decrease
+
+    def __post_init__(self):
+        if self.beam_size is not None or self.patience is not None:
+            raise NotImplementedError("beam search (beam_size / patience) is not built: the sampling branch (temperature, best_of) is")
+        if self.prefix is not None:
+            raise NotImplementedError("prefix is not built")
+        if self.length_penalty is not None:
+            raise NotImplementedError("length_penalty other than None is not built")
+        if self.temperature == 0 and self.best_of is not None:
+            raise ValueError("best_of with greedy sampling (T=0) is not compatible")
+
+
+@dataclasses.dataclass(frozen=True)
+class DecodingResult:
+    audio_features: Optional[torch.Tensor] = None
+    language: str = "en"
+    tokens: List[int] = dataclasses.field(default_factory=list)
+    text: str = ""
+    avg_logprob: float = float("nan")
+    no_speech_prob: float = float("nan")
+    temperature: float = float("nan")
+    compression_ratio: float = float("nan")
+
+
+def compression_ratio(text: str) -> float:
+    raw = text.encode("utf-8")
+    return len(raw) / len(zlib.compress(raw))
+
+
+def tail_params(tokenizer: Tokenizer, options: DecodingOptions, n_vocab: int, vocab_padded: int, n_audio_ctx: int, sample_begin: int,
+                device) -> Tuple["_lib.WhisperTailParams", torch.Tensor]:
+    """The tail kernel's constant block for a tokenizer and options, and the suppress mask it points to (keep it alive)."""
+    sup = options.suppress_tokens
+    if isinstance(sup, str):
+        sup = [int(t) for t in sup.split(",") if t.strip()]
+    sup = list(sup or [])
+    if -1 in sup:
+        sup = [t for t in sup if t >= 0] + list(tokenizer.non_speech_tokens)
+    sup += [t for t in (tokenizer.transcribe, tokenizer.translate, tokenizer.sot, tokenizer.sot_prev, tokenizer.sot_lm, tokenizer.no_speech)
+            if t is not None]
+    sup += list(range(n_vocab, vocab_padded))                         # the LM head's pad columns
+    words = np.zeros((vocab_padded + 31) // 32, dtype=np.uint32)
+    for t in set(sup):
+        if not 0 <= t < vocab_padded:
+            raise ValueError(f"suppressed token {t} outside the vocabulary of {n_vocab}")
+        words[t >> 5] |= np.uint32(1) << np.uint32(t & 31)
+    mask = torch.from_numpy(words.view(np.int32)).to(device)
+    blank = tokenizer.encode(" ")
+    p = _lib.WhisperTailParams()
+    p.n_vocab, p.eot, p.no_speech = n_vocab, tokenizer.eot, -1 if tokenizer.no_speech is None else tokenizer.no_speech
+    p.no_timestamps, p.timestamp_begin = tokenizer.no_timestamps, tokenizer.timestamp_begin
+    p.max_initial_timestamp_index = -1
+    if options.max_initial_timestamp is not None:
+        p.max_initial_timestamp_index = int(round(options.max_initial_timestamp / (CHUNK_LENGTH / n_audio_ctx)))
+    p.sample_begin, p.blank, p.suppress_blank = sample_begin, blank[0] if len(blank) == 1 else -1, int(bool(options.suppress_blank))
+    p.timestamp_rules, p.monotonic = int(not options.without_timestamps), int(bool(options.monotonic_timestamps))
+    p.temperature, p.seed, p.serial = float(options.temperature), int(options.seed) & 0xFFFFFFFF, 0
+    p.suppress_mask = mask.data_ptr()
+    return p, mask
+
+
+def new_row_state(R: int, device) -> torch.Tensor:
+    """``hirest_whisper_row_state [R]`` as an int32 ``[R, 8]`` tensor in its initial state (columns 5 .. 7 are floats)"""
+    st = torch.zeros((R, _lib.WHISPER_ROW_STATE_WORDS), dtype=torch.int32)
+    st[:, 1:4] = -1
+    return st.to(device)
+
+
+def _initial_tokens(tokenizer: Tokenizer, options: DecodingOptions, n_ctx: int) -> Tuple[List[int], int]:
+    tokens = list(tokenizer.sot_sequence)
+    if options.without_timestamps:
+        tokens.append(tokenizer.no_timestamps)
+    if options.prompt:                                                # (an empty prompt — a file's first window — adds no sot_prev either)
+        prompt = tokenizer.encode(" " + options.prompt.strip()) if isinstance(options.prompt, str) else list(options.prompt)
+        tokens = [tokenizer.sot_prev] + prompt[-(n_ctx // 2 - 1):] + tokens
+    return tokens, tokens.index(tokenizer.sot)
+
+
+@torch.no_grad()
+def decode(model: "Whisper", mel: torch.Tensor, options: DecodingOptions = DecodingOptions(), *, return_candidates: bool = False):
+    """``whisper.decode``: one 30-second window ``[n_mels, 3000]`` (or encoder states ``[Tk, D]``) or a batch of them -> a
+    ``DecodingResult`` (a list for a batch).  Greedy at temperature 0; at temperature > 0 ``best_of`` candidates per window are sampled
+    and the one with the highest ``sum_logprobs / length`` is returned.  The loop enqueues ``hirest_whisper_decode_step`` +
+    ``hirest_whisper_step_tail`` per token and reads nothing back but the pinned stamp; tokens and sums are read once at the end.
+    ``return_candidates``: also every candidate's (tokens, sum_logprobs) per window (tests)."""
+    tokenizer = model.tokenizer
+    if tokenizer is None:
+        raise ValueError("the model has no tokenizer: load_model(path, tokenizer=...) or set model.tokenizer")
+    single = mel.ndim == 2
+    if single:
+        mel = mel[None]
+    dec, dev = model.decoder, model.device
+    n_audio_ctx = model.dims["n_audio_ctx"]
+    with torch.cuda.device(dev):
+        if mel.shape[-2:] == (n_audio_ctx, model.dims["n_audio_state"]):
+            xa = mel.to(dev, torch.float32)
+        else:
+            xa = model.encoder(mel)
+        initial, sot_index = _initial_tokens(tokenizer, options, dec.ctx)
+        sample_begin = len(initial)
+        sample_len = options.sample_len or dec.ctx // 2
+        group = (options.best_of or 1) if options.temperature > 0 else 1
+        T_max = min(dec.ctx, sample_begin + sample_len)
+        steps = T_max - sample_begin
+        if steps <= 0:
+            raise ValueError(f"a prompt of {sample_begin} tokens leaves no room to sample in a context of {dec.ctx}")
+        lib = _lib.load()
+        results, everything = [], []
+        for w in range(xa.shape[0]):                                  # (batching windows into one loop is a later step)
+            kc = KVCache(dec, xa[w:w + 1], torch.zeros(group, dtype=torch.int32), T_max)
+            params, mask = tail_params(tokenizer, options, dec.vocab, dec.vocab_padded, n_audio_ctx, 0, dev)
+            padded = dec.prefill(torch.tensor([initial], dtype=torch.int32), kc)            # [T, vocab_padded]
+            state = new_row_state(group, dev)
+            tokens = torch.full((group, steps), tokenizer.eot, dtype=torch.int32, device=dev)
+            ids = torch.empty((group,), dtype=torch.int32, device=dev)
+            stamp = torch.zeros(1, dtype=torch.int32).pin_memory()
+            first = torch.empty((group, dec.vocab_padded), dtype=torch.float32, device=dev)
+            first.copy_(padded[sample_begin - 1].expand(group, -1))
+            no_speech = None
+            if sot_index != sample_begin - 1 and tokenizer.no_speech is not None:
+                # Whisper reads no_speech_prob at the sot position: one tail call on that row, into a scratch state
+                scratch, sid = new_row_state(1, dev), torch.empty(1, dtype=torch.int32, device=dev)
+                row = padded[sot_index].contiguous()
+                _lib.check(lib.hirest_whisper_step_tail(row.data_ptr(), dec.vocab_padded, 1, dec.vocab_padded, 0, 0, C.byref(params),
+                                                        scratch.data_ptr(), sid.data_ptr(), None, None, None, ops.stream_ptr()), "hirest_whisper_step_tail")
+                no_speech = scratch
+            logits = first
+            for step in range(steps):
+                params.serial = step
+                _lib.check(lib.hirest_whisper_step_tail(logits.data_ptr(), dec.vocab_padded, group, dec.vocab_padded, step, steps, C.byref(params),
+                                                        state.data_ptr(), ids.data_ptr(), tokens.data_ptr(), None, stamp.data_ptr(), ops.stream_ptr()),
+                           "hirest_whisper_step_tail")
+                s = int(stamp[0])                                     # whatever step has landed by now: no wait
+                if (s & 1) or step == steps - 1:
+                    break
+                logits = dec.step(ids, kc)
+            torch.cuda.current_stream().synchronize()
+            toks, st = tokens.cpu().numpy(), state.cpu()
+            sums = st[:, 5].view(torch.float32).tolist()
+            nsp = (no_speech.cpu() if no_speech is not None else st)[0, 6:7].view(torch.float32).item()
+            cands = []
+            for g in range(group):
+                row = toks[g].tolist()
+                cands.append((row[:row.index(tokenizer.eot)] if tokenizer.eot in row else row, sums[g]))
+            best = max(range(group), key=lambda g: (cands[g][1] / max(len(cands[g][0]), 1), -g))
+            t, lp = cands[best]
+            text = tokenizer.decode(t).strip()
+            results.append(DecodingResult(audio_features=xa[w], language=tokenizer.language or "en", tokens=t, text=text,
+                                          avg_logprob=lp / (len(t) + 1), no_speech_prob=nsp, temperature=options.temperature,
+                                          compression_ratio=compression_ratio(text) if text else 0.0))
+            everything.append(cands)
+    if return_candidates:
+        return (results[0], everything[0]) if single else (results, everything)
+    return results[0] if single else results
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the model, transcribe(), .srt
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+class Whisper(nn.Module):
+    """``whisper.model.Whisper``: ``.encoder``, ``.decoder``, ``.dims`` (OpenAI's field names), ``embed_audio``, ``logits``, ``forward``."""
+
+    def __init__(self, dims_or_config, state_dict: Dict[str, torch.Tensor], tokenizer: Optional[Tokenizer] = None):
+        super().__init__()
+        self.encoder = AudioEncoder(dims_or_config, state_dict)
+        self.decoder = TextDecoder(dims_or_config, state_dict)
+        e, d = self.encoder, self.decoder
+        self.dims = {"n_mels": e.n_mels, "n_audio_ctx": e.ctx, "n_audio_state": e.width, "n_audio_head": e.heads, "n_audio_layer": e.layers,
+                     "n_vocab": d.vocab, "n_text_ctx": d.ctx, "n_text_state": d.width, "n_text_head": d.heads, "n_text_layer": d.layers}
+        self.tokenizer = tokenizer
+
+    @property
+    def device(self) -> torch.device:
+        return self.decoder.device
+
+    @property
+    def is_multilingual(self) -> bool:
+        return self.dims["n_vocab"] >= 51865
+
+    def embed_audio(self, mel: torch.Tensor) -> torch.Tensor:
+        return self.encoder(mel)
+
+    def logits(self, tokens: torch.Tensor, audio_features: torch.Tensor) -> torch.Tensor:
+        return self.decoder(tokens, audio_features)
+
+    def forward(self, mel: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+        return self.decoder(tokens, self.encoder(mel))
+
+    def decode(self, mel, options: DecodingOptions = DecodingOptions()):
+        return decode(self, mel, options)
+
+    def transcribe(self, audio, **kw):
+        return transcribe(self, audio, **kw)
+
+
+def load_model(path: str, device: Optional[Union[str, torch.device]] = None, tokenizer: Optional[Union[str, Tokenizer]] = None) -> Whisper:
+    """A local OpenAI ``.pt`` checkpoint or a Hugging Face model directory -> ``Whisper``.  There are no model names and no downloads: a
+    bare name (``'small.en'``) raises FileNotFoundError saying so.  ``tokenizer``: a ``Tokenizer`` or a directory with ``vocab.json`` and
+    ``merges.txt`` (default: the model directory itself when it has them; a ``.pt`` carries no vocabulary)."""
+    if os.path.isdir(path):
+        with open(os.path.join(path, "config.json")) as f:
+            config = json.load(f)
+        model = Whisper(config, _load_weights(path))
+        if tokenizer is None and os.path.isfile(os.path.join(path, "vocab.json")):
+            tokenizer = path
+    elif os.path.isfile(path):
+        ckpt = torch.load(path, map_location="cpu")
+        if not (isinstance(ckpt, dict) and "dims" in ckpt and "model_state_dict" in ckpt):
+            raise ValueError(f"{path}: not a Whisper checkpoint (a dict with 'dims' and 'model_state_dict')")
+        model = Whisper(ckpt["dims"], ckpt["model_state_dict"])
+    else:
+        raise FileNotFoundError(f"{path!r} is neither a local .pt checkpoint nor a model directory: model names are not resolved and "
+                                "nothing is downloaded (no network access) — download the model beforehand and pass its path")
+    if isinstance(tokenizer, (str, os.PathLike)):
+        multilingual = model.is_multilingual
+        tokenizer = Tokenizer.from_dir(os.fspath(tokenizer), language="en" if multilingual else None, task="transcribe" if multilingual else None)
+    model.tokenizer = tokenizer
+    return model.to(device) if device is not None else model
+
+
+def transcribe(model, audio, *, temperature: Union[float, Tuple[float, ...]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
+               compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
+               no_speech_threshold: Optional[float] = 0.6, condition_on_previous_text: bool = True, initial_prompt: Optional[str] = None,
+               verbose=None, **decode_options):
+    """``whisper.transcribe``: a ``.wav`` path, a waveform or a ready spectrogram ``[n_mels, frames]`` (with its 30 s of padding) ->
+    ``{"text", "segments", "language"}``.  One spectrogram per file; 3000-frame windows from ``seek``; per window the temperature
+    fallback (the next temperature when the compression ratio or the average log-probability crosses its threshold), the no-speech
+    skip, segments cut at consecutive timestamp pairs, ``seek`` advanced to the last timestamp or by the whole window; the prompt of
+    the next window is the text so far, reset after a window decoded above temperature 0.5."""
+    tokenizer = decode_options.pop("tokenizer", None) or getattr(model, "tokenizer", None)
+    if tokenizer is None:
+        raise ValueError("no tokenizer: load_model(path, tokenizer=...) or transcribe(..., tokenizer=...)")
+    language = decode_options.get("language")
+    if getattr(model, "is_multilingual", False):
+        if language is None:
+            raise NotImplementedError("language detection is not built: pass language= for a multilingual model")
+    else:
+        language = "en"
+    if isinstance(language, str) and language.lower() == "english":
+        language = "en"
+    dims = model.dims
+    if torch.is_tensor(audio) and audio.ndim == 2:
+        mel = audio
+    else:
+        mel = log_mel_spectrogram(audio, dims["n_mels"], padding=N_SAMPLES, device=model.device)
+    content_frames = mel.shape[-1] - N_FRAMES
+    input_stride = N_FRAMES // dims["n_audio_ctx"]                    # mel frames per encoder position: 2
+    time_precision = input_stride * HOP_LENGTH / SAMPLE_RATE          # 0.02 s per timestamp token
+    temperatures = (temperature,) if isinstance(temperature, (int, float)) else tuple(temperature)
+    tb, eot = tokenizer.timestamp_begin, tokenizer.eot
+
+    def decode_with_fallback(segment) -> DecodingResult:
+        result = None
+        for t in temperatures:
+            kw = dict(decode_options)
+            for k in (("beam_size", "patience") if t > 0 else ("best_of",)):      # the sampling branch has no beams, the greedy one no candidates
+                kw.pop(k, None)
+            result = decode(model, segment, DecodingOptions(**kw, temperature=float(t)))
+            again = compression_ratio_threshold is not None and result.compression_ratio > compression_ratio_threshold
+            again = again or (logprob_threshold is not None and result.avg_logprob < logprob_threshold)
+            if not again:
+                break
+        return result
+
+    seek, all_tokens, all_segments, reset_since = 0, [], [], 0
+    if initial_prompt is not None:
+        all_tokens.extend(tokenizer.encode(" " + initial_prompt.strip()))
+
+    def add_segment(start: float, end: float, tokens: List[int], result: DecodingResult):
+        text = tokenizer.decode([t for t in tokens if t < eot])
+        if not text.strip():
+            return
+        all_segments.append({"id": len(all_segments), "seek": seek, "start": start, "end": end, "text": text, "tokens": list(tokens),
+                             "temperature": result.temperature, "avg_logprob": result.avg_logprob,
+                             "compression_ratio": result.compression_ratio, "no_speech_prob": result.no_speech_prob})
+        all_tokens.extend(tokens)
+
+    while seek < content_frames:
+        window_start = seek
+        time_offset = seek * HOP_LENGTH / SAMPLE_RATE
+        segment_size = min(N_FRAMES, content_frames - seek)
+        segment = pad_or_trim(mel[:, seek:seek + N_FRAMES], N_FRAMES)
+        decode_options["prompt"] = all_tokens[reset_since:]
+        result = decode_with_fallback(segment)
+        tokens = list(result.tokens)
+        if no_speech_threshold is not None and result.no_speech_prob > no_speech_threshold and \
+                not (logprob_threshold is not None and result.avg_logprob > logprob_threshold):
+            seek += segment_size                                      # silence: skip the window
+            continue
+        is_ts = [t >= tb for t in tokens]
+        single_ending = is_ts[-2:] == [False, True]
+        cuts = [i + 1 for i in range(len(tokens) - 1) if is_ts[i] and is_ts[i + 1]]
+        if cuts:
+            if single_ending:
+                cuts.append(len(tokens))
+            last = 0
+            for cut in cuts:
+                piece = tokens[last:cut]
+                add_segment(time_offset + (piece[0] - tb) * time_precision, time_offset + (piece[-1] - tb) * time_precision, piece, result)
+                last = cut
+            if single_ending:
+                seek += segment_size                                  # a single timestamp at the end: no speech after it
+            else:
+                seek += (tokens[last - 1] - tb) * input_stride        # the rest of the window is decoded again from the last pair's end
+        else:
+            duration = segment_size * HOP_LENGTH / SAMPLE_RATE
+            stamps = [t for t in tokens if t >= tb]
+            if stamps and stamps[-1] != tb:
+                duration = (stamps[-1] - tb) * time_precision
+            add_segment(time_offset, time_offset + duration, tokens, result)
+            seek += segment_size
+        if seek <= window_start:                                      # (a last pair that closes at <|0.00|>, possible only without the
+            seek = window_start + segment_size                        #  monotonic rule, would decode the same window for ever)
+        if not condition_on_previous_text or result.temperature > 0.5:
+            reset_since = len(all_tokens)
+    text_tokens = [t for s in all_segments for t in s["tokens"] if t < eot]
+    return {"text": tokenizer.decode(text_tokens), "segments": all_segments, "language": language}
+
+
+def format_timestamp(seconds: float, always_include_hours: bool = False, decimal_marker: str = ".") -> str:
+    if seconds < 0:
+        raise ValueError("non-negative timestamp expected")
+    ms = int(round(seconds * 1000.0))
+    h, ms = divmod(ms, 3_600_000)
+    m, ms = divmod(ms, 60_000)
+    s, ms = divmod(ms, 1000)
+    hours = f"{h:02d}:" if always_include_hours or h > 0 else ""
+    return f"{hours}{m:02d}:{s:02d}{decimal_marker}{ms:03d}"
+
+
+def write_srt(segments, file) -> None:
+    """Segments of ``transcribe()`` as SubRip: index, ``HH:MM:SS,mmm --> HH:MM:SS,mmm``, text, blank line (what ``dataset.read_srt_spans``
+    and the ``srt`` package parse)."""
+    for i, seg in enumerate(segments, start=1):
+        print(f"{i}\n{format_timestamp(seg['start'], True, ',')} --> {format_timestamp(seg['end'], True, ',')}\n"
+              f"{seg['text'].strip().replace('-->', '->')}\n", file=file, flush=True)
+
+
+utils = types.SimpleNamespace(write_srt=write_srt, format_timestamp=format_timestamp)

@@ -1233,6 +1233,98 @@ int hirest_log_mel(const float* audio, int64_t n, int64_t padding, const float* 
  * K = 3 C). */
 int hirest_mel_to_rows(const float* mel, float* rows, int32_t B, int32_t n_mels, int32_t T, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Whisper text decoder (csrc/whisper_dec.hip, hirest_amd/whisper.py): a sampling step's attention kernels, its tail and
+ * the step itself.  Prefill runs on hirest_gemm_f32(_ln) / hirest_attention_f32_qkv.
+ * ------------------------------------------------------------------------------------ */
+/* hirest_attention_f32_decode with the history in a preallocated cache: row r's keys j < t at k_cache / v_cache + r * row_stride +
+ * j * ld_cache (row_stride >= T_max * ld_cache), the newest at k_new / v_new + r * ld_new, which is also stored at position t of the
+ * cache (t < T_max); nothing else of the cache is written.  No parent rows: sampling does not reorder.  Same kernel body and same bits
+ * as hirest_attention_f32_decode(parent = NULL) over the same t + 1 keys. */
+int hirest_attention_f32_decode_inplace(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ld_cache, int64_t row_stride,
+                                        int32_t t, int32_t T_max, const float* k_new, const float* v_new, int64_t ld_new, float* out,
+                                        int32_t R, int32_t H, float scale, float add_const, float causal_penalty, void* stream);
+/* softmax(q k^T scale) v for ONE query per row against a long key set shared by rows, head width 64.  kv: n_windows arrays
+ * [Tk, ldkv >= 2 * H * 64] of key | value rows (key of head h at column 64 h, value at 64 (H + h)), window w at kv + w * window_stride,
+ * 16-byte aligned; row_window: R device ints, row r attends to window row_window[r] (a row whose window is outside [0, n_windows)
+ * gets zeros).  q [R, ldq], out [R, ldo].  The keys are cut into chunks of 64 — a function of Tk alone — one block per (window, head,
+ * chunk) serves every row of its window from one staged copy of the chunk, and a second kernel merges a row's chunk records in
+ * ascending order: no atomics, and a row's outputs have the same bits whatever else is in the call, in any row order, on every run.
+ * Keys past Tk are never read. */
+size_t hirest_attention_f32_cross_decode_workspace_bytes(int32_t R, int32_t H, int32_t Tk);
+int hirest_attention_f32_cross_decode(const float* q, int64_t ldq, const float* kv, int64_t ldkv, int64_t window_stride, int32_t n_windows,
+                                      int32_t Tk, const int32_t* row_window, float* out, int64_t ldo, int32_t R, int32_t H, float scale,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* One candidate row's decoding state, on the device.  Initial state: zeros with last = penult = last_timestamp = -1. */
+typedef struct hirest_whisper_row_state {
+    int32_t n_sampled;            /* tokens sampled so far, eot not counted */
+    int32_t last, penult;         /* the last two of them (-1: none) */
+    int32_t last_timestamp;       /* the last timestamp token among them (-1: none) */
+    int32_t completed;            /* eot was picked: the row emits eot from now on and nothing else of it changes */
+    float   sum_logprobs;         /* sum of log_softmax(filtered logits)[pick] at temperature 1, the eot pick included (Whisper's) */
+    float   no_speech_prob;       /* softmax(unfiltered logits)[no_speech] at the first sampled position */
+    float   last_logprob;         /* the newest term of sum_logprobs */
+} hirest_whisper_row_state;
+/* A call's constants (HOST struct, copied into the kernel arguments). */
+typedef struct hirest_whisper_tail_params {
+    int32_t n_vocab;                      /* real vocabulary; columns n_vocab .. V - 1 are padding and must be set in suppress_mask */
+    int32_t eot, no_speech;               /* no_speech < 0: no_speech_prob = 0 */
+    int32_t no_timestamps, timestamp_begin, max_initial_timestamp_index;      /* index < 0: no limit on the first timestamp */
+    int32_t sample_begin;                 /* column of `tokens` that receives step 0's pick */
+    int32_t blank, suppress_blank;        /* the space token; with suppress_blank it and eot are suppressed at the first position */
+    int32_t timestamp_rules;              /* 0: without_timestamps (only the suppress mask and blank suppression apply) */
+    int32_t monotonic;                    /* 1 (current Whisper): timestamps do not decrease, the last may repeat only to close a pair */
+    float   temperature;                  /* 0: argmax (lower index on ties); > 0: a categorical draw from softmax(filtered logits / T) */
+    uint32_t seed, serial;                /* the draw is Gumbel-max over a counter-based generator keyed by (seed, serial, row, token) */
+    const uint32_t* suppress_mask;        /* device, (V + 31) / 32 words: bit v & 31 of word v >> 5 suppresses token v */
+} hirest_whisper_tail_params;
+/* Everything after the LM head of a sampling step, for R rows of logits [R, V] (row stride ldx, 16-byte aligned, V % 4 == 0), in two
+ * launches.  Per row that is not completed, in Whisper's order: at the first sampled position no_speech_prob and blank suppression; the
+ * suppress mask; the timestamp rules of whisper/decoding.py::ApplyTimestampRules as transformers' WhisperTimeStampLogitsProcessor
+ * states them (no_timestamps suppressed; timestamps in pairs; after text + timestamp only a timestamp or eot; `monotonic`; the first
+ * token a timestamp <= timestamp_begin + max_initial_timestamp_index; text suppressed when logsumexp(logprobs[timestamp_begin:]) >
+ * max(logprobs[:timestamp_begin])); log_softmax; the pick; sum_logprobs += logprobs[pick]; completed on eot.  next_ids[r] = the pick
+ * (eot for a completed row), tokens[r * T_max + sample_begin + step] likewise (tokens may be NULL).  logprobs (optional, [R, V] packed, 16-byte
+ * aligned): log_softmax of the filtered row, -inf where suppressed; rows that were already completed are not written.  done_host
+ * (optional, pinned host): *done_host = ((step + 1) << 1) | (every row completed).
+ * The generator is the one hirest_dropout_add_f32 uses (the splitmix64 finaliser, counter-based), applied twice:
+ * bits = mix(mix((serial << 32 | seed) + G) + (row << 32 | token) + G) >> 40 with G = 0x9E3779B97F4A7C15; u = ((bits >> 1) + 0.5) / 2^23 (exact in fp32);
+ * the pick is argmax(logit / T - log(-log u)).  Every reduction has a fixed order: two runs give the same bits. */
+int hirest_whisper_step_tail(const float* logits, int64_t ldx, int32_t R, int32_t V, int32_t step, int32_t T_max,
+                             const hirest_whisper_tail_params* params, hirest_whisper_row_state* state, int32_t* next_ids, int32_t* tokens,
+                             float* logprobs, int32_t* done_host, void* stream);
+/* out[r * V + v] = the generator's 24 bits for (seed, serial, row r, token v) (tests) */
+int hirest_whisper_gumbel_bits(uint32_t seed, uint32_t serial, int32_t R, int32_t V, uint32_t* out, void* stream);
+
+/* whisper/model.py::TextDecoder, one position of R rows.  Pre-LN blocks: x += out(self_attn(attn_ln(x))); x += out(cross_attn(
+ * cross_attn_ln(x), xa)); x += fc2(gelu(fc1(mlp_ln(x)))); then ln and the tied-embedding LM head. */
+typedef struct hirest_whisper_layer {
+    const float* attn_ln_g; const float* attn_ln_b;
+    const float* qkv_w; const float* qkv_b;                         /* query | key | value fused [3D, D], [3D] (the key's bias: zeros) */
+    const float* so_w; const float* so_b;                           /* attn.out */
+    const float* cross_ln_g; const float* cross_ln_b;
+    const float* cq_w; const float* cq_b;                           /* cross_attn.query */
+    const float* co_w; const float* co_b;                           /* cross_attn.out */
+    const float* mlp_ln_g; const float* mlp_ln_b;
+    const float* fc1_w; const float* fc1_b; const float* fc2_w; const float* fc2_b;      /* mlp.0 [I, D] (gelu), mlp.2 [D, I] */
+} hirest_whisper_layer;
+typedef struct hirest_whisper_decoder {
+    int32_t layers, heads, hidden, inter, vocab_padded, max_pos;
+    const float* tok_emb;                                           /* [vocab_padded, D], rows past the vocabulary zero: also the LM head */
+    const float* pos_emb;                                           /* [max_pos, D] */
+    const hirest_whisper_layer* layer;                              /* HOST array [layers] */
+    const float* ln_g; const float* ln_b;
+    const float* lm_b;                                              /* [vocab_padded] zeros (Whisper's head has no bias) */
+} hirest_whisper_decoder;
+size_t hirest_whisper_step_workspace_bytes(const hirest_whisper_decoder* d, int32_t R, int32_t Tk);
+/* ids [R]: the tokens at `position`.  self_k / self_v: HOST arrays [layers] of [R, T_max, D] caches holding positions < position; the step
+ * appends position (hirest_attention_f32_decode_inplace).  cross_kv: HOST array [layers] of [n_windows, Tk, 2 D] key(xa) | value(xa) rows;
+ * row_window [R] as hirest_attention_f32_cross_decode's.  logits [R, vocab_padded]. */
+int hirest_whisper_decode_step(const hirest_whisper_decoder* d, int32_t R, int32_t position, const int32_t* ids, float* const* self_k,
+                               float* const* self_v, int32_t T_max, const float* const* cross_kv, int32_t n_windows, int32_t Tk,
+                               const int32_t* row_window, float* logits, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,125 @@
+#!/usr/bin/env python
+"""Fixtures of the Whisper text decoder: tests/golden/whisper_dec_{p,q,r}.npz.
+
+Whisper is not part of the reference tree, so the yardstick is ``transformers``' WhisperDecoder run in float64 on ``hirest_amd.synth``'s
+seeded weights, and its own logits processors (SuppressTokensAtBegin, SuppressTokens, WhisperTimeStampLogitsProcessor) for the greedy
+token sequences.  The fixtures hold the fp64 states before the LM head (the tests multiply by the embedding in fp64 themselves: rows of
+51864 logits would not fit a committed file), the error of the same forward in fp32 on the CPU — the tests' yardstick — and the greedy
+sequences.  A greedy fixture is refused when any step's top-2 margin is below 100 x that error: no step of it is then excused.
+
+    python tests/golden/make_whisper_dec_golden.py
+"""
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+
+from hirest_amd import synth  # noqa: E402
+
+SAMPLE_LEN = 24
+TEACHER_T = {"p": 12, "q": 12, "r": 6}
+
+
+def hf_decoder(cfg, sd, dtype):
+    from transformers import WhisperConfig
+    from transformers.models.whisper.modeling_whisper import WhisperDecoder
+    eot = cfg["vocab_size"] - 1
+    conf = WhisperConfig(vocab_size=cfg["vocab_size"], num_mel_bins=80, encoder_layers=1, encoder_attention_heads=cfg["encoder_attention_heads"],
+                         decoder_layers=cfg["decoder_layers"], decoder_attention_heads=cfg["decoder_attention_heads"],
+                         decoder_ffn_dim=cfg["decoder_ffn_dim"], encoder_ffn_dim=cfg["encoder_ffn_dim"], d_model=cfg["d_model"],
+                         max_source_positions=cfg["max_source_positions"], max_target_positions=cfg["max_target_positions"],
+                         pad_token_id=eot, bos_token_id=eot, eos_token_id=eot, decoder_start_token_id=eot, dropout=0.0,
+                         attention_dropout=0.0, activation_dropout=0.0, activation_function="gelu", scale_embedding=False)
+    conf._attn_implementation = "eager"
+    dec = WhisperDecoder(conf).eval()
+    own = {k[len("decoder."):]: v for k, v in sd.items()}
+    missing, unexpected = dec.load_state_dict(own, strict=False)
+    assert not unexpected and all("k_proj.bias" in m for m in missing), (missing, unexpected)
+    return dec.to(dtype)
+
+
+def logits_of(dec, emb, tokens, xa):
+    with torch.no_grad():
+        h = dec(input_ids=tokens, encoder_hidden_states=xa.to(emb.dtype), use_cache=False).last_hidden_state
+    return h, h @ emb.T
+
+
+def greedy(dec64, dec32, emb, xa, initial, sample_begin, sot_index, consts, without_timestamps):
+    from transformers.generation.logits_process import (SuppressTokensAtBeginLogitsProcessor, SuppressTokensLogitsProcessor,
+                                                        WhisperTimeStampLogitsProcessor)
+    procs = [SuppressTokensAtBeginLogitsProcessor([consts["blank"], consts["eot"]], sample_begin),
+             SuppressTokensLogitsProcessor(consts["suppress"])]
+    if not without_timestamps:
+        gc = types.SimpleNamespace(no_timestamps_token_id=consts["no_timestamps"], eos_token_id=consts["eot"], bos_token_id=consts["eot"],
+                                   max_initial_timestamp_index=consts["max_initial_timestamp_index"])
+        procs.append(WhisperTimeStampLogitsProcessor(gc, sample_begin))
+    tokens, sum_lp, no_speech, worst, err = list(initial), 0.0, None, np.inf, 0.0
+    for _ in range(SAMPLE_LEN):
+        ids = torch.tensor([tokens])
+        _, l64 = logits_of(dec64, emb, ids, xa)
+        _, l32 = logits_of(dec32, emb.float(), ids, xa)
+        err = max(err, float((l32.double() - l64).abs().max()))
+        if no_speech is None:
+            no_speech = float(l64[0, sot_index].softmax(-1)[consts["no_speech"]])
+        row = l64[:, -1]
+        for pr in procs:
+            row = pr(ids, row)
+        top = torch.topk(row[0], 2).values
+        worst = min(worst, float(top[0] - top[1]))
+        pick = int(row[0].argmax())
+        sum_lp += float(torch.log_softmax(row[0], -1)[pick])
+        if pick == consts["eot"]:
+            break
+        tokens.append(pick)
+    sampled = tokens[sample_begin:]
+    return sampled, sum_lp, no_speech, worst, err
+
+
+def main():
+    for case, (cfg, eot, seed, windows) in synth.WHISPER_DEC_CASES.items():
+        sd = synth.whisper_decoder_state_dict(cfg, seed, eot, synth.WHISPER_DEC_EOT_BIAS[case])
+        dec64, dec32 = hf_decoder(cfg, sd, torch.float64), hf_decoder(cfg, sd, torch.float32)
+        emb = sd["decoder.embed_tokens.weight"].double()
+        xa = synth.whisper_audio_states(cfg, windows, seed + 100)
+        sp = synth.whisper_special_tokens(eot)
+        T = TEACHER_T[case]
+        text = synth.token_ids(f"whisper.dec.{case}", windows * T, eot, seed).reshape(windows, T)
+        text[:, 0] = sp["<|startoftranscript|>"]
+        tokens = torch.from_numpy(text.astype(np.int64))
+        h64, l64 = logits_of(dec64, emb, tokens, xa.double())
+        _, l32 = logits_of(dec32, emb.float(), tokens, xa)
+        err = float((l32.double() - l64).abs().max())
+        print(f"{case}: teacher-forced [{windows}, {T}], |logit| max {float(l64.abs().max()):.2f}, fp32 CPU error {err:.3e}")
+        out = {"tokens": text.astype(np.int32), "hidden64": h64.numpy(), "err32": np.float64(err)}
+        if case in ("p", "q"):
+            consts = synth.whisper_tail_consts(cfg, eot)
+            prompt9 = synth.token_ids(f"whisper.dec.prompt.{case}", 9, eot, seed).tolist()
+            for has_prompt in (0, 1):
+                for wo in (0, 1):
+                    initial = [sp["<|startoftranscript|>"]] + ([sp["<|notimestamps|>"]] if wo else [])
+                    if has_prompt:
+                        initial = [sp["<|startofprev|>"]] + prompt9 + initial
+                    sot_index = initial.index(sp["<|startoftranscript|>"])
+                    sampled, sum_lp, nsp, worst, gerr = greedy(dec64, dec32, emb, xa[:1].double(), initial, len(initial), sot_index, consts, bool(wo))
+                    ended = "eot" if len(sampled) < SAMPLE_LEN else "sample_len"
+                    print(f"  greedy prompt={has_prompt} without_timestamps={wo}: {len(sampled)} tokens (ended by {ended}), smallest margin "
+                          f"{worst:.3e}, fp32 CPU error {gerr:.3e}, avg_logprob {sum_lp / (len(sampled) + 1):.4f}, no_speech {nsp:.3e}")
+                    print("   ", sampled)
+                    if worst < 100 * gerr:
+                        raise SystemExit(f"{case}: a greedy step's margin {worst:.3e} is below 100 x the fp32 error {gerr:.3e}: choose another seed")
+                    key = f"greedy_{has_prompt}{wo}"
+                    out[key + "_tokens"] = np.array(sampled, dtype=np.int32)
+                    out[key + "_stats"] = np.array([sum_lp / (len(sampled) + 1), nsp, gerr, worst], dtype=np.float64)
+            out["prompt9"] = np.array(prompt9, dtype=np.int32)
+        path = os.path.join(HERE, f"whisper_dec_{case}.npz")
+        np.savez_compressed(path, **out)
+        print(f"  wrote {path} ({os.path.getsize(path)} bytes)")
+
+
+if __name__ == "__main__":
+    main()

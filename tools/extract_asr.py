@@ -1,0 +1,54 @@
+#!/usr/bin/env python
+"""Every ``.wav`` of a directory -> an ``.srt`` beside its name, with ``hirest_amd.whisper``: the arguments and the option block of the
+reference's ``extraction/whisper_ASR/extract_ASR.py``, our own code against our own API.
+
+    python tools/extract_asr.py --model /models/whisper-small.en --audio_dir data/audio --asr_dir data/ASR
+
+``--model`` is a local OpenAI ``.pt`` checkpoint or a Hugging Face model directory, never a model name: nothing is downloaded.
+``--tokenizer`` is a directory with ``vocab.json`` and ``merges.txt`` (default: the model directory).
+"""
+import argparse
+import os
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from hirest_amd import whisper  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--model", type=str, required=True, help="local .pt checkpoint or Hugging Face model directory")
+    ap.add_argument("--audio_dir", type=str, required=True)
+    ap.add_argument("--asr_dir", type=str, required=True)
+    ap.add_argument("--tokenizer", type=str, default=None, help="directory with vocab.json and merges.txt (default: --model)")
+    ap.add_argument("--device", type=str, default="cuda")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+    print(args)
+
+    model = whisper.load_model(args.model, args.device, tokenizer=args.tokenizer).eval()
+    print("Model loaded: ", args.model, "at device", model.device)
+
+    # the reference's option block.  Its first temperature is 0.15, so every window is sampled (best_of candidates) and the beam options
+    # are never used: transcribe() drops them above temperature 0.
+    temperature, temperature_increment_on_fallback = 0.15, 0.2
+    options = dict(language="English", task="transcribe", best_of=5, beam_size=5, patience=1.0, length_penalty=None, suppress_tokens="-1",
+                   initial_prompt=None, condition_on_previous_text=True, fp16=True, compression_ratio_threshold=2.4, logprob_threshold=-1.0,
+                   no_speech_threshold=0.6, seed=args.seed)
+    temperatures = tuple(np.arange(temperature, 1.0 + 1e-6, temperature_increment_on_fallback))
+
+    out_dir = Path(args.asr_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for wav in sorted(Path(args.audio_dir).glob("*.wav")):
+        result = whisper.transcribe(model, str(wav), temperature=temperatures, **options)
+        with open(out_dir / (wav.stem + ".srt"), "w", encoding="utf-8") as f:
+            whisper.utils.write_srt(result["segments"], file=f)
+        print(f"{wav.name}: {len(result['segments'])} segments")
+
+
+if __name__ == "__main__":
+    main()
