@@ -41,6 +41,22 @@ class GemmArgs(C.Structure):
         return cls(C.sizeof(cls), *fields)
 
 
+F32_ENTRY = {"gemm": 0, "ws": 1, "layouts": 2, "ln": 3, "ln_colmax": 4, "rows_colmax": 5}   # HIREST_F32_ENTRY_*
+
+
+class GemmF32Query(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32)] + \
+               [(n, C.c_int32) for n in ("entry", "M", "N", "K", "has_resid", "has_periodic", "has_ids", "has_ln_out", "has_workspace",
+                                         "a_kmajor", "w_kmajor", "select_kernel", "ring_mode", "rows_ln_mode", "cus")]
+
+    @classmethod
+    def make(cls, entry, M, N, K, **fields):
+        """Query for entry point `entry` (a key of F32_ENTRY); switches default to -1 (the process's current value), cus to 0."""
+        q = cls(C.sizeof(cls), F32_ENTRY[entry], M, N, K, select_kernel=-1, ring_mode=-1, rows_ln_mode=-1)
+        for k, v in fields.items():
+            setattr(q, k, int(v))
+        return q
+
 
 class BlockWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b",
@@ -318,6 +334,7 @@ _SIGNATURES = {
     "hirest_caption_select": (C.c_int, [C.c_int32]),
     "hirest_gemm_f32_ln_colmax": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p,
                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "hirest_gemm_f32_dispatch_name": (C.c_int, [C.POINTER(GemmF32Query), C.c_char_p, C.c_int32]),
     "hirest_gemm_f32_rows_ln_mode": (C.c_int, [C.c_int32]),
     "hirest_gemm_f32_ring_mode": (C.c_int, [C.c_int32]),
     "hirest_gemm_f32_rows_preferred": (C.c_int, [C.c_int32]),

@@ -1189,9 +1189,7 @@ int launch_rows_stream(const GemmLN& q, int ng, int k, hipStream_t s) {
     return hirest_launch_status();
 }
 
-// M rows as ng groups of mt 16-row tiles (mt <= 5: MT x 48 fragment registers per wave) x 8 k column streams, one block per CU: the
-// split with the shortest block — tiles per stream x (MFMA time of a tile + its reduction) + the prologue (statistics, A phase)
-// hirest_gemm_f32_rows_ln_mode (A/B): 0 one block per CU, ring depth 12, 1 - 3 row tiles per wave; 1 / 2: one row tile per wave, ring depth 4,
+// hirest_gemm_f32_rows_ln_mode (A/B), read by f32_choose_rows below: 0 one block per CU, ring depth 12, 1 - 3 row tiles per wave; 1 / 2: one row tile per wave, ring depth 4,
 // one / two blocks per CU.  Default 2: the layer products of a merged search (160 x 2304 / 3072 x 768) are a few microseconds of matrix
 // time behind a LayerNorm prologue, and a second block per CU covers one block's prologue with the other's MFMAs (B = 32, beam 5:
 // 1735 -> 1800 captions/s; mode 1: 1755)
@@ -1200,41 +1198,6 @@ extern "C" int hirest_gemm_f32_rows_ln_mode(int32_t mode) {
     if (mode < 0 || mode > 2) return HIREST_E_BADARG;
     g_rows_ln_mode = mode;
     return 0;
-}
-template <bool LN>
-static int rows_stream(const GemmLN& q, hipStream_t s) {
-    static HirestDevCfg cfg;
-    int cus = 0;
-    if (int e = hirest_configure(gemm_f32_rows_stream_kernel<6, 1, 12, LN>, 160 * 1024, cfg, &cus)) return e;
-    const int per_xcd = cus / 8 < 1 ? 1 : cus / 8;          // blockIdx % 8 = XCD
-    const int tiles = (q.g.M + 15) / 16, ntile = (q.g.N + 15) / 16;
-    if (LN && g_rows_ln_mode) {
-        int k = (per_xcd * g_rows_ln_mode) / tiles; if (k < 1) k = 1;
-        if (8 * k > ntile) k = (ntile + 7) / 8;
-        return launch_rows_stream<6, 1, 4, LN>(q, tiles, k, s);
-    }
-    int best_mt = 0, best_ng = 0, best_k = 0;
-    int64_t best = 0;
-    for (int mt = 1; mt <= (LN ? 3 : 5); ++mt) {             // (the LayerNorm form of 4 / 5 row tiles does not fit the registers)
-        const int ng = (tiles + mt - 1) / mt;
-        int k = per_xcd / ng; if (k < 1) k = 1;
-        if (8 * k > ntile) k = (ntile + 7) / 8;
-        const int per_stream = (ntile + 8 * k - 1) / (8 * k);
-        const int64_t cost = (int64_t)per_stream * (mt * 6 * 8 * 42 + 800) + (int64_t)mt * (LN ? 2500 : 1500);
-        if (best_mt == 0 || cost < best) { best = cost; best_mt = mt; best_ng = ng; best_k = k; }
-    }
-    switch (best_mt) {
-        case 1: return launch_rows_stream<6, 1, 12, LN>(q, best_ng, best_k, s);
-        case 2: return launch_rows_stream<6, 2, 12, LN>(q, best_ng, best_k, s);
-        case 3: return launch_rows_stream<6, 3, 12, LN>(q, best_ng, best_k, s);
-        case 4: return launch_rows_stream<6, 4, 12, false>(q, best_ng, best_k, s);
-        default: return launch_rows_stream<6, 5, 12, false>(q, best_ng, best_k, s);
-    }
-}
-static int rows_stream_plain(const GemmF& p, float* colmax, hipStream_t s) {
-    if (p.resid || p.periodic) return HIREST_E_SHAPE;
-    GemmLN q{p, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, colmax};
-    return rows_stream<false>(q, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1758,83 +1721,311 @@ extern "C" int hirest_gemm_f32_select_kernel(int32_t which) {
     return 0;
 }
 
-extern "C" int hirest_gemm_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
-                               const float* resid, int64_t ldr, const float* periodic, int32_t period,
-                               float* out, int64_t ldo, int32_t M, int32_t N, int32_t K, int32_t act, void* stream) {
-    if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0 || act < 0 || act > 3) return HIREST_E_BADARG;
-    if (K % 16 != 0 || N % 4 != 0 || lda % 4 != 0 || ldw % 4 != 0 || (periodic && period <= 0)) return HIREST_E_SHAPE;
-    GemmF p{A, lda, W, ldw, bias, resid, ldr, periodic, period, out, ldo, M, N, K, act, nullptr};
+// ---- host side: one f32_choose_*() per entry point decides which kernel a call takes, launch_f32() maps that choice to the instantiation
+// and f32_name() to its name; the entry points launch the result and hirest_gemm_f32_dispatch_name prints it, so the two cannot disagree
+namespace {
+
+enum class F32Family { tile64, ring, skinny, m16, m16ln, m16ln_stream, rows };
+struct F32Choice {
+    int status = 0;                        // HIREST_E_* : no kernel takes this shape (the other members mean nothing then)
+    F32Family family = F32Family::tile64;
+    bool split = false;                    // tile64: one block per (tile, K quarter) into the workspace + gemm_f32_quarters_kernel
+    bool ak = false, wk = false;           // tile64: k-major operands
+    int t[4] = {0, 0, 0, 0};               // template arguments: ring <DEPTH>, m16 <MT, NT, DEPTH>, m16ln <NV, NT, DEPTH>, m16ln_stream <NV, MT, D0, D1>
+    bool ln = false;                       // rows: the LayerNorm form
+    int mt = 0, ng = 0, k = 0, mode = 0;   // rows: row tiles per wave, row groups, column streams / 8, hirest_gemm_f32_rows_ln_mode (ln only)
+};
+// What a decision looks at: the shape, which optional operands the call has, and the three process-wide switches.  No pointer, no stride.
+struct F32Query {
+    int M = 0, N = 0, K = 0;
+    bool resid = false, periodic = false;
+    bool ids = false, ln_out = false;      // hirest_gemm_f32_ln
+    bool ws = false;                       // a usable workspace: present, 16-byte aligned, at least 4 M N floats
+    bool ak = false, wk = false;           // hirest_gemm_f32_layouts
+    int sel = 0, ring = 0, rows_mode = 2;  // hirest_gemm_f32_select_kernel, hirest_gemm_f32_ring_mode, hirest_gemm_f32_rows_ln_mode
+};
+inline F32Choice f32_reject(int status) { F32Choice c; c.status = status; return c; }
+inline F32Choice f32_take(F32Family family, int t0 = 0, int t1 = 0, int t2 = 0, int t3 = 0) {
+    F32Choice c; c.family = family; c.t[0] = t0; c.t[1] = t1; c.t[2] = t2; c.t[3] = t3; return c;
+}
+
+// The decisions are pure host logic.  Two of them depend on the CU count, which `cus(family, n)` supplies when — and only when — such a
+// branch is reached (the entry points: hirest_configure of that family's kernel, as before; hirest_gemm_f32_dispatch_name: the
+// query's own figure); it returns a status.
+
+// M rows as ng groups of mt 16-row tiles (mt <= 5: MT x 48 fragment registers per wave) x 8 k column streams, one block per CU: the
+// split with the shortest block — tiles per stream x (MFMA time of a tile + its reduction) + the prologue (statistics, A phase)
+template <class Cus>
+F32Choice f32_choose_rows(const F32Query& q, bool ln, Cus&& cus) {
+    int ncu = 0;
+    if (int e = cus(F32Family::rows, ncu)) return f32_reject(e);
+    const int per_xcd = ncu / 8 < 1 ? 1 : ncu / 8;          // blockIdx % 8 = XCD
+    const int tiles = (q.M + 15) / 16, ntile = (q.N + 15) / 16;
+    F32Choice c = f32_take(F32Family::rows);
+    c.ln = ln;
+    if (ln && q.rows_mode) {
+        int k = (per_xcd * q.rows_mode) / tiles; if (k < 1) k = 1;
+        if (8 * k > ntile) k = (ntile + 7) / 8;
+        c.mt = 1; c.ng = tiles; c.k = k; c.mode = q.rows_mode;
+        return c;
+    }
+    int64_t best = 0;
+    for (int mt = 1; mt <= (ln ? 3 : 5); ++mt) {             // (the LayerNorm form of 4 / 5 row tiles does not fit the registers)
+        const int ng = (tiles + mt - 1) / mt;
+        int k = per_xcd / ng; if (k < 1) k = 1;
+        if (8 * k > ntile) k = (ntile + 7) / 8;
+        const int per_stream = (ntile + 8 * k - 1) / (8 * k);
+        const int64_t cost = (int64_t)per_stream * (mt * 6 * 8 * 42 + 800) + (int64_t)mt * (ln ? 2500 : 1500);
+        if (c.mt == 0 || cost < best) { best = cost; c.mt = mt; c.ng = ng; c.k = k; }
+    }
+    return c;
+}
+
+template <class Cus>
+F32Choice f32_choose_gemm(const F32Query& q, Cus&& cus) {
+    const int M = q.M, N = q.N, K = q.K;
+    if (K % 16 != 0 || N % 4 != 0) return f32_reject(HIREST_E_SHAPE);
     // 33 .. 256 rows (the sentence encoder's batches, the captioning task's training rows): the same kernel, 32-row tiles across
     // blockIdx.y — whole-line operand traffic beats the split-K kernel's lane = row loads (ASR encoder 108 -> 117 k sentences/s)
     // (a 3072-deep product is a chain of 192 dependent MFMAs per K quarter: one row tile per wave, i.e. twice the blocks, halves it)
-    if (M > 32 && M <= 256 && K % FK == 0 && g_f32_kernel == 0 && N < 8192)
-        return K >= 2048 ? launch_m16<1, 1, 4>(p, reinterpret_cast<hipStream_t>(stream)) : launch_m16<2, 1, 6>(p, reinterpret_cast<hipStream_t>(stream));
+    if (M > 32 && M <= 256 && K % FK == 0 && q.sel == 0 && N < 8192)
+        return K >= 2048 ? f32_take(F32Family::m16, 1, 1, 4) : f32_take(F32Family::m16, 2, 1, 6);
     // a merged beam search's LM head (60 - 160 rows x 30 522 columns): A fragments in registers, W streamed once per row group — when its row
     // groups pad the rows less than 64-row tiles do (96, 150, 160 rows; at 60, 100, 256 the 64x64 kernel below is faster: hirest_gemm_f32_rows_preferred)
-    if (M > 32 && M <= 256 && N >= 8192 && K == 768 && !resid && !periodic && g_f32_kernel == 0 && hirest_gemm_f32_rows_preferred(M))
-        return rows_stream_plain(p, nullptr, reinterpret_cast<hipStream_t>(stream));
+    if (M > 32 && M <= 256 && N >= 8192 && K == 768 && !q.resid && !q.periodic && q.sel == 0 && hirest_gemm_f32_rows_preferred(M))
+        return f32_choose_rows(q, false, cus);
     // other wide problems of 48 - 256 rows: the 64x64 kernel beats the split-K kernel's lane = row loads from 60 rows on (LM head: 63 vs 97 us at
     // 96 rows, 93 vs 150 at 160)
-    if (M >= 48 && M <= 256 && N >= 8192 && g_f32_kernel == 0) {
-        hipLaunchKernelGGL((gemm_f32_kernel<false, false>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
-        return hirest_launch_status();
-    }
-    if (M <= 32 && K % FK == 0 && g_f32_kernel == 0) {
-        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (M >= 48 && M <= 256 && N >= 8192 && q.sel == 0) return f32_take(F32Family::tile64);
+    if (M <= 32 && K % FK == 0 && q.sel == 0) {
         // one row tile per block for the decoder's layers (2 x N / 16 blocks share the operand traffic; 8 slabs in flight per wave,
         // 3 for the 2304- / 3072-wide ones so that two blocks fit a CU: +3 % per word); the LM head without a LayerNorm prologue
         // (hirest_gemm_f32_ln has its own): both row tiles and two column tiles per wave, two slabs in flight (best of 2 / 3 / 4)
-        if (N < 2048) return launch_m16<1, 1, 8>(p, s);
-        if (N < 8192) return launch_m16<1, 1, 3>(p, s);
-        return M <= 16 ? launch_m16<1, 2, 6>(p, s) : launch_m16<2, 2, 2>(p, s);
+        if (N < 2048) return f32_take(F32Family::m16, 1, 1, 8);
+        if (N < 8192) return f32_take(F32Family::m16, 1, 1, 3);
+        return M <= 16 ? f32_take(F32Family::m16, 1, 2, 6) : f32_take(F32Family::m16, 2, 2, 2);
     }
-    if (M <= 256 && g_f32_kernel != 1) {
-        hipLaunchKernelGGL(gemm_f32_skinny_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
-        return hirest_launch_status();
-    }
+    if (M <= 256 && q.sel != 1) return f32_take(F32Family::skinny);
     // row-major operands in whole 32-deep slabs, dozens of tiles per CU (the fp32 towers' layers): the LDS-DMA ring form of the same tile (same
     // bits), 4 slots and two blocks per CU: 105 -> 111 TFLOP/s at 65 792 rows.  Below ~64 tiles per CU the register-prefetch form with its four
     // blocks per CU is as fast or faster (9600 x 3072 x 768: 103 vs 100), and a deeper ring with one block per CU loses everywhere — a lone wave per
     // SIMD pays for its own DMA issue and fragment latency (profiles/r05/gemm_f32_ring_ab.txt)
-    if (g_f32_kernel == 0 && g_f32_ring != 1 && K % FK == 0 && K >= 2 * FK) {
-        int cus = 0; static HirestDevCfg cfg;
-        if (int e = hirest_configure(gemm_f32_ring_kernel<4>, 4 * 16384, cfg, &cus)) return e;
+    if (q.sel == 0 && q.ring != 1 && K % FK == 0 && K >= 2 * FK) {
+        int ncu = 0;
+        if (int e = cus(F32Family::ring, ncu)) return f32_reject(e);
         const int64_t tiles = (int64_t)((M + 63) / 64) * ((N + 63) / 64);
-        if (g_f32_ring == 2 || tiles >= 64 * (int64_t)cus) return launch_ring<4>(p, reinterpret_cast<hipStream_t>(stream));
+        if (q.ring == 2 || tiles >= 64 * (int64_t)ncu) return f32_take(F32Family::ring, 4);
     }
-    hipLaunchKernelGGL((gemm_f32_kernel<false, false>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
-    return hirest_launch_status();
+    return f32_take(F32Family::tile64);
 }
 
 // Split form of the 64x64 kernel for problems with few tiles (see gemm_f32_kernel): taken for 256 < M, at most 512 tiles, K >= 1024
 // (same box, B = 5, T = 300: segmentation 330 -> 371 videos/s, retrieval 5400 -> 5800, training step 5.85 -> 5.55 ms; thresholds of
 // 512 .. 2048 for K and 400 .. 1200 tiles measure the same: the gain is the K = 3072 layer)
-static bool splits(int M, int N, int K) {
+bool f32_splits(int sel, int M, int N, int K) {
     const int64_t tiles = (int64_t)((M + 63) / 64) * ((N + 63) / 64);
     // (round 5 lowered the threshold to K = 512 — 1500 x 768 x 768, 288 tiles: 38.4 -> 33.6 us, ~1 % of an inference batch — and that is what took
     //  the training step from 3.07 to 3.45 ms between the round-4 and round-5 bench lines: its dX / dW products at K = 768 each gained a reduce
     //  launch on a launch-bound step.  Same box, same build, round 6: 3.23 / 3.57 ms at 512 against 3.05 / 3.25 at 1024
     //  (profiles/r06/train_bisect.txt).  Back to 1024; HIREST_F32_SPLIT_MIN_K = A/B of the threshold.)
     static const int min_k = [] { const char* e = getenv("HIREST_F32_SPLIT_MIN_K"); return e ? atoi(e) : 1024; }();
-    return g_f32_kernel == 0 && M > 256 && tiles <= 512 && K >= min_k;
+    return sel == 0 && M > 256 && tiles <= 512 && K >= min_k;
 }
+template <class Cus>
+F32Choice f32_choose_ws(const F32Query& q, Cus&& cus) {
+    if (q.K % 16 != 0 || q.N % 4 != 0) return f32_reject(HIREST_E_SHAPE);
+    if (!f32_splits(q.sel, q.M, q.N, q.K) || !q.ws) return f32_choose_gemm(q, cus);
+    F32Choice c = f32_take(F32Family::tile64);
+    c.split = true;
+    return c;
+}
+
+// the 64x64 kernel for every size (the few-row kernels read row-major operands only); split form as in hirest_gemm_f32_ws
+F32Choice f32_choose_layouts(const F32Query& q) {
+    if (q.N % 4 != 0 || (q.ak ? (q.M % 4 != 0 || q.M < 4) : q.K % 4 != 0) || (q.wk ? q.N < 4 : q.K % 4 != 0)) return f32_reject(HIREST_E_SHAPE);
+    const int64_t tiles = (int64_t)((q.M + 63) / 64) * ((q.N + 63) / 64);
+    F32Choice c = f32_take(F32Family::tile64);
+    c.ak = q.ak; c.wk = q.wk;
+    c.split = tiles <= 512 && q.K >= 1024 && q.ws;
+    return c;
+}
+
+template <class Cus>
+F32Choice f32_choose_ln(const F32Query& q, Cus&& cus) {
+    const int M = q.M, N = q.N, K = q.K;
+    // the 16-row blocks of the layer form tile any number of rows across blockIdx.y (a merged beam search: 60 - 160 rows per word);
+    // the LM-head stream keeps all its rows in one block's registers: 32 at most
+    if ((M > 256 && !(K == 768 && !q.resid)) || K % 256 != 0 || K > 1024 || N % 4 != 0) return f32_reject(HIREST_E_SHAPE);
+    // (narrow layers stay with the 16-row blocks below: 10 vs 12 us at 160 x 768; above 256 rows this is the only form)
+    // a merged search's rows: row groups x column streams, rows normalised once per block
+    if (M > 32 && K == 768 && !q.resid && (N >= 2048 || M > 256)) return f32_choose_rows(q, true, cus);
+    if (M > 32 && N >= 8192) return f32_reject(HIREST_E_SHAPE);
+    if (N >= 8192 && K == 768 && !q.ids && !q.ln_out) {      // the LM head: persistent blocks, rows normalised once per CU
+        // ring depth: D0 slabs per wave in the fixed region + D1 in the space of the A image (M rows x 3200 B shared by 4 MT waves)
+        if (M <= 2) return f32_take(F32Family::m16ln_stream, 3, 1, 8, 0);
+        if (M <= 5) return f32_take(F32Family::m16ln_stream, 3, 1, 8, 1);
+        if (M <= 7) return f32_take(F32Family::m16ln_stream, 3, 1, 8, 2);
+        if (M <= 10) return f32_take(F32Family::m16ln_stream, 3, 1, 8, 3);
+        if (M <= 12) return f32_take(F32Family::m16ln_stream, 3, 1, 8, 4);
+        if (M <= 16) return f32_take(F32Family::m16ln_stream, 3, 1, 8, 5);
+        if (M <= 20) return f32_take(F32Family::m16ln_stream, 3, 2, 4, 3);
+        if (M <= 26) return f32_take(F32Family::m16ln_stream, 3, 2, 4, 4);
+        return f32_take(F32Family::m16ln_stream, 3, 2, 2, 5);
+    }
+    if (N >= 8192) return f32_reject(HIREST_E_SHAPE);
+    // NV = K / 256; two W slabs in flight per wave (66 KB of LDS at K = 768, two blocks per CU: best of 2 / 3 / 6; two column tiles
+    // per wave for the wide layers measured no better)
+    return f32_take(F32Family::m16ln, K / 256, 1, 2);
+}
+
+template <class Cus>
+F32Choice f32_choose_rows_colmax(const F32Query& q, Cus&& cus) {
+    if (q.K != 768 || q.M > 1280 || q.N % 4 != 0) return f32_reject(HIREST_E_SHAPE);
+    return f32_choose_rows(q, false, cus);
+}
+
+// The entry points' CU count: that of the current device, recorded by hirest_configure of the kernel family that wants it
+int f32_device_cus(F32Family family, int& ncu) {
+    static HirestDevCfg ring_cfg, rows_cfg;
+    if (family == F32Family::ring) return hirest_configure(gemm_f32_ring_kernel<4>, 4 * 16384, ring_cfg, &ncu);
+    return hirest_configure(gemm_f32_rows_stream_kernel<6, 1, 12, false>, 160 * 1024, rows_cfg, &ncu);
+}
+
+constexpr int f32_key(int a, int b, int c, int d = 0) { return ((a * 16 + b) * 16 + c) * 16 + d; }
+
+// Launches the chosen instantiation.  q.g is the plain product's argument block (q.g.ws set for a split choice); the LayerNorm
+// members are read by the m16ln / m16ln_stream / rows<ln> kernels only, q.colmax by m16ln_stream and rows.
+int launch_f32(const F32Choice& c, const GemmLN& q, hipStream_t s) {
+    const GemmF& p = q.g;
+    const int key = f32_key(c.t[0], c.t[1], c.t[2], c.t[3]);
+    switch (c.family) {
+        case F32Family::tile64: {
+            const dim3 grid((p.N + 63) / 64, (p.M + 63) / 64, c.split ? 4 : 1), blk(256);
+            if (c.ak && c.wk) hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, blk, 0, s, p);
+            else if (c.ak) hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, blk, 0, s, p);
+            else if (c.wk) hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, blk, 0, s, p);
+            else hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, blk, 0, s, p);
+            if (c.split) {
+                const int64_t n = (int64_t)p.M * (p.N / 4);
+                hipLaunchKernelGGL(gemm_f32_quarters_kernel, dim3((unsigned)((n + 255) / 256)), blk, 0, s, p);
+            }
+            return hirest_launch_status();
+        }
+        case F32Family::ring: return launch_ring<4>(p, s);
+        case F32Family::skinny:
+            hipLaunchKernelGGL(gemm_f32_skinny_kernel, dim3((p.N + 31) / 32, (p.M + 31) / 32), dim3(256), 0, s, p);
+            return hirest_launch_status();
+        case F32Family::m16:
+            switch (key) {
+                case f32_key(1, 1, 8): return launch_m16<1, 1, 8>(p, s);
+                case f32_key(1, 1, 3): return launch_m16<1, 1, 3>(p, s);
+                case f32_key(1, 2, 6): return launch_m16<1, 2, 6>(p, s);
+                case f32_key(2, 2, 2): return launch_m16<2, 2, 2>(p, s);
+                case f32_key(2, 1, 6): return launch_m16<2, 1, 6>(p, s);
+                case f32_key(1, 1, 4): return launch_m16<1, 1, 4>(p, s);
+                default: return HIREST_E_BADARG;
+            }
+        case F32Family::m16ln:
+            switch (key) {
+                case f32_key(1, 1, 2): return launch_m16ln<1, 1, 2>(q, s);
+                case f32_key(2, 1, 2): return launch_m16ln<2, 1, 2>(q, s);
+                case f32_key(3, 1, 2): return launch_m16ln<3, 1, 2>(q, s);
+                case f32_key(4, 1, 2): return launch_m16ln<4, 1, 2>(q, s);
+                default: return HIREST_E_BADARG;
+            }
+        case F32Family::m16ln_stream: {
+            constexpr int MAXLDS = 160 * 1024;
+            switch (key) {
+                case f32_key(3, 1, 8, 0): return launch_m16ln_stream<3, 1, 8, 0>(q, s, MAXLDS);
+                case f32_key(3, 1, 8, 1): return launch_m16ln_stream<3, 1, 8, 1>(q, s, MAXLDS);
+                case f32_key(3, 1, 8, 2): return launch_m16ln_stream<3, 1, 8, 2>(q, s, MAXLDS);
+                case f32_key(3, 1, 8, 3): return launch_m16ln_stream<3, 1, 8, 3>(q, s, MAXLDS);
+                case f32_key(3, 1, 8, 4): return launch_m16ln_stream<3, 1, 8, 4>(q, s, MAXLDS);
+                case f32_key(3, 1, 8, 5): return launch_m16ln_stream<3, 1, 8, 5>(q, s, MAXLDS);
+                case f32_key(3, 2, 4, 3): return launch_m16ln_stream<3, 2, 4, 3>(q, s, MAXLDS);
+                case f32_key(3, 2, 4, 4): return launch_m16ln_stream<3, 2, 4, 4>(q, s, MAXLDS);
+                case f32_key(3, 2, 2, 5): return launch_m16ln_stream<3, 2, 2, 5>(q, s, MAXLDS);
+                default: return HIREST_E_BADARG;
+            }
+        }
+        case F32Family::rows:
+            if (p.resid || p.periodic) return HIREST_E_SHAPE;
+            if (c.ln && c.mode) return launch_rows_stream<6, 1, 4, true>(q, c.ng, c.k, s);
+            switch (c.mt + (c.ln ? 8 : 0)) {
+                case 1: return launch_rows_stream<6, 1, 12, false>(q, c.ng, c.k, s);
+                case 2: return launch_rows_stream<6, 2, 12, false>(q, c.ng, c.k, s);
+                case 3: return launch_rows_stream<6, 3, 12, false>(q, c.ng, c.k, s);
+                case 4: return launch_rows_stream<6, 4, 12, false>(q, c.ng, c.k, s);
+                case 5: return launch_rows_stream<6, 5, 12, false>(q, c.ng, c.k, s);
+                case 9: return launch_rows_stream<6, 1, 12, true>(q, c.ng, c.k, s);
+                case 10: return launch_rows_stream<6, 2, 12, true>(q, c.ng, c.k, s);
+                case 11: return launch_rows_stream<6, 3, 12, true>(q, c.ng, c.k, s);
+                default: return HIREST_E_BADARG;
+            }
+    }
+    return HIREST_E_BADARG;
+}
+
+void f32_name(const F32Choice& c, char* out, size_t len) {
+    switch (c.family) {
+        case F32Family::tile64:
+            snprintf(out, len, "tile64%s%s", c.ak && c.wk ? "<ak,wk>" : c.ak ? "<ak>" : c.wk ? "<wk>" : "", c.split ? ".split" : "");
+            return;
+        case F32Family::ring: snprintf(out, len, "ring<%d>", c.t[0]); return;
+        case F32Family::skinny: snprintf(out, len, "skinny"); return;
+        case F32Family::m16: snprintf(out, len, "m16<%d,%d,%d>", c.t[0], c.t[1], c.t[2]); return;
+        case F32Family::m16ln: snprintf(out, len, "m16ln<%d,%d,%d>", c.t[0], c.t[1], c.t[2]); return;
+        case F32Family::m16ln_stream: snprintf(out, len, "m16ln_stream<%d,%d,%d,%d>", c.t[0], c.t[1], c.t[2], c.t[3]); return;
+        case F32Family::rows:
+            if (c.ln) snprintf(out, len, "rows<mt=%d,ln,mode=%d>", c.mt, c.mode);
+            else snprintf(out, len, "rows<mt=%d>", c.mt);
+            return;
+    }
+}
+
+GemmLN f32_plain(const GemmF& p, float* colmax = nullptr) {
+    return GemmLN{p, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, colmax};
+}
+// the epilogue stores and loads 16-byte vectors at out + m * ldo + n and resid + m * ldr + n (n % 4 == 0); rows must not overlap
+inline bool f32_bad_out_strides(int64_t ldo, const float* resid, int64_t ldr, int N) {
+    return ldo % 4 != 0 || ldo < N || (resid && (ldr % 4 != 0 || ldr < N));
+}
+
+}  // namespace
+
+extern "C" int hirest_gemm_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
+                               const float* resid, int64_t ldr, const float* periodic, int32_t period,
+                               float* out, int64_t ldo, int32_t M, int32_t N, int32_t K, int32_t act, void* stream) {
+    if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0 || act < 0 || act > 3) return HIREST_E_BADARG;
+    if (lda % 4 != 0 || ldw % 4 != 0 || (periodic && period <= 0) || f32_bad_out_strides(ldo, resid, ldr, N)) return HIREST_E_SHAPE;
+    F32Query q;
+    q.M = M; q.N = N; q.K = K; q.resid = resid != nullptr; q.periodic = periodic != nullptr;
+    q.sel = g_f32_kernel; q.ring = g_f32_ring; q.rows_mode = g_rows_ln_mode;
+    const F32Choice c = f32_choose_gemm(q, f32_device_cus);
+    if (c.status) return c.status;
+    const GemmF p{A, lda, W, ldw, bias, resid, ldr, periodic, period, out, ldo, M, N, K, act, nullptr};
+    return launch_f32(c, f32_plain(p), reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" size_t hirest_gemm_f32_workspace_bytes(int32_t M, int32_t N, int32_t K) {
-    return (M > 0 && N > 0 && K > 0 && splits(M, N, K)) ? (size_t)4 * M * N * 4 : 0;
+    return (M > 0 && N > 0 && K > 0 && f32_splits(g_f32_kernel, M, N, K)) ? (size_t)4 * M * N * 4 : 0;
+}
+static bool f32_usable_ws(const void* workspace, size_t workspace_bytes, int M, int N) {
+    return workspace && workspace_bytes >= (size_t)4 * M * N * 4 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0;
 }
 extern "C" int hirest_gemm_f32_ws(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* resid,
                                   int64_t ldr, const float* periodic, int32_t period, float* out, int64_t ldo, int32_t M, int32_t N,
                                   int32_t K, int32_t act, void* workspace, size_t workspace_bytes, void* stream) {
     if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0 || act < 0 || act > 3) return HIREST_E_BADARG;
-    if (K % 16 != 0 || N % 4 != 0 || lda % 4 != 0 || ldw % 4 != 0 || (periodic && period <= 0)) return HIREST_E_SHAPE;
-    const size_t need = hirest_gemm_f32_workspace_bytes(M, N, K);
-    if (need == 0 || !workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
-        return hirest_gemm_f32(A, lda, W, ldw, bias, resid, ldr, periodic, period, out, ldo, M, N, K, act, stream);
-    GemmF p{A, lda, W, ldw, bias, resid, ldr, periodic, period, out, ldo, M, N, K, act, static_cast<float*>(workspace)};
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL((gemm_f32_kernel<false, false>), dim3((N + 63) / 64, (M + 63) / 64, 4), dim3(256), 0, s, p);
-    const int64_t n = (int64_t)M * (N / 4);
-    hipLaunchKernelGGL(gemm_f32_quarters_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
-    return hirest_launch_status();
+    if (lda % 4 != 0 || ldw % 4 != 0 || (periodic && period <= 0) || f32_bad_out_strides(ldo, resid, ldr, N)) return HIREST_E_SHAPE;
+    F32Query q;
+    q.M = M; q.N = N; q.K = K; q.resid = resid != nullptr; q.periodic = periodic != nullptr;
+    q.ws = f32_usable_ws(workspace, workspace_bytes, M, N);
+    q.sel = g_f32_kernel; q.ring = g_f32_ring; q.rows_mode = g_rows_ln_mode;
+    const F32Choice c = f32_choose_ws(q, f32_device_cus);
+    if (c.status) return c.status;
+    const GemmF p{A, lda, W, ldw, bias, resid, ldr, periodic, period, out, ldo, M, N, K, act, c.split ? static_cast<float*>(workspace) : nullptr};
+    return launch_f32(c, f32_plain(p), reinterpret_cast<hipStream_t>(stream));
 }
 
 static thread_local float* g_ln_colmax = nullptr;       // set by hirest_gemm_f32_ln_colmax around its call of hirest_gemm_f32_ln
@@ -1843,40 +2034,15 @@ extern "C" int hirest_gemm_f32_ln(const float* X, int64_t ldx, const int32_t* id
                                   int64_t ldw, const float* bias, const float* resid, int64_t ldr, float* out, int64_t ldo, int32_t M,
                                   int32_t N, int32_t K, int32_t act, void* stream) {
     if ((!X && !(ids && table && pos_row)) || !gamma || !beta || !W || !out || M <= 0 || N <= 0 || K <= 0 || act < 0 || act > 3) return HIREST_E_BADARG;
-    // the 16-row blocks of the layer form tile any number of rows across blockIdx.y (a merged beam search: 60 - 160 rows per word);
-    // the LM-head stream keeps all its rows in one block's registers: 32 at most
-    if ((M > 256 && !(K == 768 && !resid)) || K % 256 != 0 || K > 1024 || N % 4 != 0 || ldw % 4 != 0 || (X && ldx % 4 != 0) || (ln_out && ldl % 4 != 0)) return HIREST_E_SHAPE;
-    // (narrow layers stay with the 16-row blocks below: 10 vs 12 us at 160 x 768; above 256 rows this is the only form)
-    if (M > 32 && K == 768 && !resid && (N >= 2048 || M > 256)) {   // a merged search's rows: row groups x column streams, rows normalised once per block
-        GemmLN qs{GemmF{nullptr, 0, W, ldw, bias, nullptr, 0, nullptr, 0, out, ldo, M, N, K, act, nullptr}, X, ldx, ids, table, pos_row, gamma, beta, eps,
-                  ln_out, ldl, g_ln_colmax};
-        return rows_stream<true>(qs, reinterpret_cast<hipStream_t>(stream));
-    }
-    if (M > 32 && N >= 8192) return HIREST_E_SHAPE;
-    GemmLN q{GemmF{nullptr, 0, W, ldw, bias, resid, ldr, nullptr, 0, out, ldo, M, N, K, act, nullptr}, X, ldx, ids, table, pos_row, gamma, beta, eps,
-             ln_out, ldl, g_ln_colmax};
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (N >= 8192 && K == 768 && !ids && !ln_out) {          // the LM head: persistent blocks, rows normalised once per CU
-        // ring depth: D0 slabs per wave in the fixed region + D1 in the space of the A image (M rows x 3200 B shared by 4 MT waves)
-        constexpr int MAXLDS = 160 * 1024;
-        if (M <= 2) return launch_m16ln_stream<3, 1, 8, 0>(q, s, MAXLDS);
-        if (M <= 5) return launch_m16ln_stream<3, 1, 8, 1>(q, s, MAXLDS);
-        if (M <= 7) return launch_m16ln_stream<3, 1, 8, 2>(q, s, MAXLDS);
-        if (M <= 10) return launch_m16ln_stream<3, 1, 8, 3>(q, s, MAXLDS);
-        if (M <= 12) return launch_m16ln_stream<3, 1, 8, 4>(q, s, MAXLDS);
-        if (M <= 16) return launch_m16ln_stream<3, 1, 8, 5>(q, s, MAXLDS);
-        if (M <= 20) return launch_m16ln_stream<3, 2, 4, 3>(q, s, MAXLDS);
-        if (M <= 26) return launch_m16ln_stream<3, 2, 4, 4>(q, s, MAXLDS);
-        return launch_m16ln_stream<3, 2, 2, 5>(q, s, MAXLDS);
-    }
-    if (N >= 8192) return HIREST_E_SHAPE;
-    switch (K / 256) {
-        case 1: return launch_m16ln<1, 1, 2>(q, s);
-        case 2: return launch_m16ln<2, 1, 2>(q, s);
-        case 3: return launch_m16ln<3, 1, 2>(q, s);   // two W slabs in flight per wave (66 KB of LDS, two blocks per CU: best of 2 / 3 / 6;
-                                                      // two column tiles per wave for the wide layers measured no better)
-        default: return launch_m16ln<4, 1, 2>(q, s);
-    }
+    if (ldw % 4 != 0 || (X && ldx % 4 != 0) || (ln_out && (ldl % 4 != 0 || ldl < K)) || f32_bad_out_strides(ldo, resid, ldr, N)) return HIREST_E_SHAPE;
+    F32Query fq;
+    fq.M = M; fq.N = N; fq.K = K; fq.resid = resid != nullptr; fq.ids = ids != nullptr; fq.ln_out = ln_out != nullptr;
+    fq.sel = g_f32_kernel; fq.ring = g_f32_ring; fq.rows_mode = g_rows_ln_mode;
+    const F32Choice c = f32_choose_ln(fq, f32_device_cus);
+    if (c.status) return c.status;
+    const GemmLN q{GemmF{nullptr, 0, W, ldw, bias, resid, ldr, nullptr, 0, out, ldo, M, N, K, act, nullptr}, X, ldx, ids, table, pos_row, gamma, beta, eps,
+                   ln_out, ldl, g_ln_colmax};
+    return launch_f32(c, q, reinterpret_cast<hipStream_t>(stream));
 }
 
 // The LM-head form of hirest_gemm_f32_ln (N >= 8192, K = 768, no ids, no ln_out) that also reports, per row, the maximum of every
@@ -1907,37 +2073,72 @@ extern "C" int hirest_gemm_f32_rows_preferred(int32_t M) {
 extern "C" int hirest_gemm_f32_rows_colmax(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* out, int64_t ldo,
                                            float* colmax, int32_t M, int32_t N, int32_t K, void* stream) {
     if (!A || !W || !out || M <= 0 || N <= 0) return HIREST_E_BADARG;
-    if (K != 768 || M > 1280 || N % 4 != 0 || lda % 4 != 0 || ldw % 4 != 0 || ldo % 4 != 0) return HIREST_E_SHAPE;
-    GemmF p{A, lda, W, ldw, bias, nullptr, 0, nullptr, 0, out, ldo, M, N, K, 0, nullptr};
-    return rows_stream_plain(p, colmax, reinterpret_cast<hipStream_t>(stream));
+    if (lda % 4 != 0 || ldw % 4 != 0 || ldo % 4 != 0) return HIREST_E_SHAPE;
+    F32Query q;
+    q.M = M; q.N = N; q.K = K;
+    q.sel = g_f32_kernel; q.ring = g_f32_ring; q.rows_mode = g_rows_ln_mode;
+    const F32Choice c = f32_choose_rows_colmax(q, f32_device_cus);
+    if (c.status) return c.status;
+    const GemmF p{A, lda, W, ldw, bias, nullptr, 0, nullptr, 0, out, ldo, M, N, K, 0, nullptr};
+    return launch_f32(c, f32_plain(p, colmax), reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int hirest_gemm_f32_layouts(const float* A, int64_t lda, int32_t a_kmajor, const float* W, int64_t ldw, int32_t w_kmajor,
                                        const float* bias, const float* resid, int64_t ldr, float* out, int64_t ldo, int32_t M, int32_t N,
                                        int32_t K, int32_t act, void* workspace, size_t workspace_bytes, void* stream) {
     if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0 || act < 0 || act > 3) return HIREST_E_BADARG;
-    if (N % 4 != 0 || lda % 4 != 0 || ldw % 4 != 0 || (a_kmajor ? (M % 4 != 0 || M < 4) : K % 4 != 0) || (w_kmajor ? N < 4 : K % 4 != 0)) return HIREST_E_SHAPE;
-    GemmF p{A, lda, W, ldw, bias, resid, ldr, nullptr, 0, out, ldo, M, N, K, act, nullptr};
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // the 64x64 kernel for every size (the few-row kernels read row-major operands only); split form as in hirest_gemm_f32_ws
-    const int64_t tiles = (int64_t)((M + 63) / 64) * ((N + 63) / 64);
-    const bool split = tiles <= 512 && K >= 1024 && workspace && workspace_bytes >= (size_t)4 * M * N * 4 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0;
-    if (split) p.ws = static_cast<float*>(workspace);
-    const dim3 grid((N + 63) / 64, (M + 63) / 64, split ? 4 : 1), blk(256);
-    if (a_kmajor && w_kmajor) hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, blk, 0, s, p);
-    else if (a_kmajor) hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, blk, 0, s, p);
-    else if (w_kmajor) hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, blk, 0, s, p);
-    else hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, blk, 0, s, p);
-    if (split) {
-        const int64_t n = (int64_t)M * (N / 4);
-        hipLaunchKernelGGL(gemm_f32_quarters_kernel, dim3((unsigned)((n + 255) / 256)), blk, 0, s, p);
-    }
-    return hirest_launch_status();
+    if (lda % 4 != 0 || ldw % 4 != 0 || f32_bad_out_strides(ldo, resid, ldr, N)) return HIREST_E_SHAPE;
+    F32Query q;
+    q.M = M; q.N = N; q.K = K; q.resid = resid != nullptr; q.ak = a_kmajor != 0; q.wk = w_kmajor != 0;
+    q.ws = f32_usable_ws(workspace, workspace_bytes, M, N);
+    const F32Choice c = f32_choose_layouts(q);
+    if (c.status) return c.status;
+    const GemmF p{A, lda, W, ldw, bias, resid, ldr, nullptr, 0, out, ldo, M, N, K, act, c.split ? static_cast<float*>(workspace) : nullptr};
+    return launch_f32(c, f32_plain(p), reinterpret_cast<hipStream_t>(stream));
 }
 extern "C" size_t hirest_gemm_f32_layouts_workspace_bytes(int32_t M, int32_t N, int32_t K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     const int64_t tiles = (int64_t)((M + 63) / 64) * ((N + 63) / 64);
     return (tiles <= 512 && K >= 1024) ? (size_t)4 * M * N * 4 : 0;
+}
+
+// Which kernel the fp32 entry point `query->entry` launches for this shape, these optional operands and these switch values — the same
+// f32_choose_*() answer the entry point launches; no launch.  With query->cus set it asks nothing of a device.
+extern "C" int hirest_gemm_f32_dispatch_name(const hirest_gemm_f32_query* a, char* out, int32_t out_len) {
+    if (!a || a->struct_size != sizeof(hirest_gemm_f32_query) || !out || out_len < 48) return HIREST_E_BADARG;
+    if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->cus < 0) return HIREST_E_BADARG;
+    if (a->select_kernel < -1 || a->select_kernel > 2 || a->ring_mode < -1 || a->ring_mode > 2 || a->rows_ln_mode < -1 || a->rows_ln_mode > 2) return HIREST_E_BADARG;
+    F32Query q;
+    q.M = a->M; q.N = a->N; q.K = a->K;
+    q.resid = a->has_resid != 0; q.periodic = a->has_periodic != 0; q.ids = a->has_ids != 0; q.ln_out = a->has_ln_out != 0;
+    q.ws = a->has_workspace != 0; q.ak = a->a_kmajor != 0; q.wk = a->w_kmajor != 0;
+    q.sel = a->select_kernel < 0 ? (int)g_f32_kernel : a->select_kernel;
+    q.ring = a->ring_mode < 0 ? (int)g_f32_ring : a->ring_mode;
+    q.rows_mode = a->rows_ln_mode < 0 ? (int)g_rows_ln_mode : a->rows_ln_mode;
+    const int fixed = a->cus;
+    auto cus = [fixed](F32Family, int& ncu) {
+        if (fixed > 0) { ncu = fixed; return 0; }
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+        return (int)e;
+    };
+    F32Choice c;
+    switch (a->entry) {
+        case HIREST_F32_ENTRY_GEMM: c = f32_choose_gemm(q, cus); break;
+        case HIREST_F32_ENTRY_WS: c = f32_choose_ws(q, cus); break;
+        case HIREST_F32_ENTRY_LAYOUTS: c = f32_choose_layouts(q); break;
+        case HIREST_F32_ENTRY_LN_COLMAX:
+            if (q.N < 8192 || q.K != 768) return HIREST_E_SHAPE;
+            q.resid = q.ids = q.ln_out = false;
+            [[fallthrough]];
+        case HIREST_F32_ENTRY_LN: c = f32_choose_ln(q, cus); break;
+        case HIREST_F32_ENTRY_ROWS_COLMAX: c = f32_choose_rows_colmax(q, cus); break;
+        default: return HIREST_E_BADARG;
+    }
+    if (c.status) return c.status;
+    f32_name(c, out, (size_t)out_len);
+    return 0;
 }
 
 extern "C" int hirest_attention_f32(const float* qkv, float* out, int32_t B, int32_t T, int32_t H, int32_t dh,

@@ -494,7 +494,14 @@ int hirest_vision_forward_x3(const hirest_vision_tower_x3* t, const void* frames
 /* out = act(A @ W^T + bias) (+ resid) (+ periodic[m % period]) in exact fp32 (k-ordered fmaf chain on
  * v_mfma_f32_32x32x2_f32).  act: 0 none, 1 gelu(erf), 2 tanh, 3 quick-gelu.  K % 16 == 0, N % 4 == 0.
  * Replaces the nn.Linear layers of the fusion, VisualEmbeddings (periodic = position embeddings),
- * VisualSelfOutput / VisualOutput (resid = the residual that precedes the post-LayerNorm). */
+ * VisualSelfOutput / VisualOutput (resid = the residual that precedes the post-LayerNorm).
+ * Strides (in floats), for this call and for _ws, _layouts, _ln and _ln_colmax below (HIREST_E_SHAPE otherwise, before any launch):
+ *   lda % 4 == 0, ldw % 4 == 0;  ldo % 4 == 0 and ldo >= N;  with resid: ldr % 4 == 0 and ldr >= N (the epilogue moves 16-byte vectors
+ *   at out + m * ldo + n and resid + m * ldr + n, n % 4 == 0);  hirest_gemm_f32_ln with ln_out: ldl % 4 == 0 and ldl >= K.
+ *   periodic has no stride argument: row r of it, r < period, starts at periodic + r * N.
+ *   lda < K is legal for a row-major A: the rows then overlap (A[m, k] = base[m * lda + k], the k = 3 convolutions of the Whisper
+ *   stem).  Every kernel clamps its row index to M - 1 and its loads of row m to the K floats from A + m * lda, so the call reads
+ *   nothing outside the (M - 1) * lda + K floats of the view, which the caller must own. */
 int hirest_gemm_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
                     const float* resid, int64_t ldr, const float* periodic, int32_t period,
                     float* out, int64_t ldo, int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
@@ -550,6 +557,32 @@ int hirest_gemm_f32_rows_ln_mode(int32_t mode);
 int hirest_gemm_f32_rows_preferred(int32_t M);
 int hirest_gemm_f32_rows_colmax(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* out, int64_t ldo,
                                 float* colmax, int32_t M, int32_t N, int32_t K, void* stream);
+/* Which kernel one of the fp32 entry points above launches for a call: the entry point's own dispatch decision, asked without operands
+ * and without a launch.  The decision looks at the shape, at which optional operands the call has, at whether it has a usable
+ * workspace (not NULL, 16-byte aligned, at least 4 M N floats: _ws and _layouts), at the three A/B switches and — in two places, the
+ * LDS-DMA ring threshold and the row-group split — at the CU count.  Switch fields: a value, or -1 for the process's current one.
+ * cus: the CU count to decide with; 0 asks the current device where the decision needs it, any other value makes the answer
+ * computable on a machine without a GPU.  Writes e.g. "tile64", "tile64.split", "tile64<ak,wk>", "ring<4>", "skinny", "m16<1,1,8>",
+ * "m16ln<3,1,2>", "m16ln_stream<3,2,4,3>", "rows<mt=3>", "rows<mt=1,ln,mode=2>" (template arguments as in csrc/joint.hip).
+ * out_len >= 48.  Returns the HIREST_E_* status the entry point returns for a shape that no kernel takes. */
+#define HIREST_F32_ENTRY_GEMM 0         /* hirest_gemm_f32 */
+#define HIREST_F32_ENTRY_WS 1           /* hirest_gemm_f32_ws */
+#define HIREST_F32_ENTRY_LAYOUTS 2      /* hirest_gemm_f32_layouts */
+#define HIREST_F32_ENTRY_LN 3           /* hirest_gemm_f32_ln */
+#define HIREST_F32_ENTRY_LN_COLMAX 4    /* hirest_gemm_f32_ln_colmax */
+#define HIREST_F32_ENTRY_ROWS_COLMAX 5  /* hirest_gemm_f32_rows_colmax */
+typedef struct hirest_gemm_f32_query {
+    uint32_t struct_size;                     /* sizeof(hirest_gemm_f32_query) */
+    int32_t entry;                            /* HIREST_F32_ENTRY_* */
+    int32_t M, N, K;
+    int32_t has_resid, has_periodic;          /* not NULL in the call */
+    int32_t has_ids, has_ln_out;              /* hirest_gemm_f32_ln */
+    int32_t has_workspace;                    /* _ws, _layouts: a usable workspace */
+    int32_t a_kmajor, w_kmajor;               /* _layouts */
+    int32_t select_kernel, ring_mode, rows_ln_mode;   /* hirest_gemm_f32_select_kernel / _ring_mode / _rows_ln_mode value, or -1: the current one */
+    int32_t cus;                              /* 0: ask the device */
+} hirest_gemm_f32_query;
+int hirest_gemm_f32_dispatch_name(const hirest_gemm_f32_query* query, char* out, int32_t out_len);
 /* softmax(fl(fl(q.k*scale) + add_const)) v over packed fp32 qkv [B*T, 3*H*dh]; no key masking (the
  * reference passes an all-zeros mask, i.e. add_const = -10000 on every score: SURVEY hazard H3).  dh: any multiple of 4 up to 96
  * (instantiations for 32, 64 and 96 columns; a head gives the same bits in each one that holds it); blocks of one wave (sequences of

@@ -1,5 +1,5 @@
-"""Inputs whose results are known without a tolerance, and the fp64 references that go with them, for tests/test_gpu_gemm_exact.py and
-tests/test_gpu_attention_edges.py.  tests/test_exact_inputs_host.py checks every precondition stated here on the CPU, so a wrong
+"""Inputs whose results are known without a tolerance, and the fp64 references that go with them, for tests/test_gpu_gemm_exact.py,
+tests/test_gpu_attention_edges.py and tests/test_gpu_gemm_f32_exact.py.  tests/test_exact_inputs_host.py checks every precondition stated here on the CPU, so a wrong
 generator cannot make a GPU test pass vacuously.  Not a test module.
 
 "Exact inputs" for the bf16 GEMM: operands are small integers (or integers times a power of two), so every product and every
@@ -314,4 +314,162 @@ def attention_launchers_all():
             out.add(("launch3", dh, 17, True, False, variant))
             out.add(("launch3", dh, 17, False, False, variant))
             out.add(("launch3", dh, 17, False, True, variant))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# fp32 GEMM family (csrc/joint.hip): tests/test_gpu_gemm_f32_exact.py
+# ------------------------------------------------------------------------------------------------------------------------------
+F32_WMAX, F32_EPI_MAX = 15, 8          # |w| <= 15; |bias|, |resid|, |periodic| <= 8: the three addends together stay below 24
+
+
+def f32_amax(K):
+    """Largest |a| at which sum_k |a| |w| + 24 < 2^24 for every row pair: fp32 accumulation is then exact in any order."""
+    return min(4095, (F32_EXACT - 1 - 3 * F32_EPI_MAX) // (F32_WMAX * K))
+
+
+_F32_CACHE = {}
+
+
+def gemm_f32_exact(M, N, K):
+    """a [M, K] fp32 integers in [-amax, amax] (amax = f32_amax(K): 4095, i.e. 12 significant bits, up to K = 273), w [N, K] in [-15, 15],
+    bias [N], resid [M, N], periodic [M + 3, N] in [-8, 8]; ref = a w^T (fp64).  Every 16th row of a is all +amax and two of every 8
+    rows of w are non-negative, so the largest sums come near 15 K amax."""
+    key = (M, N, K)
+    if key not in _F32_CACHE:
+        if len(_F32_CACHE) >= 2:
+            _F32_CACHE.pop(next(iter(_F32_CACHE)))
+        rng = _rng(31, M, N, K)
+        amax = f32_amax(K)
+        a, w = _ints(rng, (M, K), -amax, amax), _ints(rng, (N, K), -F32_WMAX, F32_WMAX)
+        a[0::16] = float(amax)
+        w[0::8] = w[0::8].abs()
+        w[1::8] = w[1::8].abs()
+        _F32_CACHE[key] = {"a": a, "w": w, "amax": amax, "bias": _ints(rng, (N,), -F32_EPI_MAX, F32_EPI_MAX),
+                           "resid": _ints(rng, (M, N), -F32_EPI_MAX, F32_EPI_MAX), "periodic": _ints(rng, (M + 3, N), -F32_EPI_MAX, F32_EPI_MAX),
+                           "ref": a.double() @ w.double().t()}
+    return _F32_CACHE[key]
+
+
+def f32_act_shift(K):
+    """s with the pre-activation's standard deviation sqrt(4 K / 9) 2^-s nearest 1.5 (a, w uniform on {-1, 0, 1}): four standard deviations
+    are the [-6, 6] in which erf, tanh and exp do all their work."""
+    return max(0, round(math.log2(math.sqrt(4.0 * K / 9.0) / 1.5)))
+
+
+def gemm_f32_act(M, N, K):
+    """a in {-1, 0, 1}, w in {-1, 0, 1} * 2^-s, bias in multiples of 1/8 in [-2, 2]: x = a w^T + bias (fp64 here) is exact in fp32 in any
+    order.  resid [M, N] and periodic [7, N] are integers in [-8, 8], added after the activation."""
+    rng = _rng(32, M, N, K)
+    s = f32_act_shift(K)
+    a, w = _ints(rng, (M, K), -1, 1), _ints(rng, (N, K), -1, 1) * 2.0 ** -s
+    bias = _ints(rng, (N,), -16, 16) / 8.0
+    return {"a": a, "w": w, "bias": bias, "s": s, "x": a.double() @ w.double().t() + bias.double(),
+            "resid": _ints(rng, (M, N), -F32_EPI_MAX, F32_EPI_MAX), "periodic": _ints(rng, (7, N), -F32_EPI_MAX, F32_EPI_MAX)}
+
+
+def f32_act(x, act):
+    """The epilogue's activation formula (csrc/joint.hip epilogue_apply4) in the precision of x: 1 gelu (erf), 2 tanh, 3 quick-gelu."""
+    if act == 1:
+        return 0.5 * x * (1.0 + torch.erf(x * 0.70710678118654752440))
+    if act == 2:
+        return torch.tanh(x)
+    if act == 3:
+        return x * (1.0 / (1.0 + torch.exp(-1.702 * x)))
+    return x
+
+
+def overlap_view(M, lda, K):
+    """(buf, offset, gathered): a flat NaN-filled fp32 buffer whose floats offset .. offset + (M - 1) lda + K - 1 are integers in
+    [-f32_amax(K), f32_amax(K)] — the overlapping view A[m, k] = buf[offset + m lda + k] (lda < K: rows share floats) — with at least 4 K
+    NaN floats before and after it, and the [M, K] matrix the view means, gathered row by row.  offset % 4 == 0."""
+    rng = _rng(33, M, lda, K)
+    n = (M - 1) * lda + K
+    offset = 4 * K
+    buf = torch.full((offset + n + 4 * K,), float("nan"), dtype=torch.float32)
+    amax = f32_amax(K)
+    buf[offset:offset + n] = _ints(rng, (n,), -amax, amax)
+    gathered = torch.stack([buf[offset + m * lda: offset + m * lda + K] for m in range(M)])
+    return buf, offset, gathered
+
+
+# Shapes of tests/test_gpu_gemm_f32_exact.py, per kernel: (dispatch name, entry point, select_kernel, ring_mode, [(M, N, K), ...]).
+# tests/test_exact_inputs_host.py proves with hirest_gemm_f32_dispatch_name (cus = 256) that every shape reaches the kernel it is listed under.
+F32_PLAIN = [
+    ("tile64", "gemm", 1, 0, [(1, 4, 16), (63, 60, 48), (64, 64, 112), (65, 68, 128), (129, 132, 144), (66, 36, 240)]),
+    ("tile64", "gemm", 0, 0, [(60, 8196, 48)]),
+    ("tile64.split", "ws", 0, 0, [(257, 68, 1024), (300, 132, 1040), (321, 4, 1056)]),
+    ("ring<4>", "gemm", 0, 2, [(257, 68, 64), (300, 132, 96), (321, 4, 160)]),
+    ("skinny", "gemm", 0, 0, [(1, 4, 16), (31, 36, 48), (33, 28, 112), (256, 100, 176)]),
+    ("skinny", "gemm", 2, 0, [(15, 20, 128)]),
+    ("m16<1,1,8>", "gemm", 0, 0, [(1, 4, 32), (15, 20, 64), (16, 16, 1152)]),
+    ("m16<1,1,3>", "gemm", 0, 0, [(17, 2052, 96), (32, 2048, 416)]),
+    ("m16<1,2,6>", "gemm", 0, 0, [(16, 8196, 64), (9, 8200, 896)]),
+    ("m16<2,2,2>", "gemm", 0, 0, [(17, 8212, 384)]),
+    ("m16<2,1,6>", "gemm", 0, 0, [(33, 36, 32), (47, 52, 896), (256, 20, 64)]),
+    ("m16<1,1,4>", "gemm", 0, 0, [(33, 20, 2048), (130, 36, 2080)]),
+]
+# the row-group streaming kernel: (name, entry point, (M, N, K)).  The chooser takes mt = 1 for every narrow N (the first four shapes: one
+# row group with a ragged tile, 4, 11 and 21 row tiles); mt = 2 .. 5 need enough column tiles per stream, i.e. a wide N
+F32_ROWS = [("rows<mt=1>", "rows_colmax", (33, 4, 768)), ("rows<mt=1>", "rows_colmax", (49, 20, 768)), ("rows<mt=1>", "rows_colmax", (161, 132, 768)),
+            ("rows<mt=1>", "rows_colmax", (330, 36, 768)), ("rows<mt=2>", "gemm", (96, 8200, 768)), ("rows<mt=3>", "rows_colmax", (200, 2052, 768)),
+            ("rows<mt=4>", "rows_colmax", (300, 8196, 768)), ("rows<mt=5>", "rows_colmax", (390, 2052, 768))]
+F32_LAYOUT_SHAPE = (68, 132, 48)
+F32_LAYOUTS = [("tile64", 0, 0), ("tile64<ak>", 1, 0), ("tile64<wk>", 0, 1), ("tile64<ak,wk>", 1, 1)]
+# hirest_gemm_f32_ln: (name, (M, N, K), resid, ids)
+F32_M16LN = [("m16ln<1,1,2>", (1, 4, 256), False, False), ("m16ln<2,1,2>", (15, 36, 512), False, False), ("m16ln<3,1,2>", (16, 2052, 768), False, False),
+             ("m16ln<4,1,2>", (32, 20, 1024), False, False), ("m16ln<1,1,2>", (33, 36, 256), False, False), ("m16ln<3,1,2>", (256, 20, 768), True, False),
+             ("m16ln<3,1,2>", (25, 36, 768), False, True)]
+# the LM-head stream, N = 8196, K = 768: M = 1 and the upper edge of each of the nine instantiations
+F32_STREAM_NK = (8196, 768)
+F32_STREAM = [(1, "m16ln_stream<3,1,8,0>"), (2, "m16ln_stream<3,1,8,0>"), (5, "m16ln_stream<3,1,8,1>"), (7, "m16ln_stream<3,1,8,2>"),
+              (10, "m16ln_stream<3,1,8,3>"), (12, "m16ln_stream<3,1,8,4>"), (16, "m16ln_stream<3,1,8,5>"), (20, "m16ln_stream<3,2,4,3>"),
+              (26, "m16ln_stream<3,2,4,4>"), (32, "m16ln_stream<3,2,2,5>")]
+# the row-group kernel's LayerNorm form: (hirest_gemm_f32_rows_ln_mode, (M, N, K), name); mode 0 runs the chooser (mt 1 .. 3)
+F32_ROWS_LN = [(mode, s, "rows<mt=1,ln,mode=%d>" % mode) for mode in (1, 2) for s in ((33, 2052, 768), (49, 8196, 768), (257, 20, 768), (300, 36, 768))] + \
+              [(0, (33, 2052, 768), "rows<mt=1,ln,mode=0>"), (0, (49, 8196, 768), "rows<mt=1,ln,mode=0>"), (0, (257, 20, 768), "rows<mt=1,ln,mode=0>"),
+               (0, (300, 36, 768), "rows<mt=1,ln,mode=0>"), (0, (257, 2052, 768), "rows<mt=2,ln,mode=0>"), (0, (200, 8196, 768), "rows<mt=3,ln,mode=0>")]
+# overlapping A: (lda, K, M, entry point, select_kernel, ring_mode, name), N = F32_OVERLAP_N
+F32_OVERLAP_N = 36
+F32_OVERLAP = [(80, 240, 1, "gemm", 0, 0, "skinny"), (80, 240, 31, "gemm", 0, 0, "skinny"), (80, 240, 33, "gemm", 0, 0, "skinny"),
+               (80, 240, 66, "gemm", 1, 0, "tile64"), (80, 240, 257, "gemm", 0, 0, "tile64"),
+               (128, 384, 1, "gemm", 0, 0, "m16<1,1,8>"), (128, 384, 31, "gemm", 0, 0, "m16<1,1,8>"), (128, 384, 33, "gemm", 0, 0, "m16<2,1,6>"),
+               (128, 384, 66, "gemm", 0, 0, "m16<2,1,6>"), (128, 384, 257, "gemm", 0, 2, "ring<4>"),
+               (128, 192, 1, "gemm", 0, 0, "m16<1,1,8>"), (128, 192, 33, "gemm", 0, 0, "m16<2,1,6>"), (128, 192, 66, "gemm", 2, 0, "skinny"),
+               (128, 192, 257, "gemm", 1, 0, "tile64"), (128, 192, 257, "gemm", 0, 2, "ring<4>"),
+               (1024, 1536, 257, "ws", 0, 0, "tile64.split")]
+# activations 1, 2, 3: (name, entry point, select_kernel, (M, N, K))
+F32_ACT = [("tile64", "gemm", 1, (65, 68, 128)), ("tile64.split", "ws", 0, (257, 68, 1024)), ("m16<2,1,6>", "gemm", 0, (47, 52, 896)),
+           ("skinny", "gemm", 0, (33, 28, 112))]
+# every epilogue-operand combination: one shape per kernel family, with rows past a tile boundary (indices into F32_PLAIN's rows)
+F32_EPILOGUE = {"tile64": (129, 132, 144), "tile64.split": (300, 132, 1040), "ring<4>": (300, 132, 96), "skinny": (33, 28, 112),
+                "m16<2,1,6>": (47, 52, 896)}
+
+# Every instantiation the fp32 dispatch can reach, by the name hirest_gemm_f32_dispatch_name gives it.  (hirest_gemm_f32_layouts with a
+# workspace also runs its three k-major instantiations in the split form: the same instantiations plus gemm_f32_quarters_kernel, both
+# listed here.  rows<mt=1,ln,mode=1> and mode=2 are one instantiation under two launch geometries.)
+F32_ALL_NAMES = sorted(
+    ["tile64", "tile64.split", "tile64<ak>", "tile64<wk>", "tile64<ak,wk>", "ring<4>", "skinny"] +
+    ["m16<1,1,8>", "m16<1,1,3>", "m16<1,2,6>", "m16<2,2,2>", "m16<2,1,6>", "m16<1,1,4>"] +
+    ["m16ln<%d,1,2>" % nv for nv in (1, 2, 3, 4)] +
+    ["m16ln_stream<3,1,8,%d>" % d1 for d1 in range(6)] + ["m16ln_stream<3,2,4,3>", "m16ln_stream<3,2,4,4>", "m16ln_stream<3,2,2,5>"] +
+    ["rows<mt=%d>" % mt for mt in (1, 2, 3, 4, 5)] + ["rows<mt=%d,ln,mode=0>" % mt for mt in (1, 2, 3)] +
+    ["rows<mt=1,ln,mode=1>", "rows<mt=1,ln,mode=2>"])
+
+
+def f32_dispatch_cases():
+    """Every call tests/test_gpu_gemm_f32_exact.py makes, as (expected name, entry point, M, N, K, query fields)."""
+    out = []
+    for name, entry, sel, ring, shapes in F32_PLAIN:
+        out += [(name, entry, M, N, K, dict(select_kernel=sel, ring_mode=ring, has_workspace=entry == "ws")) for M, N, K in shapes]
+    out += [(name, entry, M, N, K, {}) for name, entry, (M, N, K) in F32_ROWS]
+    out += [(name, "layouts", *F32_LAYOUT_SHAPE, dict(a_kmajor=ak, w_kmajor=wk)) for name, ak, wk in F32_LAYOUTS]
+    out += [(name, "ln", M, N, K, dict(has_resid=resid, has_ids=ids, has_ln_out=True)) for name, (M, N, K), resid, ids in F32_M16LN]
+    for M, name in F32_STREAM:
+        out += [(name, "ln", M, *F32_STREAM_NK, {}), (name, "ln_colmax", M, *F32_STREAM_NK, {})]
+    out += [(name, "ln", M, N, K, dict(rows_ln_mode=mode, has_ln_out=True)) for mode, (M, N, K), name in F32_ROWS_LN]
+    out += [(name, entry, M, F32_OVERLAP_N, K, dict(select_kernel=sel, ring_mode=ring, has_workspace=entry == "ws"))
+            for _, K, M, entry, sel, ring, name in F32_OVERLAP]
+    for name, entry, sel, (M, N, K) in F32_ACT:
+        out.append((name, entry, M, N, K, dict(select_kernel=sel, has_workspace=entry == "ws", has_resid=True, has_periodic=True)))
     return out

@@ -1,5 +1,5 @@
 """The preconditions of tests/_exact_inputs.py, checked on the CPU: the GPU tests that use these generators (test_gpu_gemm_exact.py,
-test_gpu_attention_edges.py) assert bit equality or derived bounds that only mean something while these hold."""
+test_gpu_attention_edges.py, test_gpu_gemm_f32_exact.py) assert bit equality or derived bounds that only mean something while these hold."""
 import ctypes
 
 import pytest
@@ -234,3 +234,127 @@ def test_gemm_rejects_output_strides_the_epilogues_cannot_store_to(lib):
     for epi in (_lib.EPI_BIAS_F32, _lib.EPI_BIAS_RESID_F32):             # the split-operand kernels share the fp32 epilogue
         a = _lib.GemmArgs.make(X_PTR, 64, X_PTR, 64, None, X_PTR, 134, 129, 132, 64, epi, None, 0, None, None, _lib.GEMM_X3)
         assert lib.hirest_gemm_bf16(ctypes.byref(a), None) == -2
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# fp32 GEMM family: tests/test_gpu_gemm_f32_exact.py
+# ------------------------------------------------------------------------------------------------------------------------------
+F32_SHAPES = sorted({s for _, _, _, _, shapes in X.F32_PLAIN for s in shapes} | {s for _, _, s in X.F32_ROWS})
+
+
+@pytest.mark.parametrize("M,N,K", [s for s in F32_SHAPES if s[0] * s[1] * s[2] <= 1 << 26])
+def test_f32_integer_inputs_are_exact_in_any_order(M, N, K):
+    d = X.gemm_f32_exact(M, N, K)
+    a, w, amax = d["a"], d["w"], d["amax"]
+    assert amax == min(4095, (2 ** 24 - 1 - 24) // (15 * K)) and a.abs().max() == amax and w.abs().max() <= 15
+    assert torch.equal(a, a.round()) and torch.equal(w, w.round())
+    for t in (d["bias"], d["resid"], d["periodic"]):
+        assert t.abs().max() <= 8 and torch.equal(t, t.round())
+    assert d["periodic"].shape == (M + 3, N)
+    # for every (m, n): sum_k |a| |w| + 24 < 2^24 — every partial sum of every summation order, and the epilogue's three addends on top
+    worst = (a.abs().double() @ w.abs().double().t()).max().item()
+    assert worst + 24 < X.F32_EXACT
+    assert (a[0::16] == amax).all() and (w[0::8] >= 0).all() and (w[1::8] >= 0).all()
+    if K >= 64:
+        assert d["ref"].abs().max().item() > 0.25 * 15 * K * amax                      # the largest sums come near the bound
+    assert torch.equal(d["ref"], d["ref"].float().double())
+    if K <= 256:
+        # 12 significant bits: an odd integer of magnitude >= 2048 changes when it is cut to an 11-bit significand
+        v = a.abs().long()
+        assert ((v >= 2048) & (v % 2 == 1)).any()
+
+
+def test_f32_exact_bound_holds_for_the_shapes_too_large_to_multiply_here():
+    """amax * 15 * K + 24 < 2^24 for every K in use: the precondition above without forming |a| |w|^T."""
+    for _, _, K in F32_SHAPES + [(0, 0, k) for _, k, *_ in X.F32_OVERLAP]:
+        assert X.f32_amax(K) >= 1 and X.f32_amax(K) * 15 * K + 24 < X.F32_EXACT
+
+
+@pytest.mark.parametrize("M,N,K", [s for _, _, _, s in X.F32_ACT])
+def test_f32_act_pre_activation_is_exact_and_in_range(M, N, K):
+    d = X.gemm_f32_act(M, N, K)
+    a, w, s = d["a"], d["w"], d["s"]
+    assert set(a.unique().tolist()) <= {-1.0, 0.0, 1.0} and set((w * 2.0 ** s).unique().tolist()) <= {-1.0, 0.0, 1.0}
+    assert torch.equal(d["bias"] * 8, (d["bias"] * 8).round()) and d["bias"].abs().max() <= 2
+    # 8 * 2^s * x is an integer below 8 (K + 2 * 2^s) < 2^24: exact in fp32 in any order
+    scaled = d["x"] * 8 * 2.0 ** s
+    assert torch.equal(scaled, scaled.round()) and 8 * (K + 2 * 2 ** s) < X.F32_EXACT
+    assert torch.equal(d["x"], d["x"].float().double())
+    assert torch.equal((a @ w.t() + d["bias"]).double(), d["x"])
+    x = d["x"]
+    assert 1.0 < x.std().item() < 2.5 and (x.abs() <= 6).double().mean().item() > 0.99 and x.abs().max().item() < 12
+    assert (x < -3).any() and (x > 3).any()
+    for t in (d["resid"], d["periodic"]):
+        assert t.abs().max() <= 8 and torch.equal(t, t.round())
+
+
+@pytest.mark.parametrize("lda,K,M", sorted({(lda, K, M) for lda, K, M, *_ in X.F32_OVERLAP}))
+def test_overlap_view_is_the_row_by_row_gather(lda, K, M):
+    buf, off, g = X.overlap_view(M, lda, K)
+    n = (M - 1) * lda + K
+    assert off % 4 == 0 and lda % 4 == 0 and lda < K and off >= 4 * K and buf.numel() - off - n >= 4 * K
+    assert torch.isnan(buf[:off]).all() and torch.isnan(buf[off + n:]).all()
+    inner = buf[off:off + n]
+    assert torch.equal(inner, inner.round()) and inner.abs().max() <= X.f32_amax(K)
+    assert g.shape == (M, K) and torch.equal(torch.as_strided(buf, (M, K), (lda, 1), off), g)
+    for m in (0, M // 2, M - 1):
+        for k in (0, K - 1):
+            assert g[m, k] == buf[off + m * lda + k]
+
+
+def _f32_name(lib, entry, M, N, K, **fields):
+    from hirest_amd import _lib
+    fields = dict(dict(select_kernel=0, ring_mode=0, rows_ln_mode=2, cus=256), **fields)
+    buf = ctypes.create_string_buffer(64)
+    status = lib.hirest_gemm_f32_dispatch_name(ctypes.byref(_lib.GemmF32Query.make(entry, M, N, K, **fields)), buf, 64)
+    return status, buf.value.decode()
+
+
+def test_f32_shape_lists_reach_every_instantiation(lib):
+    """With 256 CUs and the switch values the GPU test sets, every listed call takes the kernel it is listed under, and together the calls
+    take every instantiation the fp32 dispatch can reach: when a threshold moves, a kernel cannot lose its test shapes unnoticed."""
+    reached = set()
+    for name, entry, M, N, K, fields in X.f32_dispatch_cases():
+        assert _f32_name(lib, entry, M, N, K, **fields) == (0, name), (entry, M, N, K, fields)
+        reached.add(name)
+    assert sorted(reached) == X.F32_ALL_NAMES
+
+
+def test_f32_dispatch_name_arguments(lib):
+    from hirest_amd import _lib
+    buf = ctypes.create_string_buffer(64)
+    q = _lib.GemmF32Query.make("gemm", 64, 64, 64, cus=256)
+    assert lib.hirest_gemm_f32_dispatch_name(ctypes.byref(q), buf, 64) == 0 and buf.value == b"m16<2,1,6>"   # -1 switches: the defaults
+    assert lib.hirest_gemm_f32_dispatch_name(None, buf, 64) == -1 and lib.hirest_gemm_f32_dispatch_name(ctypes.byref(q), None, 64) == -1
+    assert lib.hirest_gemm_f32_dispatch_name(ctypes.byref(q), buf, 47) == -1
+    q.struct_size -= 4
+    assert lib.hirest_gemm_f32_dispatch_name(ctypes.byref(q), buf, 64) == -1
+    assert _f32_name(lib, "gemm", 64, 64, 0)[0] == -1 and _f32_name(lib, "gemm", 64, 64, 64, select_kernel=3)[0] == -1
+    # shapes no kernel takes: the entry point's own status
+    assert _f32_name(lib, "gemm", 64, 62, 64)[0] == -2 and _f32_name(lib, "gemm", 64, 64, 72)[0] == -2
+    assert _f32_name(lib, "ln", 33, 8196, 512)[0] == -2 and _f32_name(lib, "ln", 16, 64, 1280)[0] == -2
+    assert _f32_name(lib, "ln_colmax", 16, 4096, 768)[0] == -2 and _f32_name(lib, "rows_colmax", 64, 64, 512)[0] == -2
+    assert _f32_name(lib, "layouts", 66, 64, 64, a_kmajor=1)[0] == -2
+    # the ring threshold is the one decision of hirest_gemm_f32 itself that reads the CU count: 64 tiles per CU
+    assert _f32_name(lib, "gemm", 64 * 128, 64 * 128, 64, cus=256) == (0, "ring<4>")
+    assert _f32_name(lib, "gemm", 64 * 128, 64 * 127, 64, cus=256) == (0, "tile64")
+    assert _f32_name(lib, "gemm", 64 * 128, 64 * 127, 64, cus=128) == (0, "ring<4>")
+    assert _f32_name(lib, "gemm", 64 * 128, 64 * 128, 64, ring_mode=1) == (0, "tile64")
+    # hirest_gemm_f32_ws without a usable workspace is hirest_gemm_f32
+    assert _f32_name(lib, "ws", 300, 132, 1040, has_workspace=0) == (0, "tile64") and _f32_name(lib, "ws", 300, 132, 1040, has_workspace=1) == (0, "tile64.split")
+
+
+def test_f32_gemm_rejects_strides_its_epilogue_cannot_use(lib):
+    """out and resid are moved as 16-byte vectors at base + m * ld + n: ldo, ldr must be multiples of 4 and at least N; ln_out rows hold K
+    floats.  HIREST_E_SHAPE before any launch: the placeholder pointers are never dereferenced."""
+    P, SHAPE = 1 << 20, -2
+    M, N, K = 64, 132, 256
+    for ldo, ldr, resid in ((133, 132, None), (134, 132, None), (128, 132, None), (132, 133, P), (132, 134, P), (132, 128, P), (130, 132, P)):
+        assert lib.hirest_gemm_f32(P, K, P, K, None, resid, ldr, None, 0, P, ldo, M, N, K, 0, None) == SHAPE, (ldo, ldr)
+        assert lib.hirest_gemm_f32_ws(P, K, P, K, None, resid, ldr, None, 0, P, ldo, M, N, K, 0, None, 0, None) == SHAPE, (ldo, ldr)
+        assert lib.hirest_gemm_f32_layouts(P, K, 0, P, K, 0, None, resid, ldr, P, ldo, M, N, K, 0, None, 0, None) == SHAPE, (ldo, ldr)
+        assert lib.hirest_gemm_f32_ln(P, K, None, None, None, P, P, 1e-5, None, 0, P, K, None, resid, ldr, P, ldo, 16, N, K, 0, None) == SHAPE, (ldo, ldr)
+    for ldl in (252, 255, 128):
+        assert lib.hirest_gemm_f32_ln(P, K, None, None, None, P, P, 1e-5, P, ldl, P, K, None, None, 0, P, N, 16, N, K, 0, None) == SHAPE, ldl
+    for ldo in (8197, 8198, 8192):
+        assert lib.hirest_gemm_f32_ln_colmax(P, 768, P, P, 1e-5, P, 768, None, P, ldo, P, 16, 8196, 768, None) == SHAPE, ldo
