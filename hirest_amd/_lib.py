@@ -136,6 +136,7 @@ class WhisperTailParams(C.Structure):
 
 
 WHISPER_ROW_STATE_WORDS = 8      # hirest_whisper_row_state: n_sampled, last, penult, last_timestamp, completed | sum_logprobs, no_speech_prob, last_logprob
+WHISPER_ROW_CTL_WORDS = 8        # hirest_whisper_row_ctl: position, step, max_steps, draw_row, seed (uint32) | temperature (float) | 2 reserved
 
 
 class JointLayerX3(C.Structure):
@@ -460,6 +461,15 @@ _SIGNATURES = {
     "hirest_whisper_decode_step": (C.c_int, [C.POINTER(WhisperDecoder), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p),
                                              C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hirest_attention_f32_decode_inplace_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                                           C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "hirest_whisper_step_tail_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(WhisperTailParams),
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hirest_whisper_step_rows_workspace_bytes": (C.c_size_t, [C.POINTER(WhisperDecoder), C.c_int32, C.c_int32]),
+    "hirest_whisper_decode_step_rows": (C.c_int, [C.POINTER(WhisperDecoder), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hirest_vision_workspace_bytes": (C.c_size_t, [C.POINTER(VisionTower), C.c_int32]),
     "hirest_vision_forward": (C.c_int, [C.POINTER(VisionTower), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),

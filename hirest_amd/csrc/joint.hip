@@ -1369,19 +1369,30 @@ struct AttnDec {
     float* out;
     int H; float scale, add_const, causal_penalty;
     int64_t hist_row;          // floats between two rows' histories: t_hist * ld_hist when packed, T_max * ld_hist for a preallocated cache
+    const int32_t* t_rows;     // ROWS: row r's own t_hist (device, [R]), bounded by t_max
+    int t_max;
 };
 
 // INPLACE: the history is a preallocated [R, T_max, ld_hist] cache (parent unused, k_out / v_out = the cache itself): the newest key /
 // value is appended at position t_hist instead of the whole history being written out again.  Position t_hist is read from k_new /
 // v_new only, never from the cache, and a block writes its own (row, head) slice: no ordering between the append and any read.
-template <bool INPLACE>
+// ROWS (with INPLACE): every row has its own t_hist, p.t_rows[r] — rows of different windows sit at different positions.  A row whose
+// position is outside [0, t_max) is inactive: its blocks leave before any load, and neither its cache nor its out row is written.
+// For every other row the body below is the scalar form's at t_hist = t_rows[r], operation for operation.
+template <bool INPLACE, bool ROWS = false>
 __global__ __launch_bounds__(64) void attention_f32_decode_kernel(AttnDec p) {
+    static_assert(INPLACE || !ROWS, "per-row positions exist for the in-place cache only");
     constexpr int KLD = 68;
     __shared__ __attribute__((aligned(16))) float Ks[64 * KLD];
     __shared__ __attribute__((aligned(16))) float Qs[64];
     const int lane = threadIdx.x;
     const int r = blockIdx.x / p.H, h = blockIdx.x - r * p.H;
-    const int D = p.H * 64, T = p.t_hist + (p.k_new ? 1 : 0);
+    int t_hist = p.t_hist;
+    if (ROWS) {
+        t_hist = __builtin_amdgcn_readfirstlane(p.t_rows[r]);     // (block-uniform)
+        if (t_hist < 0 || t_hist >= p.t_max) return;
+    }
+    const int D = p.H * 64, T = t_hist + (p.k_new ? 1 : 0);
     const int64_t src = !INPLACE && p.parent ? p.parent[r] : r;
     Qs[lane] = p.q[(int64_t)r * p.ldq + h * 64 + lane];
     float mrun = -3.0e38f, lrun = 0.f, o = 0.f;
@@ -1395,26 +1406,26 @@ __global__ __launch_bounds__(64) void attention_f32_decode_kernel(AttnDec p) {
 #pragma unroll
         for (int ps = 0; ps < 16; ++ps) {
             const int key = k0 + ps * 4 + (lane >> 4), kk = key < T ? key : T - 1;
-            const float* kp = kk < p.t_hist ? p.k_hist + src * p.hist_row + kk * p.ld_hist : p.k_new + (int64_t)r * p.ld_new;
+            const float* kp = kk < t_hist ? p.k_hist + src * p.hist_row + kk * p.ld_hist : p.k_new + (int64_t)r * p.ld_new;
             kreg[ps] = *reinterpret_cast<const f32x4*>(kp + h * 64 + 4 * (lane & 15));
         }
 #pragma unroll
         for (int j = 0; j < 64; ++j) {
             const int key = k0 + j, kk = key < T ? key : T - 1;
-            const float* vp = kk < p.t_hist ? p.v_hist + src * p.hist_row + kk * p.ld_hist : p.v_new + (int64_t)r * p.ld_new;
+            const float* vp = kk < t_hist ? p.v_hist + src * p.hist_row + kk * p.ld_hist : p.v_new + (int64_t)r * p.ld_new;
             vv[j] = vp[h * 64 + lane];
         }
 #pragma unroll
         for (int ps = 0; ps < 16; ++ps) *reinterpret_cast<f32x4*>(Ks + (ps * 4 + (lane >> 4)) * KLD + 4 * (lane & 15)) = kreg[ps];
         if (INPLACE) {
-            if (p.t_hist >= k0 && p.t_hist < k0 + 64) {       // (uniform) the chunk that holds the newest position
+            if (t_hist >= k0 && t_hist < k0 + 64) {           // (uniform) the chunk that holds the newest position
 #pragma unroll
                 for (int ps = 0; ps < 16; ++ps)
-                    if (k0 + ps * 4 + (lane >> 4) == p.t_hist)
-                        *reinterpret_cast<f32x4*>(p.k_out + (int64_t)r * p.hist_row + (int64_t)p.t_hist * p.ld_hist + h * 64 + 4 * (lane & 15)) = kreg[ps];
+                    if (k0 + ps * 4 + (lane >> 4) == t_hist)
+                        *reinterpret_cast<f32x4*>(p.k_out + (int64_t)r * p.hist_row + (int64_t)t_hist * p.ld_hist + h * 64 + 4 * (lane & 15)) = kreg[ps];
 #pragma unroll
                 for (int j = 0; j < 64; ++j)
-                    if (k0 + j == p.t_hist) p.v_out[(int64_t)r * p.hist_row + (int64_t)p.t_hist * p.ld_hist + h * 64 + lane] = vv[j];
+                    if (k0 + j == t_hist) p.v_out[(int64_t)r * p.hist_row + (int64_t)t_hist * p.ld_hist + h * 64 + lane] = vv[j];
             }
         } else if (p.k_out) {
 #pragma unroll
@@ -2188,6 +2199,20 @@ extern "C" int hirest_attention_f32_decode_inplace(const float* q, int64_t ldq, 
     AttnDec p{q, ldq, k_cache, v_cache, ld_cache, nullptr, t, k_new, v_new, ld_new, k_cache, v_cache, out, H, scale, add_const, causal_penalty,
               row_stride};
     hipLaunchKernelGGL(attention_f32_decode_kernel<true>, dim3(R * H), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), p);
+    return hirest_launch_status();
+}
+
+extern "C" int hirest_attention_f32_decode_inplace_rows(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ld_cache,
+                                                        int64_t row_stride, const int32_t* t, int32_t T_max, const float* k_new, const float* v_new,
+                                                        int64_t ld_new, float* out, int32_t R, int32_t H, float scale, float add_const,
+                                                        float causal_penalty, void* stream) {
+    if (!q || !out || !k_cache || !v_cache || !k_new || !v_new || !t || R <= 0 || H <= 0 || T_max <= 0) return HIREST_E_BADARG;
+    if (ld_cache < (int64_t)H * 64 || row_stride < (int64_t)T_max * ld_cache) return HIREST_E_SHAPE;
+    if (ldq % 4 != 0 || ld_cache % 4 != 0 || ld_new % 4 != 0 || row_stride % 4 != 0) return HIREST_E_SHAPE;
+    if ((int64_t)R * H > 0x7fffffffll) return HIREST_E_SHAPE;
+    AttnDec p{q, ldq, k_cache, v_cache, ld_cache, nullptr, 0, k_new, v_new, ld_new, k_cache, v_cache, out, H, scale, add_const, causal_penalty,
+              row_stride, t, T_max};
+    hipLaunchKernelGGL((attention_f32_decode_kernel<true, true>), dim3(R * H), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), p);
     return hirest_launch_status();
 }
 

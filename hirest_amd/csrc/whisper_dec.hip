@@ -1,7 +1,9 @@
 // Whisper's text decoder on gfx950: the two kernels a decoded token needs that the tree did not have — one-query
 // cross-attention over a long, shared key set, split over keys, and the whole tail of a sampling step (logit filters, log_softmax, the
 // pick, the row's bookkeeping) with its state on the device — and the C-side step that strings them together with the exact-fp32
-// GEMMs.  The in-place self-attention form lives beside the kernel it shares its body with (joint.hip).
+// GEMMs.  The in-place self-attention form lives beside the kernel it shares its body with (joint.hip).  The `_rows` entry points
+//  are the same step and tail for rows of several windows, each with its own position, step, temperature and seed in a
+// device record (hirest_whisper_row_ctl).
 #include "common.h"
 #include <math.h>
 
@@ -156,21 +158,18 @@ __device__ __forceinline__ float block_sum(float v, float* sh, int tid) {
     return s;
 }
 
-__global__ __launch_bounds__(1024) void whisper_tail_kernel(const float* __restrict__ logits, int64_t ldx, int V, int step, int T_max,
-                                                           hirest_whisper_tail_params c, hirest_whisper_row_state* __restrict__ state,
-                                                           int32_t* __restrict__ next_ids, int32_t* __restrict__ tokens,
-                                                           float* __restrict__ logprobs) {
+// One row that is not completed, by its block: x the row's V logits, st its state on entry (block-uniform), lp_row where its
+// log-probabilities go (or null).  The draw is keyed by (seed, serial, draw_row): in a call of one window these are the call's own
+// and the row's index, in a call of rows from several windows the row's record supplies them.  Thread 0 stores the new state, the
+// pick and the token slot and gets the pick back; every other thread gets -1.
+__device__ __forceinline__ int tail_row(const float* __restrict__ x, int V, const hirest_whisper_tail_params& c, float temperature, uint32_t seed,
+                                        uint32_t serial, uint32_t draw_row, const hirest_whisper_row_state& st,
+                                        hirest_whisper_row_state* __restrict__ state_out, int32_t* __restrict__ next_id,
+                                        int32_t* __restrict__ slot, float* __restrict__ lp_row) {
     __shared__ float sh[16];
     __shared__ float best_v[16];
     __shared__ int best_i[16];
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const hirest_whisper_row_state st = state[r];                 // (block-uniform: written only by this block, in an earlier launch)
-    int32_t* slot = tokens ? tokens + (int64_t)r * T_max + c.sample_begin + step : nullptr;
-    if (st.completed) {
-        if (tid == 0) { next_ids[r] = c.eot; if (slot) *slot = c.eot; }
-        return;
-    }
-    const float* x = logits + (int64_t)r * ldx;
+    const int tid = threadIdx.x;
     const uint32_t* mask = c.suppress_mask;
     const int tb = c.timestamp_begin;
     Rule k;
@@ -219,19 +218,19 @@ __global__ __launch_bounds__(1024) void whisper_tail_kernel(const float* __restr
     if (text_in && has_ts) { M = fmaxf(m_text, m_ts); S = s_text * expf(m_text - M) + s_ts * expf(m_ts - M); }
     else if (text_in) { M = m_text; S = s_text; }
     else { M = m_ts; S = s_ts; }
-    if (logprobs) {                                               // log_softmax of the filtered row, -inf where suppressed
+    if (lp_row) {                                                 // log_softmax of the filtered row, -inf where suppressed
         const float logS = logf(S);
         for (int i = tid; i < V4; i += 1024) {
             const f32x4 v4 = *reinterpret_cast<const f32x4*>(x + 4 * i);
             f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = allowed(k, mask, 4 * i + e) ? (v4[e] - M) - logS : -INFINITY;
-            *reinterpret_cast<f32x4*>(logprobs + (int64_t)r * V + 4 * i) = o;
+            *reinterpret_cast<f32x4*>(lp_row + 4 * i) = o;
         }
     }
     // pass 3: the pick — the largest logit (T = 0) or the largest logit / T + Gumbel noise (a categorical draw); the lower index on ties
-    const bool sample = c.temperature > 0.f;
-    const uint64_t key = draw_key(c.seed, c.serial);
+    const bool sample = temperature > 0.f;
+    const uint64_t key = draw_key(seed, serial);
     float bv = NEG; int bi = 0x7fffffff;
     for (int i = tid; i < V4; i += 1024) {
         const f32x4 v4 = *reinterpret_cast<const f32x4*>(x + 4 * i);
@@ -239,7 +238,7 @@ __global__ __launch_bounds__(1024) void whisper_tail_kernel(const float* __restr
         for (int e = 0; e < 4; ++e) {
             const int v = 4 * i + e;
             if (!allowed(k, mask, v)) continue;
-            const float s = sample ? v4[e] / c.temperature + gumbel(draw_bits(key, (uint32_t)r, (uint32_t)v)) : v4[e];
+            const float s = sample ? v4[e] / temperature + gumbel(draw_bits(key, draw_row, (uint32_t)v)) : v4[e];
             if (s > bv) { bv = s; bi = v; }                       // (ascending v: the first of equals stays)
         }
     }
@@ -250,11 +249,12 @@ __global__ __launch_bounds__(1024) void whisper_tail_kernel(const float* __restr
     }
     if ((tid & 63) == 0) { best_v[tid >> 6] = bv; best_i[tid >> 6] = bi; }
     __syncthreads();
+    int pick = -1;
     if (tid == 0) {
         for (int i = 1; i < 16; ++i)
             if (best_v[i] > bv || (best_v[i] == bv && best_i[i] < bi)) { bv = best_v[i]; bi = best_i[i]; }
         hirest_whisper_row_state ns = st;
-        int pick = bi;
+        pick = bi;
         float lp = 0.f;
         if (pick >= V || !(text_in || has_ts)) pick = c.eot;       // nothing was allowed: end the row (no log-probability to add)
         else lp = (x[pick] - M) - logf(S);
@@ -266,9 +266,50 @@ __global__ __launch_bounds__(1024) void whisper_tail_kernel(const float* __restr
             ns.n_sampled = st.n_sampled + 1; ns.penult = st.last; ns.last = pick;
             if (pick >= tb) ns.last_timestamp = pick;
         }
-        state[r] = ns;
-        next_ids[r] = pick;
+        *state_out = ns;
+        *next_id = pick;
         if (slot) *slot = pick;
+    }
+    return pick;
+}
+
+__global__ __launch_bounds__(1024) void whisper_tail_kernel(const float* __restrict__ logits, int64_t ldx, int V, int step, int T_max,
+                                                           hirest_whisper_tail_params c, hirest_whisper_row_state* __restrict__ state,
+                                                           int32_t* __restrict__ next_ids, int32_t* __restrict__ tokens,
+                                                           float* __restrict__ logprobs) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const hirest_whisper_row_state st = state[r];                 // (block-uniform: written only by this block, in an earlier launch)
+    int32_t* slot = tokens ? tokens + (int64_t)r * T_max + c.sample_begin + step : nullptr;
+    if (st.completed) {
+        if (tid == 0) { next_ids[r] = c.eot; if (slot) *slot = c.eot; }
+        return;
+    }
+    tail_row(logits + (int64_t)r * ldx, V, c, c.temperature, c.seed, c.serial, (uint32_t)r, st, state + r, next_ids + r, slot,
+             logprobs ? logprobs + (int64_t)r * V : nullptr);
+}
+
+// Rows of several windows in one call: step, temperature, seed and the generator's row come from the row's record, and the block
+// advances the record after its pick.  A row leaves the loop (position = -1) on eot or when it has made max_steps picks; the latter
+// neither completes it nor writes an eot, as a call per window that stops at its last step does not.  An inactive row's block
+// returns at once: nothing of the row changes.
+__global__ __launch_bounds__(1024) void whisper_tail_rows_kernel(const float* __restrict__ logits, int64_t ldx, int V, int64_t ld_tokens,
+                                                                hirest_whisper_tail_params c, hirest_whisper_row_ctl* __restrict__ ctl,
+                                                                hirest_whisper_row_state* __restrict__ state, int32_t* __restrict__ next_ids,
+                                                                int32_t* __restrict__ tokens, float* __restrict__ logprobs) {
+    const int r = blockIdx.x;
+    const hirest_whisper_row_ctl rc = ctl[r];                     // (block-uniform, as the state)
+    if (rc.position < 0) return;
+    const hirest_whisper_row_state st = state[r];
+    if (st.completed || rc.step < 0 || rc.step >= rc.max_steps || rc.step >= ld_tokens) {     // no pick to make: the row leaves the loop
+        if (threadIdx.x == 0) ctl[r].position = -1;
+        return;
+    }
+    const int pick = tail_row(logits + (int64_t)r * ldx, V, c, rc.temperature, rc.seed, (uint32_t)rc.step, (uint32_t)rc.draw_row, st, state + r,
+                              next_ids + r, tokens + (int64_t)r * ld_tokens + rc.step, logprobs ? logprobs + (int64_t)r * V : nullptr);
+    if (threadIdx.x == 0) {
+        const int step = rc.step + 1;
+        ctl[r].step = step;
+        ctl[r].position = pick == c.eot || step >= rc.max_steps ? -1 : rc.position + 1;
     }
 }
 
@@ -279,6 +320,15 @@ __global__ __launch_bounds__(64) void whisper_stamp_kernel(const hirest_whisper_
     for (int r = threadIdx.x; r < R; r += 64) all &= state[r].completed != 0;
     all = __all(all);
     if (threadIdx.x == 0) *done_host = ((step + 1) << 1) | (all ? 1 : 0);
+}
+
+// the same word for a call of rows: ((call + 1) << 1) | no row is active any more
+__global__ __launch_bounds__(64) void whisper_stamp_rows_kernel(const hirest_whisper_row_ctl* __restrict__ ctl, int R, int call,
+                                                               int32_t* __restrict__ done_host) {
+    int none = 1;
+    for (int r = threadIdx.x; r < R; r += 64) none &= ctl[r].position < 0;
+    none = __all(none);
+    if (threadIdx.x == 0) *done_host = ((call + 1) << 1) | (none ? 1 : 0);
 }
 
 __global__ __launch_bounds__(256) void gumbel_bits_kernel(uint32_t seed, uint32_t serial, int R, int V, uint32_t* __restrict__ out) {
@@ -299,11 +349,31 @@ __global__ __launch_bounds__(256) void embed_kernel(const int32_t* __restrict__ 
     reinterpret_cast<f32x4*>(x)[i] = a + b;
 }
 
+// x[r] = tok_emb[ids[r]] + pos_emb[ctl[r].position], and t[r] = that position for the self-attention.  A row whose position is
+// outside [0, limit) is inactive: t[r] = -1, and so that the GEMMs it still passes through read defined values it embeds its clamped
+// id at position 0 and its context row, which no attention block will write in the first layer, is zeroed.
+__global__ __launch_bounds__(256) void embed_rows_kernel(const int32_t* __restrict__ ids, const hirest_whisper_row_ctl* __restrict__ ctl,
+                                                        const float* __restrict__ tok, const float* __restrict__ pos, float* __restrict__ x,
+                                                        float* __restrict__ ctx, int32_t* __restrict__ t, int R, int D4, int vocab, int limit) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= R * D4) return;
+    const int r = i / D4, d = i - r * D4;
+    const int p = ctl[r].position;
+    const bool active = p >= 0 && p < limit;
+    int id = ids[r];
+    id = id < 0 ? 0 : id >= vocab ? vocab - 1 : id;
+    const f32x4 a = reinterpret_cast<const f32x4*>(tok)[(int64_t)id * D4 + d];
+    const f32x4 b = reinterpret_cast<const f32x4*>(pos)[(int64_t)(active ? p : 0) * D4 + d];
+    reinterpret_cast<f32x4*>(x)[i] = a + b;
+    if (!active) reinterpret_cast<f32x4*>(ctx)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (d == 0) t[r] = active ? p : -1;
+}
+
 inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int nchunks(int Tk) { return (Tk + XCH - 1) / XCH; }
 
-struct Ws { size_t x, a, b, ln, qkv, ctx, mid, part, total; };
-Ws plan(const hirest_whisper_decoder* d, int R, int Tk) {
+struct Ws { size_t x, a, b, ln, qkv, ctx, mid, part, t, total; };
+Ws plan(const hirest_whisper_decoder* d, int R, int Tk, bool rows = false) {
     Ws w; size_t off = 0;
     const size_t D = d->hidden;
     w.x = off; off += al((size_t)R * D * 4);
@@ -314,6 +384,7 @@ Ws plan(const hirest_whisper_decoder* d, int R, int Tk) {
     w.ctx = off; off += al((size_t)R * D * 4);
     w.mid = off; off += al((size_t)R * d->inter * 4);
     w.part = off; off += al((size_t)R * d->heads * nchunks(Tk) * XREC * 4);
+    w.t = off; if (rows) off += al((size_t)R * 4);                // the rows' positions, behind everything the one-position step lays out
     w.total = off;
     return w;
 }
@@ -374,6 +445,24 @@ extern "C" int hirest_whisper_step_tail(const float* logits, int64_t ldx, int32_
     return hirest_launch_status();
 }
 
+extern "C" int hirest_whisper_step_tail_rows(const float* logits, int64_t ldx, int32_t R, int32_t V, int32_t call, int64_t ld_tokens,
+                                             const hirest_whisper_tail_params* params, hirest_whisper_row_ctl* ctl,
+                                             hirest_whisper_row_state* state, int32_t* next_ids, int32_t* tokens, float* logprobs,
+                                             int32_t* done_host, void* stream) {
+    if (!logits || !params || !ctl || !state || !next_ids || !tokens || !params->suppress_mask || R <= 0 || V <= 0 || call < 0 || ld_tokens <= 0)
+        return HIREST_E_BADARG;
+    const hirest_whisper_tail_params& c = *params;                // temperature, seed, serial and sample_begin: the rows' records replace them
+    if (V % 4 != 0 || ldx % 4 != 0 || ldx < V || (reinterpret_cast<uintptr_t>(logits) & 15) != 0) return HIREST_E_SHAPE;
+    if (logprobs && (reinterpret_cast<uintptr_t>(logprobs) & 15) != 0) return HIREST_E_SHAPE;
+    if (c.n_vocab <= 0 || c.n_vocab > V || c.eot < 0 || c.eot >= c.n_vocab || c.no_speech >= c.n_vocab || c.blank >= c.n_vocab) return HIREST_E_BADARG;
+    if (c.timestamp_rules && (c.timestamp_begin <= c.eot || c.timestamp_begin > c.n_vocab || c.no_timestamps < 0 || c.no_timestamps >= c.n_vocab))
+        return HIREST_E_BADARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(whisper_tail_rows_kernel, dim3(R), dim3(1024), 0, s, logits, ldx, (int)V, ld_tokens, c, ctl, state, next_ids, tokens, logprobs);
+    if (done_host) hipLaunchKernelGGL(whisper_stamp_rows_kernel, dim3(1), dim3(64), 0, s, ctl, (int)R, (int)call, done_host);
+    return hirest_launch_status();
+}
+
 extern "C" int hirest_whisper_gumbel_bits(uint32_t seed, uint32_t serial, int32_t R, int32_t V, uint32_t* out, void* stream) {
     if (!out || R <= 0 || V <= 0) return HIREST_E_BADARG;
     const int64_t n = (int64_t)R * V;
@@ -387,16 +476,18 @@ extern "C" size_t hirest_whisper_step_workspace_bytes(const hirest_whisper_decod
     return plan(d, R, Tk).total;
 }
 
-extern "C" int hirest_whisper_decode_step(const hirest_whisper_decoder* d, int32_t R, int32_t position, const int32_t* ids,
-                                          float* const* self_k, float* const* self_v, int32_t T_max, const float* const* cross_kv,
-                                          int32_t n_windows, int32_t Tk, const int32_t* row_window, float* logits, void* workspace,
-                                          size_t workspace_bytes, void* stream) {
+// One position of R rows.  ctl == null: every row at `position`.  Otherwise row r at ctl[r].position (rows outside [0, min(max_pos,
+// T_max)) inactive): the embedding and the self-attention take the per-row form, every other call is the same one in the same order.
+static int decode_step(const hirest_whisper_decoder* d, int32_t R, int32_t position, const hirest_whisper_row_ctl* ctl, const int32_t* ids,
+                       float* const* self_k, float* const* self_v, int32_t T_max, const float* const* cross_kv, int32_t n_windows, int32_t Tk,
+                const int32_t* row_window, float* logits, void* workspace, size_t workspace_bytes, void* stream) {
     if (!d || !d->layer || !ids || !self_k || !self_v || !cross_kv || !row_window || !logits || !workspace || R <= 0 || Tk <= 0 || n_windows <= 0)
         return HIREST_E_BADARG;
-    if (position < 0 || position >= d->max_pos || position >= T_max) return HIREST_E_BADARG;
+    if (!ctl && (position < 0 || position >= d->max_pos || position >= T_max)) return HIREST_E_BADARG;
+    if (ctl && (T_max <= 0 || d->max_pos <= 0)) return HIREST_E_BADARG;
     const int D = d->hidden, H = d->heads, I = d->inter, Vp = d->vocab_padded;
     if (H <= 0 || D != H * 64 || D % 16 != 0 || I % 16 != 0 || Vp % 4 != 0) return HIREST_E_SHAPE;
-    const Ws w = plan(d, R, Tk);
+    const Ws w = plan(d, R, Tk, ctl != nullptr);
     if (workspace_bytes < w.total) return HIREST_E_WORKSPACE;
     char* base = static_cast<char*>(workspace);
     float* x = reinterpret_cast<float*>(base + w.x);
@@ -407,16 +498,25 @@ extern "C" int hirest_whisper_decode_step(const hirest_whisper_decoder* d, int32
     float* ctx = reinterpret_cast<float*>(base + w.ctx);
     float* mid = reinterpret_cast<float*>(base + w.mid);
     void* part = base + w.part;
-    const size_t part_bytes = w.total - w.part;
+    int32_t* t_rows = reinterpret_cast<int32_t*>(base + w.t);
+    const size_t part_bytes = w.t - w.part;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const float scale = 0.125f;                                   // 64^-0.5: Whisper scales q and k by 64^-0.25 each
-    hipLaunchKernelGGL(embed_kernel, dim3((R * (D / 4) + 255) / 256), dim3(256), 0, s, ids, d->tok_emb, d->pos_emb + (int64_t)position * D, x, (int)R,
-                       D / 4, Vp);
+    if (ctl)
+        hipLaunchKernelGGL(embed_rows_kernel, dim3((R * (D / 4) + 255) / 256), dim3(256), 0, s, ids, ctl, d->tok_emb, d->pos_emb, x, ctx, t_rows, (int)R,
+                           D / 4, Vp, d->max_pos < T_max ? d->max_pos : T_max);
+    else
+        hipLaunchKernelGGL(embed_kernel, dim3((R * (D / 4) + 255) / 256), dim3(256), 0, s, ids, d->tok_emb, d->pos_emb + (int64_t)position * D, x,
+                           (int)R, D / 4, Vp);
     for (int i = 0; i < d->layers; ++i) {
         const hirest_whisper_layer& L = d->layer[i];
         CK(ln_gemm(x, L.attn_ln_g, L.attn_ln_b, ln, L.qkv_w, L.qkv_b, qkv, R, 3 * D, D, 0, stream));
-        CK(hirest_attention_f32_decode_inplace(qkv, 3 * D, self_k[i], self_v[i], D, (int64_t)T_max * D, position, T_max, qkv + D, qkv + 2 * D, 3 * D,
-                                               ctx, R, H, scale, 0.f, 0.f, stream));
+        if (ctl)
+            CK(hirest_attention_f32_decode_inplace_rows(qkv, 3 * D, self_k[i], self_v[i], D, (int64_t)T_max * D, t_rows, T_max, qkv + D, qkv + 2 * D,
+                                                        3 * D, ctx, R, H, scale, 0.f, 0.f, stream));
+        else
+            CK(hirest_attention_f32_decode_inplace(qkv, 3 * D, self_k[i], self_v[i], D, (int64_t)T_max * D, position, T_max, qkv + D, qkv + 2 * D,
+                                                   3 * D, ctx, R, H, scale, 0.f, 0.f, stream));
         CK(hirest_gemm_f32(ctx, D, L.so_w, D, L.so_b, x, D, nullptr, 0, a, D, R, D, D, 0, stream));
         CK(ln_gemm(a, L.cross_ln_g, L.cross_ln_b, ln, L.cq_w, L.cq_b, qkv, R, D, D, 0, stream));
         CK(hirest_attention_f32_cross_decode(qkv, D, cross_kv[i], 2 * D, (int64_t)Tk * 2 * D, n_windows, Tk, row_window, ctx, D, R, H, scale, part,
@@ -427,4 +527,25 @@ extern "C" int hirest_whisper_decode_step(const hirest_whisper_decoder* d, int32
     }
     CK(ln_gemm(x, d->ln_g, d->ln_b, ln, d->tok_emb, d->lm_b, logits, R, Vp, D, 0, stream));
     return hirest_launch_status();
+}
+
+extern "C" int hirest_whisper_decode_step(const hirest_whisper_decoder* d, int32_t R, int32_t position, const int32_t* ids,
+                                          float* const* self_k, float* const* self_v, int32_t T_max, const float* const* cross_kv,
+                                          int32_t n_windows, int32_t Tk, const int32_t* row_window, float* logits, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    return decode_step(d, R, position, nullptr, ids, self_k, self_v, T_max, cross_kv, n_windows, Tk, row_window, logits, workspace, workspace_bytes,
+                       stream);
+}
+
+extern "C" size_t hirest_whisper_step_rows_workspace_bytes(const hirest_whisper_decoder* d, int32_t R, int32_t Tk) {
+    if (!d || R <= 0 || Tk <= 0) return 0;
+    return plan(d, R, Tk, true).total;
+}
+
+extern "C" int hirest_whisper_decode_step_rows(const hirest_whisper_decoder* d, int32_t R, const hirest_whisper_row_ctl* ctl, const int32_t* ids,
+                                               float* const* self_k, float* const* self_v, int32_t T_max, const float* const* cross_kv,
+                                               int32_t n_windows, int32_t Tk, const int32_t* row_window, float* logits, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+    if (!ctl) return HIREST_E_BADARG;
+    return decode_step(d, R, 0, ctl, ids, self_k, self_v, T_max, cross_kv, n_windows, Tk, row_window, logits, workspace, workspace_bytes, stream);
 }

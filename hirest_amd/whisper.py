@@ -32,7 +32,7 @@ import re
 import types
 import wave
 import zlib
-from typing import Dict, Iterable, List, Optional, Tuple, Union
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -484,9 +484,11 @@ def _canonical_decoder(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.T
 
 class KVCache:
     """What a decoding loop keeps between steps: per layer the preallocated self-attention cache ``[R, T_max, D]`` (key, value), the
-    cross-attention ``key(xa) | value(xa)`` rows ``[n_windows, Tk, 2 D]``, ``row_window [R]`` and the number of filled positions."""
+    cross-attention ``key(xa) | value(xa)`` rows ``[n_windows, Tk, 2 D]``, ``row_window [R]`` and the number of filled positions.
+    ``per_row``: the rows sit at positions of their own (``decode_many``): the workspace is ``hirest_whisper_decode_step_rows``'s and
+    ``length`` is not used."""
 
-    def __init__(self, decoder: "TextDecoder", xa: torch.Tensor, row_window: torch.Tensor, T_max: Optional[int] = None):
+    def __init__(self, decoder: "TextDecoder", xa: torch.Tensor, row_window: torch.Tensor, T_max: Optional[int] = None, per_row: bool = False):
         dev, D = xa.device, decoder.width
         self.R, self.T_max, self.length = int(row_window.numel()), int(T_max or decoder.ctx), 0
         self.n_windows, self.Tk = int(xa.shape[0]), int(xa.shape[1])
@@ -498,7 +500,9 @@ class KVCache:
         self.k_ptrs, self.v_ptrs = P(*(t.data_ptr() for t in self.self_k)), P(*(t.data_ptr() for t in self.self_v))
         self.x_ptrs = P(*(t.data_ptr() for t in self.cross_kv))
         self.logits = torch.empty((self.R, decoder.vocab_padded), dtype=torch.float32, device=dev)
-        need = _lib.load().hirest_whisper_step_workspace_bytes(C.byref(decoder._w()["desc"]), self.R, self.Tk)
+        lib = _lib.load()
+        need = (lib.hirest_whisper_step_rows_workspace_bytes if per_row else lib.hirest_whisper_step_workspace_bytes)(
+            C.byref(decoder._w()["desc"]), self.R, self.Tk)
         self.ws = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=dev)
 
 
@@ -1003,6 +1007,142 @@ def decode(model: "Whisper", mel: torch.Tensor, options: DecodingOptions = Decod
     return results[0] if single else results
 
 
+_PER_WINDOW_OPTIONS = ("prompt", "temperature", "best_of", "seed")     # what may differ between the windows of one decode_many call
+_ROWS_PER_CALL = 256           # hirest_gemm_f32_ln's forms, which the step's LayerNorm GEMMs rely on, take up to 256 rows
+FILES_IN_FLIGHT = 16           # transcribe_many's default: the largest of the sweep in DESIGN §4.17, where windows/s was still growing
+
+
+def new_row_ctl(rows, device) -> torch.Tensor:
+    """``hirest_whisper_row_ctl [R]`` as an int32 ``[R, 8]`` tensor from ``(position, step, max_steps, draw_row, seed, temperature)`` per row"""
+    ctl = np.zeros((len(rows), _lib.WHISPER_ROW_CTL_WORDS), dtype=np.int32)
+    for r, (position, step, max_steps, draw_row, seed, temperature) in enumerate(rows):
+        ctl[r, :4] = position, step, max_steps, draw_row
+        ctl[r, 4:5].view(np.uint32)[0] = int(seed) & 0xFFFFFFFF
+        ctl[r, 5:6].view(np.float32)[0] = float(temperature)
+    return torch.from_numpy(ctl).to(device)
+
+
+@torch.no_grad()
+def decode_many(model: "Whisper", mels, options: Union[DecodingOptions, Sequence[DecodingOptions]] = DecodingOptions(), *,
+                return_candidates: bool = False):
+    """``decode`` for W windows that need not share their options — the current windows of W files — in ONE decoding loop: ``mels`` W
+    spectrograms ``[n_mels, 3000]`` or encoder states ``[Tk, D]`` (a tensor or a sequence of them), ``options`` one ``DecodingOptions`` or
+    W of them.  ``prompt``, ``temperature``, ``best_of`` and ``seed`` may differ between windows; any other field that does raises
+    ValueError.  One encoder call and one cross key / value projection for all windows, one cache of all candidate rows, the B = 1
+    prefill per window, then per token ``hirest_whisper_decode_step_rows`` + ``hirest_whisper_step_tail_rows`` over all rows — each at
+    its own position, with its own temperature, seed and remaining room, kept in a device record per row — until no row is active.
+    Returns a list of W ``DecodingResult`` with the values ``decode`` gives window by window, bit for bit; ``return_candidates`` as
+    ``decode``'s.  More than 256 candidate rows are split into consecutive loops."""
+    tokenizer = model.tokenizer
+    if tokenizer is None:
+        raise ValueError("the model has no tokenizer: load_model(path, tokenizer=...) or set model.tokenizer")
+    mel = mels if torch.is_tensor(mels) else torch.stack([m.to(model.device) for m in mels])
+    if mel.ndim != 3:
+        raise ValueError(f"decode_many takes W windows [W, n_mels, frames] or [W, Tk, D], not a tensor of shape {tuple(mel.shape)}")
+    W = int(mel.shape[0])
+    opts = [options] * W if isinstance(options, DecodingOptions) else list(options)
+    if len(opts) != W:
+        raise ValueError(f"{len(opts)} DecodingOptions for {W} windows")
+    for f in dataclasses.fields(DecodingOptions):
+        if f.name not in _PER_WINDOW_OPTIONS and any(getattr(o, f.name) != getattr(opts[0], f.name) for o in opts):
+            raise ValueError(f"decode_many: {f.name} differs between the windows of one call (only {', '.join(_PER_WINDOW_OPTIONS)} may)")
+    dec, dev = model.decoder, model.device
+    n_audio_ctx = model.dims["n_audio_ctx"]
+    plans = []                                                        # per window: initial tokens, sot index, steps, candidate rows
+    for o in opts:
+        initial, sot_index = _initial_tokens(tokenizer, o, dec.ctx)
+        steps = min(dec.ctx, len(initial) + (o.sample_len or dec.ctx // 2)) - len(initial)
+        if steps <= 0:
+            raise ValueError(f"a prompt of {len(initial)} tokens leaves no room to sample in a context of {dec.ctx}")
+        plans.append((initial, sot_index, steps, (o.best_of or 1) if o.temperature > 0 else 1))
+    results, everything = [], []
+    with torch.cuda.device(dev):
+        if mel.shape[-2:] == (n_audio_ctx, model.dims["n_audio_state"]):
+            xa = mel.to(dev, torch.float32)
+        else:
+            xa = model.encoder(mel)
+        w0 = 0
+        while w0 < W:                                                 # consecutive windows, as many as fit the row limit (at least one)
+            w1, rows = w0 + 1, plans[w0][3]
+            while w1 < W and rows + plans[w1][3] <= _ROWS_PER_CALL:
+                rows += plans[w1][3]
+                w1 += 1
+            res, cands = _decode_rows(model, xa[w0:w1], opts[w0:w1], plans[w0:w1])
+            results += res
+            everything += cands
+            w0 = w1
+    return (results, everything) if return_candidates else results
+
+
+def _decode_rows(model, xa, opts, plans):
+    """one loop over the candidate rows of ``xa``'s windows (decode_many)"""
+    tokenizer, dec, dev, lib = model.tokenizer, model.decoder, model.device, _lib.load()
+    D, Vp = dec.width, dec.vocab_padded
+    first_row = np.cumsum([0] + [p[3] for p in plans]).tolist()
+    R = first_row[-1]
+    T_max = max(len(initial) + steps for initial, _, steps, _ in plans)
+    max_steps = max(steps for _, _, steps, _ in plans)
+    row_window = torch.tensor([w for w, p in enumerate(plans) for _ in range(p[3])], dtype=torch.int32)
+    kc = KVCache(dec, xa, row_window, T_max, per_row=True)
+    # the constants every window shares; temperature, seed, serial and sample_begin are the rows' own (hirest_whisper_row_ctl)
+    params, mask = tail_params(tokenizer, opts[0], dec.vocab, Vp, model.dims["n_audio_ctx"], 0, dev)
+    first = torch.empty((R, Vp), dtype=torch.float32, device=dev)
+    no_speech, ctl_rows = [], []
+    for w, (initial, sot_index, steps, group) in enumerate(plans):
+        r0, T = first_row[w], len(initial)
+
+        def keep(i, qkv):          # the prompt's keys / values, the same for every candidate row of the window
+            kc.self_k[i][r0:r0 + group, :T] = qkv[:, D:2 * D]
+            kc.self_v[i][r0:r0 + group, :T] = qkv[:, 2 * D:]
+        x = dec._sequences(torch.tensor([initial], dtype=torch.int32), [kv[w:w + 1] for kv in kc.cross_kv], kc.Tk, keep)
+        padded = dec._head(x)                                         # [T, vocab_padded]
+        first[r0:r0 + group].copy_(padded[T - 1].expand(group, -1))
+        scratch = None
+        if sot_index != T - 1 and tokenizer.no_speech is not None:    # no_speech_prob is read at the sot position, as decode() does
+            scratch, sid = new_row_state(1, dev), torch.empty(1, dtype=torch.int32, device=dev)
+            row = padded[sot_index].contiguous()
+            _lib.check(lib.hirest_whisper_step_tail(row.data_ptr(), Vp, 1, Vp, 0, 0, C.byref(params), scratch.data_ptr(), sid.data_ptr(), None,
+                                                    None, None, ops.stream_ptr()), "hirest_whisper_step_tail")
+        no_speech.append(scratch)
+        ctl_rows += [(T - 1, 0, steps, g, opts[w].seed, opts[w].temperature) for g in range(group)]
+    ctl = new_row_ctl(ctl_rows, dev)
+    state = new_row_state(R, dev)
+    tokens = torch.full((R, max_steps), tokenizer.eot, dtype=torch.int32, device=dev)
+    ids = torch.zeros((R,), dtype=torch.int32, device=dev)
+    stamp = torch.zeros(1, dtype=torch.int32).pin_memory()
+    desc, logits = C.byref(dec._w()["desc"]), first
+    for call in range(max_steps):
+        _lib.check(lib.hirest_whisper_step_tail_rows(logits.data_ptr(), Vp, R, Vp, call, max_steps, C.byref(params), ctl.data_ptr(), state.data_ptr(),
+                                                     ids.data_ptr(), tokens.data_ptr(), None, stamp.data_ptr(), ops.stream_ptr()),
+                   "hirest_whisper_step_tail_rows")
+        s = int(stamp[0])                                             # whatever call has landed by now: no wait
+        if (s & 1) or call == max_steps - 1:
+            break
+        _lib.check(lib.hirest_whisper_decode_step_rows(desc, R, ctl.data_ptr(), ids.data_ptr(), kc.k_ptrs, kc.v_ptrs, kc.T_max, kc.x_ptrs,
+                                                       kc.n_windows, kc.Tk, kc.row_window.data_ptr(), kc.logits.data_ptr(), kc.ws.data_ptr(),
+                                                       kc.ws.numel(), ops.stream_ptr()), "hirest_whisper_decode_step_rows")
+        logits = kc.logits
+    torch.cuda.current_stream().synchronize()
+    toks, st = tokens.cpu().numpy(), state.cpu()
+    sums = st[:, 5].view(torch.float32).tolist()
+    results, everything = [], []
+    for w, (initial, sot_index, steps, group) in enumerate(plans):
+        r0 = first_row[w]
+        nsp = (no_speech[w].cpu()[0] if no_speech[w] is not None else st[r0])[6:7].view(torch.float32).item()
+        cands = []
+        for g in range(group):
+            row = toks[r0 + g, :steps].tolist()
+            cands.append((row[:row.index(tokenizer.eot)] if tokenizer.eot in row else row, sums[r0 + g]))
+        best = max(range(group), key=lambda g: (cands[g][1] / max(len(cands[g][0]), 1), -g))
+        t, lp = cands[best]
+        text = tokenizer.decode(t).strip()
+        results.append(DecodingResult(audio_features=xa[w], language=tokenizer.language or "en", tokens=t, text=text,
+                                      avg_logprob=lp / (len(t) + 1), no_speech_prob=nsp, temperature=opts[w].temperature,
+                                      compression_ratio=compression_ratio(text) if text else 0.0))
+        everything.append(cands)
+    return results, everything
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the model, transcribe(), .srt
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -1042,6 +1182,9 @@ class Whisper(nn.Module):
     def transcribe(self, audio, **kw):
         return transcribe(self, audio, **kw)
 
+    def transcribe_many(self, audios, **kw):
+        return transcribe_many(self, audios, **kw)
+
 
 def load_model(path: str, device: Optional[Union[str, torch.device]] = None, tokenizer: Optional[Union[str, Tokenizer]] = None) -> Whisper:
     """A local OpenAI ``.pt`` checkpoint or a Hugging Face model directory -> ``Whisper``.  There are no model names and no downloads: a
@@ -1068,75 +1211,81 @@ def load_model(path: str, device: Optional[Union[str, torch.device]] = None, tok
     return model.to(device) if device is not None else model
 
 
-def transcribe(model, audio, *, temperature: Union[float, Tuple[float, ...]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
-               compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
-               no_speech_threshold: Optional[float] = 0.6, condition_on_previous_text: bool = True, initial_prompt: Optional[str] = None,
-               verbose=None, **decode_options):
-    """``whisper.transcribe``: a ``.wav`` path, a waveform or a ready spectrogram ``[n_mels, frames]`` (with its 30 s of padding) ->
-    ``{"text", "segments", "language"}``.  One spectrogram per file; 3000-frame windows from ``seek``; per window the temperature
-    fallback (the next temperature when the compression ratio or the average log-probability crosses its threshold), the no-speech
-    skip, segments cut at consecutive timestamp pairs, ``seek`` advanced to the last timestamp or by the whole window; the prompt of
-    the next window is the text so far, reset after a window decoded above temperature 0.5."""
-    tokenizer = decode_options.pop("tokenizer", None) or getattr(model, "tokenizer", None)
-    if tokenizer is None:
-        raise ValueError("no tokenizer: load_model(path, tokenizer=...) or transcribe(..., tokenizer=...)")
-    language = decode_options.get("language")
-    if getattr(model, "is_multilingual", False):
-        if language is None:
-            raise NotImplementedError("language detection is not built: pass language= for a multilingual model")
-    else:
-        language = "en"
-    if isinstance(language, str) and language.lower() == "english":
-        language = "en"
-    dims = model.dims
-    if torch.is_tensor(audio) and audio.ndim == 2:
-        mel = audio
-    else:
-        mel = log_mel_spectrogram(audio, dims["n_mels"], padding=N_SAMPLES, device=model.device)
-    content_frames = mel.shape[-1] - N_FRAMES
-    input_stride = N_FRAMES // dims["n_audio_ctx"]                    # mel frames per encoder position: 2
-    time_precision = input_stride * HOP_LENGTH / SAMPLE_RATE          # 0.02 s per timestamp token
-    temperatures = (temperature,) if isinstance(temperature, (int, float)) else tuple(temperature)
-    tb, eot = tokenizer.timestamp_begin, tokenizer.eot
+class _FileWalk:
+    """``transcribe()``'s walk over one file, cut at its decode calls so that one caller can drive one file with ``decode`` and another
+    the current windows of several files with ``decode_many``: ``next_request()`` is the next (window, options) to decode, or None when
+    the file is done; ``accept(result)`` takes that request's result — it moves on to the next fallback temperature of the same window
+    or settles the window (no-speech skip, segments, ``seek``, prompt reset); ``result()`` is ``transcribe()``'s dict."""
 
-    def decode_with_fallback(segment) -> DecodingResult:
-        result = None
-        for t in temperatures:
-            kw = dict(decode_options)
-            for k in (("beam_size", "patience") if t > 0 else ("best_of",)):      # the sampling branch has no beams, the greedy one no candidates
-                kw.pop(k, None)
-            result = decode(model, segment, DecodingOptions(**kw, temperature=float(t)))
-            again = compression_ratio_threshold is not None and result.compression_ratio > compression_ratio_threshold
-            again = again or (logprob_threshold is not None and result.avg_logprob < logprob_threshold)
-            if not again:
-                break
-        return result
+    def __init__(self, model, audio, *, temperature: Union[float, Tuple[float, ...]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
+                 compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
+                 no_speech_threshold: Optional[float] = 0.6, condition_on_previous_text: bool = True, initial_prompt: Optional[str] = None,
+                 verbose=None, **decode_options):
+        self.tokenizer = tokenizer = decode_options.pop("tokenizer", None) or getattr(model, "tokenizer", None)
+        if tokenizer is None:
+            raise ValueError("no tokenizer: load_model(path, tokenizer=...) or transcribe(..., tokenizer=...)")
+        language = decode_options.get("language")
+        if getattr(model, "is_multilingual", False):
+            if language is None:
+                raise NotImplementedError("language detection is not built: pass language= for a multilingual model")
+        else:
+            language = "en"
+        if isinstance(language, str) and language.lower() == "english":
+            language = "en"
+        self.language = language
+        dims = model.dims
+        if torch.is_tensor(audio) and audio.ndim == 2:
+            self.mel = audio
+        else:
+            self.mel = log_mel_spectrogram(audio, dims["n_mels"], padding=N_SAMPLES, device=model.device)
+        self.content_frames = self.mel.shape[-1] - N_FRAMES
+        self.input_stride = N_FRAMES // dims["n_audio_ctx"]           # mel frames per encoder position: 2
+        self.time_precision = self.input_stride * HOP_LENGTH / SAMPLE_RATE      # 0.02 s per timestamp token
+        self.temperatures = (temperature,) if isinstance(temperature, (int, float)) else tuple(temperature)
+        self.compression_ratio_threshold, self.logprob_threshold = compression_ratio_threshold, logprob_threshold
+        self.no_speech_threshold, self.condition_on_previous_text = no_speech_threshold, condition_on_previous_text
+        self.decode_options = decode_options
+        self.seek, self.all_tokens, self.all_segments, self.reset_since = 0, [], [], 0
+        self.attempt = 0                                              # index of the fallback temperature the current window is at
+        if initial_prompt is not None:
+            self.all_tokens.extend(tokenizer.encode(" " + initial_prompt.strip()))
 
-    seek, all_tokens, all_segments, reset_since = 0, [], [], 0
-    if initial_prompt is not None:
-        all_tokens.extend(tokenizer.encode(" " + initial_prompt.strip()))
+    def next_request(self):
+        if self.seek >= self.content_frames:
+            return None
+        t = self.temperatures[self.attempt]
+        kw = dict(self.decode_options)
+        kw["prompt"] = self.all_tokens[self.reset_since:]
+        for k in (("beam_size", "patience") if t > 0 else ("best_of",)):      # the sampling branch has no beams, the greedy one no candidates
+            kw.pop(k, None)
+        return pad_or_trim(self.mel[:, self.seek:self.seek + N_FRAMES], N_FRAMES), DecodingOptions(**kw, temperature=float(t))
 
-    def add_segment(start: float, end: float, tokens: List[int], result: DecodingResult):
-        text = tokenizer.decode([t for t in tokens if t < eot])
+    def _add_segment(self, start: float, end: float, tokens: List[int], result: DecodingResult):
+        text = self.tokenizer.decode([t for t in tokens if t < self.tokenizer.eot])
         if not text.strip():
             return
-        all_segments.append({"id": len(all_segments), "seek": seek, "start": start, "end": end, "text": text, "tokens": list(tokens),
-                             "temperature": result.temperature, "avg_logprob": result.avg_logprob,
-                             "compression_ratio": result.compression_ratio, "no_speech_prob": result.no_speech_prob})
-        all_tokens.extend(tokens)
+        self.all_segments.append({"id": len(self.all_segments), "seek": self.seek, "start": start, "end": end, "text": text,
+                                  "tokens": list(tokens), "temperature": result.temperature, "avg_logprob": result.avg_logprob,
+                                  "compression_ratio": result.compression_ratio, "no_speech_prob": result.no_speech_prob})
+        self.all_tokens.extend(tokens)
 
-    while seek < content_frames:
+    def accept(self, result: DecodingResult) -> None:
+        again = self.compression_ratio_threshold is not None and result.compression_ratio > self.compression_ratio_threshold
+        again = again or (self.logprob_threshold is not None and result.avg_logprob < self.logprob_threshold)
+        if again and self.attempt + 1 < len(self.temperatures):
+            self.attempt += 1                                         # the same window again, at the next temperature
+            return
+        self.attempt = 0
+        tb, seek, input_stride, time_precision = self.tokenizer.timestamp_begin, self.seek, self.input_stride, self.time_precision
+        add_segment, logprob_threshold = self._add_segment, self.logprob_threshold
         window_start = seek
         time_offset = seek * HOP_LENGTH / SAMPLE_RATE
-        segment_size = min(N_FRAMES, content_frames - seek)
-        segment = pad_or_trim(mel[:, seek:seek + N_FRAMES], N_FRAMES)
-        decode_options["prompt"] = all_tokens[reset_since:]
-        result = decode_with_fallback(segment)
+        segment_size = min(N_FRAMES, self.content_frames - seek)
         tokens = list(result.tokens)
-        if no_speech_threshold is not None and result.no_speech_prob > no_speech_threshold and \
+        if self.no_speech_threshold is not None and result.no_speech_prob > self.no_speech_threshold and \
                 not (logprob_threshold is not None and result.avg_logprob > logprob_threshold):
-            seek += segment_size                                      # silence: skip the window
-            continue
+            self.seek = seek + segment_size                           # silence: skip the window
+            return
         is_ts = [t >= tb for t in tokens]
         single_ending = is_ts[-2:] == [False, True]
         cuts = [i + 1 for i in range(len(tokens) - 1) if is_ts[i] and is_ts[i + 1]]
@@ -1161,10 +1310,65 @@ def transcribe(model, audio, *, temperature: Union[float, Tuple[float, ...]] = (
             seek += segment_size
         if seek <= window_start:                                      # (a last pair that closes at <|0.00|>, possible only without the
             seek = window_start + segment_size                        #  monotonic rule, would decode the same window for ever)
-        if not condition_on_previous_text or result.temperature > 0.5:
-            reset_since = len(all_tokens)
-    text_tokens = [t for s in all_segments for t in s["tokens"] if t < eot]
-    return {"text": tokenizer.decode(text_tokens), "segments": all_segments, "language": language}
+        self.seek = seek                                              # (after the segments: they carry the window's own seek)
+        if not self.condition_on_previous_text or result.temperature > 0.5:
+            self.reset_since = len(self.all_tokens)
+
+    def result(self) -> Dict[str, object]:
+        text_tokens = [t for s in self.all_segments for t in s["tokens"] if t < self.tokenizer.eot]
+        return {"text": self.tokenizer.decode(text_tokens), "segments": self.all_segments, "language": self.language}
+
+
+def transcribe(model, audio, **kw):
+    """``whisper.transcribe``: a ``.wav`` path, a waveform or a ready spectrogram ``[n_mels, frames]`` (with its 30 s of padding) ->
+    ``{"text", "segments", "language"}``.  One spectrogram per file; 3000-frame windows from ``seek``; per window the temperature
+    fallback (the next temperature when the compression ratio or the average log-probability crosses its threshold), the no-speech
+    skip, segments cut at consecutive timestamp pairs, ``seek`` advanced to the last timestamp or by the whole window; the prompt of
+    the next window is the text so far, reset after a window decoded above temperature 0.5.  Keywords: ``temperature`` (one or a tuple,
+    default 0.0 .. 1.0 in steps of 0.2), ``compression_ratio_threshold`` (2.4), ``logprob_threshold`` (-1.0), ``no_speech_threshold``
+    (0.6), ``condition_on_previous_text`` (True), ``initial_prompt``, ``verbose``, ``tokenizer``; the rest are ``DecodingOptions``."""
+    walk = _FileWalk(model, audio, **kw)
+    while True:
+        request = walk.next_request()
+        if request is None:
+            return walk.result()
+        walk.accept(decode(model, *request))
+
+
+def transcribe_many(model, audios, *, files_in_flight: int = FILES_IN_FLIGHT, **kw):
+    """``transcribe()`` of every item of ``audios`` (keywords as ``transcribe``'s, the same for all), with the current windows of up
+    to ``files_in_flight`` files decoded together by ``decode_many``: a file's windows stay in order, files are independent.  After a
+    round every file takes its result (a fallback is simply its request of the next round); a file that ends hands its slot to the
+    next one.  Returns the files' dicts in input order, each equal to ``transcribe()``'s."""
+    if files_in_flight < 1:
+        raise ValueError(f"files_in_flight = {files_in_flight}: at least one file")
+    audios = list(audios)
+    out: List[Optional[Dict[str, object]]] = [None] * len(audios)
+    waiting = iter(range(len(audios)))
+    slots: List[Optional[tuple]] = [None] * files_in_flight          # (file index, its walk, its request)
+
+    def seat(walk_of_slot):
+        """the slot's file with its next request; a file without one is finished and the next waiting file takes the slot"""
+        while True:
+            if walk_of_slot is None:
+                i = next(waiting, None)
+                if i is None:
+                    return None
+                walk_of_slot = (i, _FileWalk(model, audios[i], **kw))
+            i, walk = walk_of_slot
+            request = walk.next_request()
+            if request is not None:
+                return i, walk, request
+            out[i] = walk.result()
+            walk_of_slot = None
+    slots = [seat(None) for _ in slots]
+    while any(s is not None for s in slots):
+        live = [s for s in slots if s is not None]
+        results = decode_many(model, [s[2][0] for s in live], [s[2][1] for s in live])
+        for (i, walk, _), result in zip(live, results):
+            walk.accept(result)
+        slots = [seat(s[:2]) if s is not None else None for s in slots]
+    return out
 
 
 def format_timestamp(seconds: float, always_include_hours: bool = False, decimal_marker: str = ".") -> str:

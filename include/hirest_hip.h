@@ -1277,6 +1277,12 @@ int hirest_mel_to_rows(const float* mel, float* rows, int32_t B, int32_t n_mels,
 int hirest_attention_f32_decode_inplace(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ld_cache, int64_t row_stride,
                                         int32_t t, int32_t T_max, const float* k_new, const float* v_new, int64_t ld_new, float* out,
                                         int32_t R, int32_t H, float scale, float add_const, float causal_penalty, void* stream);
+/* The same with a position per row: t [R] device ints, row r appends at t[r] and attends to its keys j <= t[r].  A row
+ * with t[r] outside [0, T_max) is inactive: its blocks return before any load, and neither its cache nor its out row is written.  For
+ * every other row the arithmetic and its order are hirest_attention_f32_decode_inplace's at t = t[r]: the same bits. */
+int hirest_attention_f32_decode_inplace_rows(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ld_cache, int64_t row_stride,
+                                             const int32_t* t, int32_t T_max, const float* k_new, const float* v_new, int64_t ld_new, float* out,
+                                             int32_t R, int32_t H, float scale, float add_const, float causal_penalty, void* stream);
 /* softmax(q k^T scale) v for ONE query per row against a long key set shared by rows, head width 64.  kv: n_windows arrays
  * [Tk, ldkv >= 2 * H * 64] of key | value rows (key of head h at column 64 h, value at 64 (H + h)), window w at kv + w * window_stride,
  * 16-byte aligned; row_window: R device ints, row r attends to window row_window[r] (a row whose window is outside [0, n_windows)
@@ -1327,6 +1333,28 @@ typedef struct hirest_whisper_tail_params {
 int hirest_whisper_step_tail(const float* logits, int64_t ldx, int32_t R, int32_t V, int32_t step, int32_t T_max,
                              const hirest_whisper_tail_params* params, hirest_whisper_row_state* state, int32_t* next_ids, int32_t* tokens,
                              float* logprobs, int32_t* done_host, void* stream);
+/* What a row of a call over several windows has of its own, on the device, 8 words.  The host writes it when a round
+ * starts; hirest_whisper_step_tail_rows advances it; hirest_whisper_decode_step_rows reads it. */
+typedef struct hirest_whisper_row_ctl {
+    int32_t position;             /* before a tail call: the row's last filled cache position; the tail advances it, so the decode step that
+                                   * follows finds the position its new token takes.  < 0: the row is inactive */
+    int32_t step;                 /* picks made so far: the draw's serial and the column of `tokens` the next pick goes to */
+    int32_t max_steps;            /* the row goes inactive after this many picks */
+    int32_t draw_row;             /* the row's index among its own window's candidates: the generator's row */
+    uint32_t seed;
+    float   temperature;
+    int32_t reserved[2];
+} hirest_whisper_row_ctl;
+/* hirest_whisper_step_tail for rows of several windows: the shared constants come from params, whose temperature, seed, serial and
+ * sample_begin are ignored; a row's step, temperature and seed come from ctl[r], the draw is keyed by (seed, serial = step, row =
+ * draw_row, token).  An active row (position >= 0) that can still pick (step < max_steps, step < ld_tokens, not completed) gets
+ * exactly the single-window call's arithmetic; its pick goes to next_ids[r] and tokens[r * ld_tokens + step]; then step += 1,
+ * position += 1, and position = -1 when the pick was eot or step reached max_steps (the latter neither sets completed nor writes an
+ * eot).  An active row that cannot pick only gets position = -1.  Nothing of an inactive row is read past its record or written.
+ * done_host (optional, pinned host): *done_host = ((call + 1) << 1) | (no row is active). */
+int hirest_whisper_step_tail_rows(const float* logits, int64_t ldx, int32_t R, int32_t V, int32_t call, int64_t ld_tokens,
+                                  const hirest_whisper_tail_params* params, hirest_whisper_row_ctl* ctl, hirest_whisper_row_state* state,
+                                  int32_t* next_ids, int32_t* tokens, float* logprobs, int32_t* done_host, void* stream);
 /* out[r * V + v] = the generator's 24 bits for (seed, serial, row r, token v) (tests) */
 int hirest_whisper_gumbel_bits(uint32_t seed, uint32_t serial, int32_t R, int32_t V, uint32_t* out, void* stream);
 
@@ -1357,6 +1385,15 @@ size_t hirest_whisper_step_workspace_bytes(const hirest_whisper_decoder* d, int3
 int hirest_whisper_decode_step(const hirest_whisper_decoder* d, int32_t R, int32_t position, const int32_t* ids, float* const* self_k,
                                float* const* self_v, int32_t T_max, const float* const* cross_kv, int32_t n_windows, int32_t Tk,
                                const int32_t* row_window, float* logits, void* workspace, size_t workspace_bytes, void* stream);
+/* The step for rows at different positions (windows of several files in one loop): row r embeds ids[r] at ctl[r].position and its
+ * self-attention appends there (hirest_attention_f32_decode_inplace_rows); every other call is hirest_whisper_decode_step's, in the same
+ * order, so an active row's logits have the bits of that step at its position.  A row whose position is outside [0, min(max_pos,
+ * T_max)) is inactive: its caches are not written; it passes through the GEMMs on defined values (its id at position 0, a zero
+ * context row) and its logits row means nothing. */
+size_t hirest_whisper_step_rows_workspace_bytes(const hirest_whisper_decoder* d, int32_t R, int32_t Tk);
+int hirest_whisper_decode_step_rows(const hirest_whisper_decoder* d, int32_t R, const hirest_whisper_row_ctl* ctl, const int32_t* ids,
+                                    float* const* self_k, float* const* self_v, int32_t T_max, const float* const* cross_kv, int32_t n_windows,
+                                    int32_t Tk, const int32_t* row_window, float* logits, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,7 +27,11 @@ def main(argv=None):
     ap.add_argument("--tokenizer", type=str, default=None, help="directory with vocab.json and merges.txt (default: --model)")
     ap.add_argument("--device", type=str, default="cuda")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--files_in_flight", type=int, default=whisper.FILES_IN_FLIGHT,
+                    help="files whose current windows are decoded together (whisper.transcribe_many); 1: one file at a time (whisper.transcribe)")
     args = ap.parse_args(argv)
+    if args.files_in_flight < 1:
+        ap.error("--files_in_flight must be at least 1")
     print(args)
 
     model = whisper.load_model(args.model, args.device, tokenizer=args.tokenizer).eval()
@@ -43,8 +47,12 @@ def main(argv=None):
 
     out_dir = Path(args.asr_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
-    for wav in sorted(Path(args.audio_dir).glob("*.wav")):
-        result = whisper.transcribe(model, str(wav), temperature=temperatures, **options)
+    wavs = sorted(Path(args.audio_dir).glob("*.wav"))
+    if args.files_in_flight > 1:                                      # the current windows of that many files share one decoding loop
+        results = whisper.transcribe_many(model, [str(w) for w in wavs], files_in_flight=args.files_in_flight, temperature=temperatures, **options)
+    else:
+        results = (whisper.transcribe(model, str(wav), temperature=temperatures, **options) for wav in wavs)
+    for wav, result in zip(wavs, results):
         with open(out_dir / (wav.stem + ".srt"), "w", encoding="utf-8") as f:
             whisper.utils.write_srt(result["segments"], file=f)
         print(f"{wav.name}: {len(result['segments'])} segments")

@@ -3,9 +3,10 @@
 windows per second through ``log_mel_spectrogram`` + ``AudioEncoder.forward`` for 1 and 8 windows per call, the split between the
 front end, the convolution stem and the blocks (each timed on its own, a device synchronise closing every timed window), and the
 encoder's rate as a fraction of the 157-TFLOP/s fp32 MFMA peak DESIGN.md uses for the joint model.  Operations are counted from the
-shapes.  Each figure is the median with the min .. max spread over the repeats.
+shapes.  Each figure is the median with the min .. max spread over the repeats.  The decode leg: W windows through one
+``decode_many`` loop against W sequential ``decode`` calls at small.en's decoder shape.
 
-    python tools/whisper_bench.py [--repeats 7] [--warmup 2] [--batches 1 8]
+    python tools/whisper_bench.py [--repeats 7] [--warmup 2] [--batches 1 8] [--legs encoder decode] [--windows 1 2 4 8 16]
 """
 import argparse
 import json
@@ -53,15 +54,56 @@ def timed(fn, repeats, warmup, min_window=0.25):
     return out
 
 
+def decode_leg(a, dev):
+    """W windows of small.en's shape (random weights, random encoder states) with best_of 5 and 64 forced steps — the eot embedding is
+    biased so far down that no row ends — through one decode_many() loop against W sequential decode() calls, the single-window path, in
+    the same process; and the same two with one step, which is the prefill and everything else a window costs before its loop."""
+    cfg = synth._dec_config(768, 12, 12, 1500, 51864, 448)
+    eot, steps = 50256, 64
+    sd = synth.whisper_decoder_state_dict(cfg, 83, eot, -8.0)
+    sd.update({"encoder." + k: v for k, v in synth.whisper_encoder_state_dict({**cfg, "encoder_layers": 1}, 73).items()})
+    tok = synth.whisper_tokenizer(eot)
+    tok.decode = lambda ids: ""                                       # random weights pick ids the synthetic vocabulary cannot spell; no text is needed
+    model = whisper.Whisper({**cfg, "encoder_layers": 1}, sd, tok).to(dev)                                 # the encoder is not run: states go in
+    full = whisper.DecodingOptions(temperature=0.4, best_of=5, seed=5, sample_len=steps)
+    one = whisper.DecodingOptions(temperature=0.4, best_of=5, seed=5, sample_len=1)
+    xa_all = synth.whisper_audio_states(cfg, max(a.windows), 7).to(dev)
+    print(f"decode: small.en's decoder shape, best_of 5, {steps} forced steps, medians of {a.repeats} after {a.warmup} warm-up calls")
+    print("   W | decode_many: windows/s  ms/step  prefill share | W x decode: windows/s  ms/step  prefill share | ratio")
+    table = {}
+    for W in a.windows:
+        xa = xa_all[:W]
+        res, cands = whisper.decode_many(model, xa, full, return_candidates=True)
+        assert all(len(t) == steps for c in cands for t, _ in c), "a row ended before its forced steps: lower the eot bias"
+        assert [r.tokens for r in res] == [whisper.decode(model, xa[w], full).tokens for w in range(W)]
+        med = lambda fn: statistics.median(timed(fn, a.repeats, a.warmup, min_window=0.0))
+        many, many1 = med(lambda: whisper.decode_many(model, xa, full)), med(lambda: whisper.decode_many(model, xa, one))
+        seq = med(lambda: [whisper.decode(model, xa[w], full) for w in range(W)])
+        seq1 = med(lambda: [whisper.decode(model, xa[w], one) for w in range(W)])
+        row = {"many_windows_per_s": W / many, "many_ms_per_step": (many - many1) / (steps - 1) * 1e3, "many_prefill_share": many1 / many,
+               "sequential_windows_per_s": W / seq, "sequential_ms_per_step": (seq - seq1) / (steps - 1) / W * 1e3,
+               "sequential_prefill_share": seq1 / seq}
+        table[str(W)] = row
+        print(f"  {W:2d} | {row['many_windows_per_s']:22.2f}  {row['many_ms_per_step']:7.3f}  {row['many_prefill_share']:13.3f} | "
+              f"{row['sequential_windows_per_s']:21.2f}  {row['sequential_ms_per_step']:7.3f}  {row['sequential_prefill_share']:13.3f} | "
+              f"{seq / many:5.2f}")
+    return table
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--legs", nargs="+", choices=["encoder", "decode"], default=["encoder", "decode"])
+    ap.add_argument("--windows", type=int, nargs="+", default=[1, 2, 4, 8, 16], help="windows per decode_many() call of the decode leg")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("whisper_bench needs an MI355X: there is nothing to measure without one")
     dev = torch.device("cuda:0")
+    if "encoder" not in a.legs:
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "decode": decode_leg(a, dev)}))
+        return
     cfg = synth.WHISPER_SMALL_EN
     enc = whisper.AudioEncoder(cfg, synth.whisper_encoder_state_dict(cfg, 73)).to(dev)
     audio = torch.from_numpy(synth.audio_clip("mixed", whisper.N_SAMPLES, 71)).to(dev)
@@ -88,6 +130,8 @@ def main():
                                      "windows_per_s": 1.0 / per_window, "front_end_share": t_front / per_window,
                                      "encoder_tflops": B * (stem_flop + block_flop) / t_whole / 1e12,
                                      "fraction_of_fp32_mfma_peak": B * (stem_flop + block_flop) / t_whole / FP32_MFMA_PEAK}
+    if "decode" in a.legs:
+        result["decode"] = decode_leg(a, dev)
     print(json.dumps(result))
 
 
