@@ -726,6 +726,15 @@ WHISPER_DEC_Q = _dec_config(128, 2, 2, 261, 200, 48)
 WHISPER_DEC_R = _dec_config(256, 4, 1, 1500, 51864, 32)
 # case -> (config, eot, decoder seed, windows)
 WHISPER_DEC_CASES = {"p": (WHISPER_DEC_P, 100, 81, 1), "q": (WHISPER_DEC_Q, 100, 82, 2), "r": (WHISPER_DEC_R, 50256, 83, 1)}
+# The widths and head counts of the released checkpoints (tests/test_gpu_whisper_widths.py), one layer and 70 audio positions each (two key
+# chunks, the second ragged).  s: small.en's width with a vocabulary past 8192 columns, where the LM head takes the branches 51864 takes;
+# w384 / w512 / w1024 / w1280: tiny's, base's, medium's and large's width.
+WHISPER_DEC_S = _dec_config(768, 12, 1, 70, 8200, 24)
+WHISPER_DEC_CASES.update({"s": (WHISPER_DEC_S, 8000, 84, 3),
+                          "w384": (_dec_config(384, 6, 1, 70, 200, 16), 100, 85, 1), "w512": (_dec_config(512, 8, 1, 70, 200, 16), 100, 86, 1),
+                          "w1024": (_dec_config(1024, 16, 1, 70, 200, 16), 100, 87, 1),
+                          "w1280": (_dec_config(1280, 20, 1, 70, 200, 16), 100, 88, 1)})
+WHISPER_DEC_WIDTH_CASES = ("s", "w384", "w512", "w1024", "w1280")
 
 
 def whisper_decoder_shapes(c: dict) -> Dict[str, Tuple[int, ...]]:
@@ -778,7 +787,7 @@ def whisper_audio_states(c: dict, windows: int, seed: int) -> torch.Tensor:
 
 def whisper_vocab(eot: int) -> Tuple[Dict[str, int], list]:
     """A byte-level vocabulary of ``eot`` text ids for the tokenizer tests: the 256 byte symbols first when they fit (else the printable
-    ASCII ones), then a few merges."""
+    ASCII ones), then a few merges, then unmerged two-symbol strings up to ``eot``."""
     from .bytebpe import bytes_to_unicode
     alphabet = list(bytes_to_unicode().values())
     if eot < 300:
@@ -791,12 +800,21 @@ def whisper_vocab(eot: int) -> Tuple[Dict[str, int], list]:
         if a in vocab and b in vocab and a + b not in vocab and len(vocab) < eot:
             vocab[a + b] = len(vocab)
             merges.append(f"{a} {b}")
+    # the text ids left over (a vocabulary of thousands): two-symbol strings no merge produces, so that encode() is unchanged and every id
+    # a decoder can pick has a text
+    if len(vocab) < eot:
+        for a in alphabet:
+            for b in alphabet:
+                if len(vocab) == eot:
+                    return vocab, merges
+                if a + b not in vocab:
+                    vocab[a + b] = len(vocab)
     return vocab, merges
 
 
 # added to the eot embedding along the final LayerNorm's bias (whisper_decoder_state_dict): case p's greedy fixtures end by eot, case q's
-# run to sample_len
-WHISPER_DEC_EOT_BIAS = {"p": 0.5, "q": 0.0, "r": 0.0}
+# run to sample_len, case s's ends by eot inside its 12 sampled positions
+WHISPER_DEC_EOT_BIAS = {"p": 0.5, "q": 0.0, "r": 0.0, "s": 3.0, "w384": 0.0, "w512": 0.0, "w1024": 0.0, "w1280": 0.0}
 
 
 def token_ids(name: str, n: int, vocab: int, seed: int) -> np.ndarray:

@@ -142,3 +142,50 @@ def cross_attention(q, k, v, scale, dtype=np.float64):
     s = np.einsum("hd,thd->ht", q, k) * dtype(scale)
     p = np.exp(s - s.max(axis=1, keepdims=True))
     return np.einsum("ht,thd->hd", p, v) / p.sum(axis=1, keepdims=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# which fp32 GEMM kernel each call of a decode step gets (tests/test_gpu_whisper_widths.py and its host-side twin)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+STEP_ROW_COUNTS = [1, 5, 16, 17, 32, 33, 47, 48, 80, 96, 256]        # around 16 / 32 / 48 rows, transcribe_many's 80, the limit of a call
+
+
+def step_dispatch(R, D, I, Vp, **fields):
+    """call of hirest_whisper_decode_step -> (status, name) of hirest_gemm_f32_dispatch_name for R rows of a decoder of width D, MLP
+    width I and Vp LM-head columns: ``qkv``, ``cross_q``, ``fc1`` and ``head`` are ln_gemm's (the ``ln`` entry where it takes the fused
+    form, else the plain product after hirest_layernorm; ``*_fused`` says which), ``self_out``, ``cross_out`` and ``fc2`` the plain
+    product with a residual.  ``fields``: cus and the switches (default: the device's and the process's)."""
+    import ctypes
+    from hirest_amd import _lib
+
+    def name(entry, M, N, K, **kw):
+        buf = ctypes.create_string_buffer(64)
+        status = _lib.load().hirest_gemm_f32_dispatch_name(ctypes.byref(_lib.GemmF32Query.make(entry, M, N, K, **fields, **kw)), buf, 64)
+        return status, buf.value.decode() if status == 0 else ""
+
+    out = {}
+    for call, N in (("qkv", 3 * D), ("cross_q", D), ("fc1", I), ("head", Vp)):
+        fused = R <= 256 and D % 256 == 0 and D <= 1024 and (N < 8192 or (D == 768 and R <= 32))      # ln_gemm() in csrc/whisper_dec.hip
+        out[call] = name("ln", R, N, D) if fused else name("gemm", R, N, D)
+        out[call + "_fused"] = fused
+    out["self_out"] = out["cross_out"] = name("gemm", R, D, D, has_resid=1)
+    out["fc2"] = name("gemm", R, D, I, has_resid=1)
+    return out
+
+
+def check_small_en_step_families(R, names):
+    """the kernel families a step of R rows takes at small.en's width (768, MLP 3072, 8192 or more LM-head columns)"""
+    ok = lambda call: names[call][0] == 0
+    assert all(ok(c) for c in ("qkv", "cross_q", "fc1", "head", "self_out", "cross_out", "fc2")), names
+    assert names["qkv_fused"] and names["cross_q_fused"] and names["fc1_fused"] and names["head_fused"] == (R <= 32), names
+    assert names["cross_q"][1] == "m16ln<3,1,2>", names
+    if R <= 32:
+        assert names["qkv"][1] == names["fc1"][1] == "m16ln<3,1,2>", names
+        assert names["self_out"][1] == names["fc2"][1] == "m16<1,1,8>", names
+        assert names["head"][1].startswith("m16ln_stream<"), names
+    else:
+        assert all(names[c][1].startswith("rows<mt=") and ",ln" in names[c][1] for c in ("qkv", "fc1")), names
+        assert names["self_out"][1] == "m16<2,1,6>" and names["fc2"][1] == "m16<1,1,4>", names
+        head = names["head"][1]
+        assert head in ("skinny", "tile64") or (head.startswith("rows<mt=") and ",ln" not in head), names

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Fixtures of the Whisper text decoder: tests/golden/whisper_dec_{p,q,r}.npz.
+"""Fixtures of the Whisper text decoder: tests/golden/whisper_dec_{p,q,r,s,w384,w512,w1024,w1280}.npz.
 
 Whisper is not part of the reference tree, so the yardstick is ``transformers``' WhisperDecoder run in float64 on ``hirest_amd.synth``'s
 seeded weights, and its own logits processors (SuppressTokensAtBegin, SuppressTokens, WhisperTimeStampLogitsProcessor) for the greedy
@@ -7,7 +7,8 @@ token sequences.  The fixtures hold the fp64 states before the LM head (the test
 51864 logits would not fit a committed file), the error of the same forward in fp32 on the CPU — the tests' yardstick — and the greedy
 sequences.  A greedy fixture is refused when any step's top-2 margin is below 100 x that error: no step of it is then excused.
 
-    python tests/golden/make_whisper_dec_golden.py
+    python tests/golden/make_whisper_dec_golden.py              the cases of the released widths: s w384 w512 w1024 w1280
+    python tests/golden/make_whisper_dec_golden.py p q r        the named cases
 """
 import os
 import sys
@@ -21,8 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 from hirest_amd import synth  # noqa: E402
 
-SAMPLE_LEN = 24
-TEACHER_T = {"p": 12, "q": 12, "r": 6}
+TEACHER_T = {"p": 12, "q": 12, "r": 6, "s": 6, "w384": 6, "w512": 6, "w1024": 6, "w1280": 6}
+GREEDY = {"p": ((0, 0), (0, 1), (1, 0), (1, 1)), "q": ((0, 0), (0, 1), (1, 0), (1, 1)), "s": ((0, 0),)}      # case -> (prompt, without_timestamps)
 
 
 def hf_decoder(cfg, sd, dtype):
@@ -49,7 +50,7 @@ def logits_of(dec, emb, tokens, xa):
     return h, h @ emb.T
 
 
-def greedy(dec64, dec32, emb, xa, initial, sample_begin, sot_index, consts, without_timestamps):
+def greedy(dec64, dec32, emb, xa, initial, sample_begin, sot_index, consts, without_timestamps, sample_len):
     from transformers.generation.logits_process import (SuppressTokensAtBeginLogitsProcessor, SuppressTokensLogitsProcessor,
                                                         WhisperTimeStampLogitsProcessor)
     procs = [SuppressTokensAtBeginLogitsProcessor([consts["blank"], consts["eot"]], sample_begin),
@@ -59,7 +60,7 @@ def greedy(dec64, dec32, emb, xa, initial, sample_begin, sot_index, consts, with
                                    max_initial_timestamp_index=consts["max_initial_timestamp_index"])
         procs.append(WhisperTimeStampLogitsProcessor(gc, sample_begin))
     tokens, sum_lp, no_speech, worst, err = list(initial), 0.0, None, np.inf, 0.0
-    for _ in range(SAMPLE_LEN):
+    for _ in range(sample_len):
         ids = torch.tensor([tokens])
         _, l64 = logits_of(dec64, emb, ids, xa)
         _, l32 = logits_of(dec32, emb.float(), ids, xa)
@@ -81,7 +82,8 @@ def greedy(dec64, dec32, emb, xa, initial, sample_begin, sot_index, consts, with
 
 
 def main():
-    for case, (cfg, eot, seed, windows) in synth.WHISPER_DEC_CASES.items():
+    for case in sys.argv[1:] or synth.WHISPER_DEC_WIDTH_CASES:
+        cfg, eot, seed, windows = synth.WHISPER_DEC_CASES[case]
         sd = synth.whisper_decoder_state_dict(cfg, seed, eot, synth.WHISPER_DEC_EOT_BIAS[case])
         dec64, dec32 = hf_decoder(cfg, sd, torch.float64), hf_decoder(cfg, sd, torch.float32)
         emb = sd["decoder.embed_tokens.weight"].double()
@@ -96,25 +98,28 @@ def main():
         err = float((l32.double() - l64).abs().max())
         print(f"{case}: teacher-forced [{windows}, {T}], |logit| max {float(l64.abs().max()):.2f}, fp32 CPU error {err:.3e}")
         out = {"tokens": text.astype(np.int32), "hidden64": h64.numpy(), "err32": np.float64(err)}
-        if case in ("p", "q"):
+        if case in GREEDY:
+            sample_len = cfg["max_target_positions"] // 2                 # decode()'s default
             consts = synth.whisper_tail_consts(cfg, eot)
             prompt9 = synth.token_ids(f"whisper.dec.prompt.{case}", 9, eot, seed).tolist()
-            for has_prompt in (0, 1):
-                for wo in (0, 1):
-                    initial = [sp["<|startoftranscript|>"]] + ([sp["<|notimestamps|>"]] if wo else [])
-                    if has_prompt:
-                        initial = [sp["<|startofprev|>"]] + prompt9 + initial
-                    sot_index = initial.index(sp["<|startoftranscript|>"])
-                    sampled, sum_lp, nsp, worst, gerr = greedy(dec64, dec32, emb, xa[:1].double(), initial, len(initial), sot_index, consts, bool(wo))
-                    ended = "eot" if len(sampled) < SAMPLE_LEN else "sample_len"
-                    print(f"  greedy prompt={has_prompt} without_timestamps={wo}: {len(sampled)} tokens (ended by {ended}), smallest margin "
-                          f"{worst:.3e}, fp32 CPU error {gerr:.3e}, avg_logprob {sum_lp / (len(sampled) + 1):.4f}, no_speech {nsp:.3e}")
-                    print("   ", sampled)
-                    if worst < 100 * gerr:
-                        raise SystemExit(f"{case}: a greedy step's margin {worst:.3e} is below 100 x the fp32 error {gerr:.3e}: choose another seed")
-                    key = f"greedy_{has_prompt}{wo}"
-                    out[key + "_tokens"] = np.array(sampled, dtype=np.int32)
-                    out[key + "_stats"] = np.array([sum_lp / (len(sampled) + 1), nsp, gerr, worst], dtype=np.float64)
+            for has_prompt, wo in GREEDY[case]:
+                initial = [sp["<|startoftranscript|>"]] + ([sp["<|notimestamps|>"]] if wo else [])
+                if has_prompt:
+                    initial = [sp["<|startofprev|>"]] + prompt9 + initial
+                sot_index = initial.index(sp["<|startoftranscript|>"])
+                sampled, sum_lp, nsp, worst, gerr = greedy(dec64, dec32, emb, xa[:1].double(), initial, len(initial), sot_index, consts, bool(wo),
+                                                          sample_len)
+                ended = "eot" if len(sampled) < sample_len else "sample_len"
+                print(f"  greedy prompt={has_prompt} without_timestamps={wo}: {len(sampled)} tokens (ended by {ended}), smallest margin "
+                      f"{worst:.3e}, fp32 CPU error {gerr:.3e}, avg_logprob {sum_lp / (len(sampled) + 1):.4f}, no_speech {nsp:.3e}")
+                print("   ", sampled)
+                if worst < 100 * gerr:
+                    raise SystemExit(f"{case}: a greedy step's margin {worst:.3e} is below 100 x the fp32 error {gerr:.3e}: choose another seed")
+                if case == "s" and (ended != "eot" or len(sampled) < 4):
+                    raise SystemExit(f"{case}: the greedy sequence is to end by eot after a few tokens: adjust synth.WHISPER_DEC_EOT_BIAS")
+                key = f"greedy_{has_prompt}{wo}"
+                out[key + "_tokens"] = np.array(sampled, dtype=np.int32)
+                out[key + "_stats"] = np.array([sum_lp / (len(sampled) + 1), nsp, gerr, worst], dtype=np.float64)
             out["prompt9"] = np.array(prompt9, dtype=np.int32)
         path = os.path.join(HERE, f"whisper_dec_{case}.npz")
         np.savez_compressed(path, **out)

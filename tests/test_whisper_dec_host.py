@@ -1,5 +1,6 @@
 """Whisper text decoder, the host side: tokenizer, options, transcribe()'s seek / segment / fallback logic on scripted decode results, .srt
 writing, the numpy restatement of the tail's rules against transformers' processors, and the ABI of the new entry points."""
+import ctypes
 import io
 import os
 import re
@@ -286,6 +287,69 @@ def test_decoder_tables_and_synth_cases():
     full = {**{"encoder." + k: v for k, v in enc_sd.items()}, **synth.whisper_decoder_state_dict(synth.WHISPER_DEC_P, 81)}
     model = whisper.Whisper(synth.WHISPER_DEC_P, full)
     assert model.dims["n_vocab"] == 200 and model.dims["n_audio_ctx"] == 33 and not model.is_multilingual
+
+
+@pytest.mark.parametrize("case", synth.WHISPER_DEC_WIDTH_CASES)
+def test_width_fixtures_agree_with_synth(case):
+    cfg, eot, seed, windows = synth.WHISPER_DEC_CASES[case]
+    path = os.path.join(REPO, "tests", "golden", f"whisper_dec_{case}.npz")
+    assert os.path.getsize(path) < os.path.getsize(os.path.join(REPO, "tests", "golden", "whisper_enc_c.npz"))
+    z = np.load(path)
+    T = 6
+    assert z["tokens"].shape == (windows, T) and z["tokens"].dtype == np.int32
+    assert z["hidden64"].shape == (windows, T, cfg["d_model"]) and z["hidden64"].dtype == np.float64 and np.isfinite(z["hidden64"]).all()
+    assert 0 < float(z["err32"]) < 1e-3
+    sp = synth.whisper_special_tokens(eot)
+    assert (z["tokens"][:, 0] == sp["<|startoftranscript|>"]).all() and (z["tokens"][:, 1:] >= 0).all() and (z["tokens"][:, 1:] < eot).all()
+    text = synth.token_ids(f"whisper.dec.{case}", windows * T, eot, seed).reshape(windows, T)
+    assert np.array_equal(z["tokens"][:, 1:], text[:, 1:])
+    assert cfg["d_model"] == 64 * cfg["decoder_attention_heads"] and cfg["max_source_positions"] == 70 and cfg["decoder_layers"] == 1
+    assert T <= cfg["max_target_positions"]
+    if case != "s":
+        assert set(z.files) == {"tokens", "hidden64", "err32"}
+        return
+    # small.en's width with an LM head of at least 8192 columns, a multiple of 4; the special tokens and 188 timestamps fit behind eot
+    assert cfg["vocab_size"] >= 8192 and cfg["vocab_size"] % 4 == 0 and windows == 3
+    tok = synth.whisper_tokenizer(eot)
+    k = synth.whisper_tail_consts(cfg, eot)
+    assert eot < tok.sot < tok.no_timestamps < tok.timestamp_begin < cfg["vocab_size"] and k["max_initial_timestamp_index"] == 2
+    assert tok.timestamp_begin + k["max_initial_timestamp_index"] < cfg["vocab_size"] and all(0 <= t < cfg["vocab_size"] for t in k["suppress"])
+    greedy, (avg, nsp, err32, margin) = z["greedy_00_tokens"].tolist(), z["greedy_00_stats"]
+    assert 4 <= len(greedy) < cfg["max_target_positions"] // 2                  # ended by eot inside decode()'s default sample_len
+    assert margin > 100 * err32 > 0 and avg < 0 and 0 <= nsp <= 1
+    c = R.Consts(k["n_vocab"], k["eot"], k["no_speech"], k["no_timestamps"], k["timestamp_begin"], k["max_initial_timestamp_index"], k["blank"],
+                 k["suppress"])
+    assert R.grammar_ok(c, greedy) and not set(greedy) & (set(k["suppress"]) | {eot})
+    assert tok.decode(list(range(eot))) != ""      # every text id has a text: decode() can name any pick
+    assert tok.encode(tok.decode(greedy)) != [] and len(tok.encode(" the")) == 1
+    assert z["prompt9"].tolist() == synth.token_ids("whisper.dec.prompt.s", 9, eot, seed).tolist()
+
+
+@pytest.mark.parametrize("rows", R.STEP_ROW_COUNTS)
+def test_step_dispatch_families_at_small_en_width(rows):
+    """What tests/test_gpu_whisper_widths.py asserts on the device, at 256 CUs and the default switches: a chooser change that would
+    leave that test without the kernels it is there for fails here first."""
+    cfg = synth.WHISPER_DEC_S
+    names = R.step_dispatch(rows, cfg["d_model"], cfg["decoder_ffn_dim"], cfg["vocab_size"], cus=256, select_kernel=0, ring_mode=0, rows_ln_mode=2)
+    R.check_small_en_step_families(rows, names)
+
+
+def test_step_dispatch_covers_the_ln_and_lm_head_instantiations():
+    """Over the row counts of the GPU test the LM head reaches five of the nine m16ln_stream instantiations below 33 rows and rows<mt>,
+    tile64 above; the checkpoint widths reach m16ln<2> and m16ln<4> and are refused at 384 and 1280 (the two-call path)."""
+    cfg = synth.WHISPER_DEC_S
+    kw = dict(cus=256, select_kernel=0, ring_mode=0, rows_ln_mode=2)
+    heads = {r: R.step_dispatch(r, 768, 3072, cfg["vocab_size"], **kw)["head"][1] for r in R.STEP_ROW_COUNTS}
+    assert len({n for r, n in heads.items() if r <= 32}) == 5 and all(n.startswith("m16ln_stream<") for r, n in heads.items() if r <= 32)
+    assert {n for r, n in heads.items() if r > 32} == {"rows<mt=1>", "rows<mt=2>", "tile64"}
+    for width, want in ((384, None), (512, "m16ln<2,1,2>"), (1024, "m16ln<4,1,2>"), (1280, None)):
+        for rows in (3, 40):
+            names = R.step_dispatch(rows, width, 4 * width, 200, **kw)
+            assert all(names[c + "_fused"] == (want is not None) and names[c][0] == 0 for c in ("qkv", "cross_q", "fc1", "head")), (width, rows, names)
+            assert want is None or all(names[c][1] == want for c in ("qkv", "cross_q", "fc1", "head")), (width, rows, names)
+            buf = ctypes.create_string_buffer(64)
+            q = _lib.GemmF32Query.make("ln", rows, 3 * width, width, **kw)
+            assert (_lib.load().hirest_gemm_f32_dispatch_name(ctypes.byref(q), buf, 64) == 0) == (want is not None), (width, rows)
 
 
 def test_tokenizer_from_dir_and_load_model_from_pt(tmp_path):
