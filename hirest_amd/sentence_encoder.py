@@ -50,6 +50,31 @@ def _load_weights(model_dir: str) -> Dict[str, torch.Tensor]:
     raise FileNotFoundError(f"no model.safetensors / pytorch_model.bin under {model_dir}")
 
 
+def _padded_head_width(heads: int, dh: int) -> int:
+    """head width as the attention kernels see it (zero lanes after dh): the next multiple of 4, and on from there until the output
+    projection's reduction length ``heads * ah`` suits the GEMM (a multiple of 16)"""
+    ah = (dh + 3) // 4 * 4
+    while (heads * ah) % 16:
+        ah += 4
+    return ah
+
+
+def _fused_head_operands(qkv, out_w: torch.Tensor, H: int, dh: int, AH: int):
+    """``qkv``: the (weight ``[H dh, D]``, bias ``[H dh]``) of query, key and value; ``out_w [D, H dh]`` -> the fused ``[3 H AH, D]``
+    weight and ``[3 H AH]`` bias and the ``[D, H AH]`` output projection, every head zero-padded from dh to AH lanes (this encoder's
+    and Whisper's audio encoder's, which passes a zero key bias)"""
+    D, dev = out_w.shape[0], out_w.device
+
+    def pad_rows(w, b):      # [H*dh, D] -> [H*AH, D]: head h's rows at AH h .. AH h + dh, zeros after (AH = dh: a copy)
+        wp = torch.zeros((H, AH, D), device=dev); wp[:, :dh] = w.view(H, dh, D)
+        bp = torch.zeros((H, AH), device=dev); bp[:, :dh] = b.view(H, dh)
+        return wp.view(H * AH, D), bp.view(H * AH)
+    ws, bs = zip(*(pad_rows(w, b) for w, b in qkv))
+    wo = torch.zeros((D, H, AH), device=dev)
+    wo[:, :, :dh] = out_w.view(D, H, dh)
+    return torch.cat(ws, 0).contiguous(), torch.cat(bs, 0).contiguous(), wo.view(D, H * AH).contiguous()
+
+
 class PackedBertEncoder(nn.Module):
     """The post-LN BERT / RoBERTa encoder stack over sentences packed row after row: the weights under their checkpoint names, the
     fused per-layer operands, and the layer loop that returns the [tokens, hidden] states.  ``SentenceTransformer`` pools them into
@@ -76,9 +101,7 @@ class PackedBertEncoder(nn.Module):
         self.dh = self.hidden // self.heads
         if self.dh > _AH_MAX or self.hidden % self.heads or self.hidden % 4:
             raise NotImplementedError(f"head width {self.dh} > {_AH_MAX}")
-        self.ah = (self.dh + 3) // 4 * 4               # head width as the kernels see it (MiniLM: 32, no padding) ...
-        while (self.heads * self.ah) % 16:             # ... such that the output projection's reduction length suits the GEMM
-            self.ah += 4
+        self.ah = _padded_head_width(self.heads, self.dh)         # (MiniLM: 32, no padding)
         if state_dict is None:
             raise ValueError("state_dict required with an explicit config")
         sd = {}
@@ -118,27 +141,15 @@ class PackedBertEncoder(nn.Module):
         if dev.type != "cuda":
             raise RuntimeError(f"{self._NAME} runs on MI355X only (no CPU fallback); move the model to a GPU")
         f = lambda n: self._p(n).detach().float().contiguous()
-        H, dh, D = self.heads, self.dh, self.hidden
         c = {"word": f("embeddings.word_embeddings.weight"),
              # token type is always 0 (single sentences): fold its row into the position table once
              "pos": (f("embeddings.position_embeddings.weight") + f("embeddings.token_type_embeddings.weight")[0]).contiguous(),
              "eln_w": f("embeddings.LayerNorm.weight"), "eln_b": f("embeddings.LayerNorm.bias")}
-
-        AH = self.ah
-
-        def pad_rows(w, b):      # [H*dh, D] -> [H*AH, D]: head h's rows at AH h .. AH h + dh, zeros after (AH = dh: a copy)
-            wp = torch.zeros((H, AH, D), device=dev); wp[:, :dh] = w.view(H, dh, D)
-            bp = torch.zeros((H, AH), device=dev); bp[:, :dh] = b.view(H, dh)
-            return wp.view(H * AH, D), bp.view(H * AH)
         for i in range(self.layers):
             p = f"encoder.layer.{i}."
-            ws, bs = zip(*(pad_rows(f(p + f"attention.self.{n}.weight"), f(p + f"attention.self.{n}.bias"))
-                           for n in ("query", "key", "value")))
-            c[f"qkv_w.{i}"] = torch.cat(ws, 0).contiguous()
-            c[f"qkv_b.{i}"] = torch.cat(bs, 0).contiguous()
-            wo = torch.zeros((D, H, AH), device=dev)
-            wo[:, :, :dh] = f(p + "attention.output.dense.weight").view(D, H, dh)
-            c[f"o_w.{i}"] = wo.view(D, H * AH).contiguous()
+            c[f"qkv_w.{i}"], c[f"qkv_b.{i}"], c[f"o_w.{i}"] = _fused_head_operands(
+                [(f(p + f"attention.self.{n}.weight"), f(p + f"attention.self.{n}.bias")) for n in ("query", "key", "value")],
+                f(p + "attention.output.dense.weight"), self.heads, self.dh, self.ah)
             for n in ("attention.output.dense.bias", "attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias",
                       "intermediate.dense.weight", "intermediate.dense.bias", "output.dense.weight", "output.dense.bias",
                       "output.LayerNorm.weight", "output.LayerNorm.bias"):

@@ -20,6 +20,12 @@ row m of the A operand starts ``stride * C`` floats after row m - 1 and is ``3 C
 the positional embedding in its epilogue, after the GELU.  The blocks run on the exact-fp32 kernels of the other encoders
 (``hirest_gemm_f32`` / ``hirest_gemm_f32_ln`` / ``hirest_attention_f32`` / ``hirest_layernorm``).  There is no CPU path: ``forward`` and
 ``log_mel_spectrogram`` raise off-GPU.  A local ``.pt`` or model directory is required: nothing is downloaded.
+
+What the two halves share is written once: the size and key tables of both checkpoint schemas (``_dims``, ``_canonical``, by side), the
+checkpoint reader, the frozen-weights base of ``AudioEncoder`` and ``TextDecoder``, and ``_linear`` / ``_ln_linear``.  Decoding has ONE
+token loop, ``_decode_rows`` over the per-row entry points: ``decode()`` runs it once per window, ``decode_many()`` once
+for the windows of several files.  ``TextDecoder.forward(kv_cache=)`` / ``prefill`` / ``step`` over the lock-step ``KVCache`` stay as
+Whisper's ``decoder(tokens, xa, kv_cache)`` surface; the lock-step loop over them is the tests' yardstick (tests/_whisper_lockstep.py).
 """
 from __future__ import annotations
 
@@ -40,7 +46,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from .bytebpe import ByteBPETokenizer
-from .sentence_encoder import _AH_MAX, _load_weights
+from .sentence_encoder import _AH_MAX, _fused_head_operands, _load_weights, _padded_head_width
 
 SAMPLE_RATE = 16000
 N_FFT = 400
@@ -181,87 +187,92 @@ def conv_as_gemm_weight(w: torch.Tensor) -> torch.Tensor:
     return w.permute(0, 2, 1).reshape(w.shape[0], -1).contiguous()
 
 
-def _dims(d) -> Dict[str, int]:
-    """OpenAI ``ModelDimensions`` (object or dict: n_mels, n_audio_ctx, n_audio_state, n_audio_head, n_audio_layer) or a Hugging Face
-    Whisper ``config.json`` dict -> the encoder's sizes."""
+# Per side ("audio": the encoder, "text": the decoder): the name of the side's first size, OpenAI's ``ModelDimensions`` fields for
+# (first size, ctx, width, heads, layers), and the Hugging Face ``config.json`` fields for the same five and the MLP width.
+_DIM_FIELDS = {"audio": ("n_mels", ("n_mels", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_layer"),
+                         ("num_mel_bins", "max_source_positions", "d_model", "encoder_attention_heads", "encoder_layers", "encoder_ffn_dim")),
+               "text": ("vocab", ("n_vocab", "n_text_ctx", "n_text_state", "n_text_head", "n_text_layer"),
+                        ("vocab_size", "max_target_positions", "d_model", "decoder_attention_heads", "decoder_layers", "decoder_ffn_dim"))}
+
+
+def _dims(d, side: str = "audio") -> Dict[str, int]:
+    """OpenAI ``ModelDimensions`` (object or dict) or a Hugging Face Whisper ``config.json`` dict -> that side's sizes: ``n_mels``
+    (audio) or ``vocab`` (text), ``ctx``, ``width``, ``heads``, ``layers``, ``ffn``."""
+    first, openai, hf = _DIM_FIELDS[side]
     get = (lambda k, default=None: d.get(k, default)) if isinstance(d, dict) else (lambda k, default=None: getattr(d, k, default))
-    if get("n_audio_state") is not None:
-        width = int(get("n_audio_state"))
-        return {"n_mels": int(get("n_mels")), "ctx": int(get("n_audio_ctx")), "width": width, "heads": int(get("n_audio_head")),
-                "layers": int(get("n_audio_layer")), "ffn": 4 * width}
-    if get("d_model") is not None:
+    if get(openai[2]) is not None:
+        size, ctx, width, heads, layers = (int(get(k)) for k in openai)
+        ffn = 4 * width
+    elif get("d_model") is not None:
         if get("activation_function", "gelu") != "gelu":
             raise NotImplementedError(f"activation {get('activation_function')!r}: Whisper's erf GELU is what is built")
-        width = int(get("d_model"))
-        return {"n_mels": int(get("num_mel_bins")), "ctx": int(get("max_source_positions")), "width": width,
-                "heads": int(get("encoder_attention_heads")), "layers": int(get("encoder_layers")),
-                "ffn": int(get("encoder_ffn_dim", 4 * width))}
-    raise ValueError("neither Whisper's ModelDimensions (n_audio_state ...) nor a Hugging Face Whisper config (d_model ...)")
+        size, ctx, width, heads, layers = (int(get(k)) for k in hf[:5])
+        ffn = int(get(hf[5], 4 * width))
+    else:
+        raise ValueError(f"neither Whisper's ModelDimensions ({openai[2]} ...) nor a Hugging Face Whisper config (d_model ...)")
+    return {first: size, "ctx": ctx, "width": width, "heads": heads, "layers": layers, "ffn": ffn}
 
 
+# Hugging Face WhisperEncoder / WhisperDecoder names -> OpenAI's, applied in this order; then the side's final LayerNorm
 _HF_TO_OPENAI = (("embed_positions.weight", "positional_embedding"), ("layers.", "blocks."), ("self_attn.q_proj", "attn.query"),
                  ("self_attn.k_proj", "attn.key"), ("self_attn.v_proj", "attn.value"), ("self_attn.out_proj", "attn.out"),
                  ("self_attn_layer_norm", "attn_ln"), ("final_layer_norm", "mlp_ln"), ("fc1", "mlp.0"), ("fc2", "mlp.2"))
+_HF_TO_OPENAI_DEC = (("embed_tokens.weight", "token_embedding.weight"), ("embed_positions.weight", "positional_embedding"),
+                     ("layers.", "blocks."), ("encoder_attn_layer_norm", "cross_attn_ln"), ("self_attn_layer_norm", "attn_ln"),
+                     ("final_layer_norm", "mlp_ln"), ("encoder_attn.q_proj", "cross_attn.query"), ("encoder_attn.k_proj", "cross_attn.key"),
+                     ("encoder_attn.v_proj", "cross_attn.value"), ("encoder_attn.out_proj", "cross_attn.out"),
+                     ("self_attn.q_proj", "attn.query"), ("self_attn.k_proj", "attn.key"), ("self_attn.v_proj", "attn.value"),
+                     ("self_attn.out_proj", "attn.out"), ("fc1", "mlp.0"), ("fc2", "mlp.2"))
+_KEY_TABLES = {"audio": ("encoder.", _HF_TO_OPENAI, "ln_post."), "text": ("decoder.", _HF_TO_OPENAI_DEC, "ln.")}
 
 
-def _canonical(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """Either schema's encoder tensors under OpenAI's names without the ``encoder.`` prefix; decoder tensors are dropped."""
+def _canonical(state_dict: Dict[str, torch.Tensor], side: str = "audio") -> Dict[str, torch.Tensor]:
+    """Either schema's tensors of one side under OpenAI's names without the ``encoder.`` / ``decoder.`` prefix.  Audio: decoder tensors
+    are dropped and a key without a prefix counts as the encoder's (a bare WhisperEncoder state dict); text: everything that is not
+    under ``decoder.`` is dropped."""
+    prefix, table, final_ln = _KEY_TABLES[side]
     out = {}
     for k, v in state_dict.items():
         if k.startswith("model."):
             k = k[len("model."):]
-        if k.startswith("decoder.") or k.startswith("proj_out."):
+        if k.startswith(prefix):
+            k = k[len(prefix):]
+        elif side == "text" or k.startswith("decoder.") or k.startswith("proj_out."):
             continue
-        if k.startswith("encoder."):
-            k = k[len("encoder."):]
-        if k.startswith("layers.") or k.startswith("embed_positions.") or k.startswith("layer_norm."):
-            for a, b in _HF_TO_OPENAI:
+        if k.startswith("layers.") or k.startswith("embed_") or k.startswith("layer_norm."):
+            for a, b in table:
                 k = k.replace(a, b)
             if k.startswith("layer_norm."):
-                k = "ln_post." + k[len("layer_norm."):]
+                k = final_ln + k[len("layer_norm."):]
         out[k] = v
     return out
 
 
-class AudioEncoder(nn.Module):
-    """``whisper.model.AudioEncoder``: conv1 (k 3) + GELU, conv2 (k 3, stride 2) + GELU, + positional embedding, pre-LN blocks, ln_post.
+def _read_checkpoint(path: str, unresolved: str):
+    """``path`` -> (``dims`` or config, state dict, whether it is a model directory): an OpenAI ``.pt`` (a dict with ``dims`` and
+    ``model_state_dict``) or a Hugging Face model directory (``config.json`` + ``model.safetensors`` / ``pytorch_model.bin``), picked by
+    what ``path`` is.  Anything else, a model name included, raises FileNotFoundError ending in ``unresolved``: nothing is downloaded."""
+    if os.path.isdir(path):
+        with open(os.path.join(path, "config.json")) as f:
+            return json.load(f), _load_weights(path), True
+    if os.path.isfile(path):
+        ckpt = torch.load(path, map_location="cpu")
+        if not (isinstance(ckpt, dict) and "dims" in ckpt and "model_state_dict" in ckpt):
+            raise ValueError(f"{path}: not a Whisper checkpoint (a dict with 'dims' and 'model_state_dict')")
+        return ckpt["dims"], ckpt["model_state_dict"], False
+    raise FileNotFoundError(f"{path!r} is neither a local .pt checkpoint nor a model directory{unresolved}")
 
-    ``dims_or_config``: OpenAI's ``ModelDimensions`` / ``dims`` dict or a Hugging Face ``config.json`` dict; ``state_dict`` in either
-    schema (``encoder.blocks.i.attn.query ...`` or ``[model.]encoder.layers.i.self_attn.q_proj ...``; decoder tensors are ignored).
-    The weights are frozen parameters under OpenAI's names; the fused operands are built on first use and dropped on any move / cast."""
 
-    def __init__(self, dims_or_config, state_dict: Dict[str, torch.Tensor]):
-        super().__init__()
-        self.dims = _dims(dims_or_config)
-        d = self.dims
-        self.n_mels, self.ctx, self.width, self.heads, self.layers, self.ffn = (d[k] for k in ("n_mels", "ctx", "width", "heads", "layers", "ffn"))
-        if self.width % self.heads or self.width % 16 or self.ffn % 16 or self.n_mels % 16:
-            raise NotImplementedError(f"width {self.width} / heads {self.heads} / ffn {self.ffn} / n_mels {self.n_mels}: multiples of 16 expected")
-        self.dh = self.width // self.heads
-        if self.dh > _AH_MAX:
-            raise NotImplementedError(f"head width {self.dh} > {_AH_MAX}")
-        self.ah = (self.dh + 3) // 4 * 4               # head width as the kernels see it (zero lanes after dh) ...
-        while (self.heads * self.ah) % 16:             # ... such that the output projection's reduction length suits the GEMM
-            self.ah += 4
-        self.eps = 1e-5
-        sd = _canonical(state_dict)
-        want = {"conv1.weight": (self.width, self.n_mels, 3), "conv1.bias": (self.width,), "conv2.weight": (self.width, self.width, 3),
-                "conv2.bias": (self.width,), "positional_embedding": (self.ctx, self.width), "ln_post.weight": (self.width,),
-                "ln_post.bias": (self.width,)}
-        for i in range(self.layers):
-            p = f"blocks.{i}."
-            for n in ("query", "key", "value", "out"):
-                want[p + f"attn.{n}.weight"] = (self.width, self.width)
-                if n != "key":
-                    want[p + f"attn.{n}.bias"] = (self.width,)
-            want.update({p + "attn_ln.weight": (self.width,), p + "attn_ln.bias": (self.width,), p + "mlp_ln.weight": (self.width,),
-                         p + "mlp_ln.bias": (self.width,), p + "mlp.0.weight": (self.ffn, self.width), p + "mlp.0.bias": (self.ffn,),
-                         p + "mlp.2.weight": (self.width, self.ffn), p + "mlp.2.bias": (self.width,)})
+class _FrozenWeights(nn.Module):
+    """What ``AudioEncoder`` and ``TextDecoder`` share: the checkpoint's tensors as frozen fp32 parameters under OpenAI's names, and the
+    cache of the fused operands (``prepared_weights()`` of the subclass), built on first use on a GPU and dropped on any move / cast."""
+
+    def _freeze(self, sd: Dict[str, torch.Tensor], want: Dict[str, tuple]) -> None:
         for k, shape in want.items():
             if k not in sd:
-                raise KeyError(f"AudioEncoder: {k} missing from the state dict")
+                raise KeyError(f"{type(self).__name__}: {k} missing from the state dict")
             if tuple(sd[k].shape) != shape:
-                raise ValueError(f"AudioEncoder: {k} has shape {tuple(sd[k].shape)}, expected {shape}")
+                raise ValueError(f"{type(self).__name__}: {k} has shape {tuple(sd[k].shape)}, expected {shape}")
             # parameter names cannot hold dots: keep the checkpoint's name with '/'
             self.register_parameter(k.replace(".", "/"), nn.Parameter(sd[k].detach().float().clone(), requires_grad=False))
         self._cache = None
@@ -276,71 +287,105 @@ class AudioEncoder(nn.Module):
 
     @property
     def device(self) -> torch.device:
-        return self._p("conv1.weight").device
+        return next(iter(self._parameters.values())).device
+
+    def _require_gpu(self) -> None:
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{_NAME}.{type(self).__name__} runs on MI355X only (no CPU fallback); move the model to a GPU")
+
+    def _w(self):
+        if self._cache is None:
+            self._require_gpu()
+            self._cache = self.prepared_weights()
+        return self._cache
+
+
+_LN_EPS = 1e-5                 # of every LayerNorm of both halves
+
+
+def _gemm(a_ptr, lda, w, bias, out_ptr, ldo, M, device, act=0, resid=None, periodic=None, period=0):
+    """out[M, N] = act(A W^T + bias) (+ resid) (+ periodic[m % period]) on raw operand addresses: A's rows may overlap"""
+    lib = _lib.load()
+    N, K = w.shape
+    ws, wsb = ops.stream_workspace(device, lib.hirest_gemm_f32_workspace_bytes(M, N, K))
+    _lib.check(lib.hirest_gemm_f32_ws(a_ptr, lda, w.data_ptr(), K, bias.data_ptr(), resid.data_ptr() if resid is not None else None, N,
+                                      periodic.data_ptr() if periodic is not None else None, period, out_ptr, ldo, M, N, K, act,
+                                      ws, wsb, ops.stream_ptr()), "hirest_gemm_f32_ws")
+
+
+def _linear(x, w, bias, act=0, resid=None):
+    out = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
+    _gemm(x.data_ptr(), x.shape[1], w, bias, out.data_ptr(), w.shape[0], x.shape[0], x.device, act=act, resid=resid)
+    return out
+
+
+def _ln_linear(x, gamma, beta, w, bias, act=0):
+    """act(LayerNorm(x) W^T + bias): inside one GEMM where hirest_gemm_f32_ln has a form for the shape (up to 256 rows, K a multiple of
+    256 up to 1024; from 8192 columns on — an LM head — only small.en's K = 768 up to 32 rows), else hirest_layernorm + hirest_gemm_f32:
+    the same bits either way.  The condition is that of ``ln_gemm`` in csrc/whisper_dec.hip, its C twin behind the decode step: the two
+    have to stay the same.  No encoder product reaches 8192 columns (its N is 3 width, width or ffn)."""
+    M, K = x.shape
+    N = w.shape[0]
+    if M <= 256 and K % 256 == 0 and K <= 1024 and (N < 8192 or (K == 768 and M <= 32)):
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.load().hirest_gemm_f32_ln(x.data_ptr(), K, None, None, None, gamma.data_ptr(), beta.data_ptr(), _LN_EPS, None, 0,
+                                                  w.data_ptr(), K, bias.data_ptr(), None, 0, out.data_ptr(), N, M, N, K, act,
+                                                  ops.stream_ptr()), "hirest_gemm_f32_ln")
+        return out
+    return _linear(ops.layernorm(x, gamma, beta, _LN_EPS, torch.empty_like(x)), w, bias, act=act)
+
+
+class AudioEncoder(_FrozenWeights):
+    """``whisper.model.AudioEncoder``: conv1 (k 3) + GELU, conv2 (k 3, stride 2) + GELU, + positional embedding, pre-LN blocks, ln_post.
+
+    ``dims_or_config``: OpenAI's ``ModelDimensions`` / ``dims`` dict or a Hugging Face ``config.json`` dict; ``state_dict`` in either
+    schema (``encoder.blocks.i.attn.query ...`` or ``[model.]encoder.layers.i.self_attn.q_proj ...``; decoder tensors are ignored).
+    The weights are frozen parameters under OpenAI's names; the fused operands are built on first use and dropped on any move / cast."""
+
+    def __init__(self, dims_or_config, state_dict: Dict[str, torch.Tensor]):
+        super().__init__()
+        self.dims = _dims(dims_or_config, "audio")
+        d = self.dims
+        self.n_mels, self.ctx, self.width, self.heads, self.layers, self.ffn = (d[k] for k in ("n_mels", "ctx", "width", "heads", "layers", "ffn"))
+        if self.width % self.heads or self.width % 16 or self.ffn % 16 or self.n_mels % 16:
+            raise NotImplementedError(f"width {self.width} / heads {self.heads} / ffn {self.ffn} / n_mels {self.n_mels}: multiples of 16 expected")
+        self.dh = self.width // self.heads
+        if self.dh > _AH_MAX:
+            raise NotImplementedError(f"head width {self.dh} > {_AH_MAX}")
+        self.ah = _padded_head_width(self.heads, self.dh)
+        want = {"conv1.weight": (self.width, self.n_mels, 3), "conv1.bias": (self.width,), "conv2.weight": (self.width, self.width, 3),
+                "conv2.bias": (self.width,), "positional_embedding": (self.ctx, self.width), "ln_post.weight": (self.width,),
+                "ln_post.bias": (self.width,)}
+        for i in range(self.layers):
+            p = f"blocks.{i}."
+            for n in ("query", "key", "value", "out"):
+                want[p + f"attn.{n}.weight"] = (self.width, self.width)
+                if n != "key":
+                    want[p + f"attn.{n}.bias"] = (self.width,)
+            want.update({p + "attn_ln.weight": (self.width,), p + "attn_ln.bias": (self.width,), p + "mlp_ln.weight": (self.width,),
+                         p + "mlp_ln.bias": (self.width,), p + "mlp.0.weight": (self.ffn, self.width), p + "mlp.0.bias": (self.ffn,),
+                         p + "mlp.2.weight": (self.width, self.ffn), p + "mlp.2.bias": (self.width,)})
+        self._freeze(_canonical(state_dict, "audio"), want)
 
     def prepared_weights(self) -> Dict[str, torch.Tensor]:
         """The operands the kernels read, on the parameters' device: reordered convolution weights, per-block fused QKV (zero key bias,
         heads zero-padded to the attention kernel's width) and output projections."""
         f = lambda n: self._p(n).detach().float().contiguous()
-        H, dh, AH, D = self.heads, self.dh, self.ah, self.width
-        dev = self.device
         c = {"conv1_w": conv_as_gemm_weight(f("conv1.weight")), "conv1_b": f("conv1.bias"),
              "conv2_w": conv_as_gemm_weight(f("conv2.weight")), "conv2_b": f("conv2.bias"),
              "pos": f("positional_embedding"), "ln_post_w": f("ln_post.weight"), "ln_post_b": f("ln_post.bias")}
-
-        def pad_rows(w, b):      # [H*dh, D] -> [H*AH, D]: head h's rows at AH h .. AH h + dh, zeros after (AH = dh: a copy)
-            wp = torch.zeros((H, AH, D), device=dev); wp[:, :dh] = w.view(H, dh, D)
-            bp = torch.zeros((H, AH), device=dev); bp[:, :dh] = b.view(H, dh)
-            return wp.view(H * AH, D), bp.view(H * AH)
+        no_bias = torch.zeros(self.width, device=self.device)
         for i in range(self.layers):
             p = f"blocks.{i}."
-            ws, bs = zip(*(pad_rows(f(p + f"attn.{n}.weight"), f(p + f"attn.{n}.bias") if n != "key" else torch.zeros(D, device=dev))
-                           for n in ("query", "key", "value")))
-            c[f"qkv_w.{i}"] = torch.cat(ws, 0).contiguous()
-            c[f"qkv_b.{i}"] = torch.cat(bs, 0).contiguous()
-            wo = torch.zeros((D, H, AH), device=dev)
-            wo[:, :, :dh] = f(p + "attn.out.weight").view(D, H, dh)
-            c[f"o_w.{i}"] = wo.view(D, H * AH).contiguous()
+            c[f"qkv_w.{i}"], c[f"qkv_b.{i}"], c[f"o_w.{i}"] = _fused_head_operands(
+                [(f(p + f"attn.{n}.weight"), f(p + f"attn.{n}.bias") if n != "key" else no_bias) for n in ("query", "key", "value")],
+                f(p + "attn.out.weight"), self.heads, self.dh, self.ah)
             for n in ("attn.out.bias", "attn_ln.weight", "attn_ln.bias", "mlp_ln.weight", "mlp_ln.bias", "mlp.0.weight", "mlp.0.bias",
                       "mlp.2.weight", "mlp.2.bias"):
                 c[p + n] = f(p + n)
         return c
 
-    def _w(self):
-        if self._cache is None:
-            if self.device.type != "cuda":
-                raise RuntimeError(f"{_NAME}.AudioEncoder runs on MI355X only (no CPU fallback); move the model to a GPU")
-            self._cache = self.prepared_weights()
-        return self._cache
-
     # ------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _gemm(a_ptr, lda, w, bias, out_ptr, ldo, M, device, act=0, resid=None, periodic=None, period=0):
-        """out[M, N] = act(A W^T + bias) (+ resid) (+ periodic[m % period]) on raw operand addresses: A's rows may overlap"""
-        lib = _lib.load()
-        N, K = w.shape
-        ws, wsb = ops.stream_workspace(device, lib.hirest_gemm_f32_workspace_bytes(M, N, K))
-        _lib.check(lib.hirest_gemm_f32_ws(a_ptr, lda, w.data_ptr(), K, bias.data_ptr(), resid.data_ptr() if resid is not None else None, N,
-                                          periodic.data_ptr() if periodic is not None else None, period, out_ptr, ldo, M, N, K, act,
-                                          ws, wsb, ops.stream_ptr()), "hirest_gemm_f32_ws")
-
-    def _linear(self, x, w, bias, act=0, resid=None):
-        out = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
-        self._gemm(x.data_ptr(), x.shape[1], w, bias, out.data_ptr(), w.shape[0], x.shape[0], x.device, act=act, resid=resid)
-        return out
-
-    def _ln_linear(self, x, gamma, beta, w, bias, act=0):
-        """act(LayerNorm(x) W^T + bias): inside one GEMM where hirest_gemm_f32_ln has a form for the shape (up to 256 rows, K a multiple
-        of 256 up to 1024), else hirest_layernorm + hirest_gemm_f32 — the same bits either way."""
-        M, K = x.shape
-        N = w.shape[0]
-        if M <= 256 and K % 256 == 0 and K <= 1024 and N < 8192:
-            out = torch.empty((M, N), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.load().hirest_gemm_f32_ln(x.data_ptr(), K, None, None, None, gamma.data_ptr(), beta.data_ptr(), self.eps, None, 0,
-                                                      w.data_ptr(), K, bias.data_ptr(), None, 0, out.data_ptr(), N, M, N, K, act,
-                                                      ops.stream_ptr()), "hirest_gemm_f32_ln")
-            return out
-        return self._linear(ops.layernorm(x, gamma, beta, self.eps, torch.empty_like(x)), w, bias, act=act)
 
     def _stem(self, mel: torch.Tensor) -> torch.Tensor:
         """[B, n_mels, 2 ctx] -> [B * ctx, width]: gelu(conv2(gelu(conv1(mel)))) + positional embedding, per clip, as two products over
@@ -356,9 +401,9 @@ class AudioEncoder(nn.Module):
         x = torch.empty((B * ctx, D), dtype=torch.float32, device=dev)
         for b in range(B):
             # conv1 (stride 1): output row t reads padded rows t, t + 1, t + 2 = 3 C consecutive floats from row t on
-            self._gemm(rows[b].data_ptr(), C, c["conv1_w"], c["conv1_b"], h[b, 1].data_ptr(), D, T, dev, act=1)
+            _gemm(rows[b].data_ptr(), C, c["conv1_w"], c["conv1_b"], h[b, 1].data_ptr(), D, T, dev, act=1)
             # conv2 (stride 2): output row t reads padded rows 2 t, 2 t + 1, 2 t + 2; GELU, then + positional embedding (row t of the clip)
-            self._gemm(h[b].data_ptr(), 2 * D, c["conv2_w"], c["conv2_b"], x[b * ctx].data_ptr(), D, ctx, dev, act=1,
+            _gemm(h[b].data_ptr(), 2 * D, c["conv2_w"], c["conv2_b"], x[b * ctx].data_ptr(), D, ctx, dev, act=1,
                        periodic=c["pos"], period=ctx)
         return x
 
@@ -366,8 +411,7 @@ class AudioEncoder(nn.Module):
     def forward(self, mel: torch.Tensor, return_stem: bool = False) -> torch.Tensor:
         """``mel`` ``[B, n_mels, 2 ctx]`` or ``[n_mels, 2 ctx]`` -> ``[B, ctx, width]`` fp32 encoder states (``return_stem``: the input of
         the first block instead).  Any other frame count raises ValueError, where Whisper asserts."""
-        if self.device.type != "cuda":
-            raise RuntimeError(f"{_NAME}.AudioEncoder runs on MI355X only (no CPU fallback); move the model to a GPU")
+        self._require_gpu()
         if mel.ndim == 2:
             mel = mel[None]
         if mel.ndim != 3 or mel.shape[1] != self.n_mels or mel.shape[2] != 2 * self.ctx:
@@ -382,14 +426,14 @@ class AudioEncoder(nn.Module):
                 return x.view(B, ctx, self.width)
             for i in range(self.layers):
                 p = f"blocks.{i}."
-                qkv = self._ln_linear(x, c[p + "attn_ln.weight"], c[p + "attn_ln.bias"], c[f"qkv_w.{i}"], c[f"qkv_b.{i}"])
+                qkv = _ln_linear(x, c[p + "attn_ln.weight"], c[p + "attn_ln.bias"], c[f"qkv_w.{i}"], c[f"qkv_b.{i}"])
                 att = torch.empty((B * ctx, H * AH), dtype=torch.float32, device=dev)
                 _lib.check(lib.hirest_attention_f32(qkv.data_ptr(), att.data_ptr(), B, ctx, H, AH, self.dh ** -0.5, 0.0, ops.stream_ptr()),
                            "hirest_attention_f32")
-                x = self._linear(att, c[f"o_w.{i}"], c[p + "attn.out.bias"], resid=x)
-                hid = self._ln_linear(x, c[p + "mlp_ln.weight"], c[p + "mlp_ln.bias"], c[p + "mlp.0.weight"], c[p + "mlp.0.bias"], act=1)
-                x = self._linear(hid, c[p + "mlp.2.weight"], c[p + "mlp.2.bias"], resid=x)
-            out = ops.layernorm(x, c["ln_post_w"], c["ln_post_b"], self.eps, torch.empty_like(x))
+                x = _linear(att, c[f"o_w.{i}"], c[p + "attn.out.bias"], resid=x)
+                hid = _ln_linear(x, c[p + "mlp_ln.weight"], c[p + "mlp_ln.bias"], c[p + "mlp.0.weight"], c[p + "mlp.0.bias"], act=1)
+                x = _linear(hid, c[p + "mlp.2.weight"], c[p + "mlp.2.bias"], resid=x)
+            out = ops.layernorm(x, c["ln_post_w"], c["ln_post_b"], _LN_EPS, torch.empty_like(x))
         return out.view(B, ctx, self.width)
 
     embed_audio = forward
@@ -399,18 +443,8 @@ def load_encoder(path: str, device: Optional[Union[str, torch.device]] = None) -
     """An OpenAI ``.pt`` checkpoint (a dict with ``dims`` and ``model_state_dict``) or a Hugging Face model directory (``config.json`` +
     ``model.safetensors`` / ``pytorch_model.bin``), picked by what ``path`` is.  A model name (``'small.en'``, ``'openai/whisper-small.en'``)
     raises FileNotFoundError: nothing is downloaded."""
-    if os.path.isdir(path):
-        with open(os.path.join(path, "config.json")) as f:
-            config = json.load(f)
-        enc = AudioEncoder(config, _load_weights(path))
-    elif os.path.isfile(path):
-        ckpt = torch.load(path, map_location="cpu")
-        if not (isinstance(ckpt, dict) and "dims" in ckpt and "model_state_dict" in ckpt):
-            raise ValueError(f"{path}: not a Whisper checkpoint (a dict with 'dims' and 'model_state_dict')")
-        enc = AudioEncoder(ckpt["dims"], ckpt["model_state_dict"])
-    else:
-        raise FileNotFoundError(f"{path!r} is neither a local .pt checkpoint nor a model directory (no network access: download the "
-                                "model beforehand and pass its path)")
+    dims, sd, _ = _read_checkpoint(path, " (no network access: download the model beforehand and pass its path)")
+    enc = AudioEncoder(dims, sd)
     return enc.to(device) if device is not None else enc
 
 
@@ -437,56 +471,11 @@ def encode_file(path: str, encoder: AudioEncoder) -> torch.Tensor:
 _CAUSAL_PENALTY = -1.0e30      # added to scores of future keys in prefill: exp() of it is exactly 0 against any fp32 score, no overflow
 
 
-def _dec_dims(d) -> Dict[str, int]:
-    """OpenAI ``ModelDimensions`` (n_vocab, n_text_ctx, n_text_state, n_text_head, n_text_layer) or a Hugging Face Whisper ``config.json``
-    dict -> the decoder's sizes."""
-    get = (lambda k, default=None: d.get(k, default)) if isinstance(d, dict) else (lambda k, default=None: getattr(d, k, default))
-    if get("n_text_state") is not None:
-        width = int(get("n_text_state"))
-        return {"vocab": int(get("n_vocab")), "ctx": int(get("n_text_ctx")), "width": width, "heads": int(get("n_text_head")),
-                "layers": int(get("n_text_layer")), "ffn": 4 * width}
-    if get("d_model") is not None:
-        if get("activation_function", "gelu") != "gelu":
-            raise NotImplementedError(f"activation {get('activation_function')!r}: Whisper's erf GELU is what is built")
-        width = int(get("d_model"))
-        return {"vocab": int(get("vocab_size")), "ctx": int(get("max_target_positions")), "width": width,
-                "heads": int(get("decoder_attention_heads")), "layers": int(get("decoder_layers")),
-                "ffn": int(get("decoder_ffn_dim", 4 * width))}
-    raise ValueError("neither Whisper's ModelDimensions (n_text_state ...) nor a Hugging Face Whisper config (d_model ...)")
-
-
-# the decoder's table beside the encoder's (_HF_TO_OPENAI): Hugging Face WhisperDecoder names -> OpenAI's, applied in this order
-_HF_TO_OPENAI_DEC = (("embed_tokens.weight", "token_embedding.weight"), ("embed_positions.weight", "positional_embedding"),
-                     ("layers.", "blocks."), ("encoder_attn_layer_norm", "cross_attn_ln"), ("self_attn_layer_norm", "attn_ln"),
-                     ("final_layer_norm", "mlp_ln"), ("encoder_attn.q_proj", "cross_attn.query"), ("encoder_attn.k_proj", "cross_attn.key"),
-                     ("encoder_attn.v_proj", "cross_attn.value"), ("encoder_attn.out_proj", "cross_attn.out"),
-                     ("self_attn.q_proj", "attn.query"), ("self_attn.k_proj", "attn.key"), ("self_attn.v_proj", "attn.value"),
-                     ("self_attn.out_proj", "attn.out"), ("fc1", "mlp.0"), ("fc2", "mlp.2"))
-
-
-def _canonical_decoder(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """Either schema's decoder tensors under OpenAI's names without the ``decoder.`` prefix; everything else is dropped."""
-    out = {}
-    for k, v in state_dict.items():
-        if k.startswith("model."):
-            k = k[len("model."):]
-        if not k.startswith("decoder."):
-            continue
-        k = k[len("decoder."):]
-        if k.startswith("layers.") or k.startswith("embed_") or k.startswith("layer_norm."):
-            for a, b in _HF_TO_OPENAI_DEC:
-                k = k.replace(a, b)
-            if k.startswith("layer_norm."):
-                k = "ln." + k[len("layer_norm."):]
-        out[k] = v
-    return out
-
-
 class KVCache:
     """What a decoding loop keeps between steps: per layer the preallocated self-attention cache ``[R, T_max, D]`` (key, value), the
     cross-attention ``key(xa) | value(xa)`` rows ``[n_windows, Tk, 2 D]``, ``row_window [R]`` and the number of filled positions.
-    ``per_row``: the rows sit at positions of their own (``decode_many``): the workspace is ``hirest_whisper_decode_step_rows``'s and
-    ``length`` is not used."""
+    ``per_row``: the rows sit at positions of their own (the decoding loop of ``decode`` and ``decode_many``): the workspace is
+    ``hirest_whisper_decode_step_rows``'s and ``length`` is not used."""
 
     def __init__(self, decoder: "TextDecoder", xa: torch.Tensor, row_window: torch.Tensor, T_max: Optional[int] = None, per_row: bool = False):
         dev, D = xa.device, decoder.width
@@ -506,7 +495,7 @@ class KVCache:
         self.ws = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=dev)
 
 
-class TextDecoder(nn.Module):
+class TextDecoder(_FrozenWeights):
     """``whisper.model.TextDecoder``: token + learned positional embedding, pre-LN blocks (self-attention, cross-attention over the audio
     encoder's states, MLP), ``ln``, the tied-embedding LM head.  ``dims_or_config`` / ``state_dict`` as ``AudioEncoder``'s (either schema).
 
@@ -516,7 +505,7 @@ class TextDecoder(nn.Module):
 
     def __init__(self, dims_or_config, state_dict: Dict[str, torch.Tensor]):
         super().__init__()
-        self.dims = _dec_dims(dims_or_config)
+        self.dims = _dims(dims_or_config, "text")
         d = self.dims
         self.vocab, self.ctx, self.width, self.heads, self.layers, self.ffn = (d[k] for k in ("vocab", "ctx", "width", "heads", "layers", "ffn"))
         if self.width != 64 * self.heads:
@@ -524,8 +513,6 @@ class TextDecoder(nn.Module):
         if self.ffn % 16:
             raise NotImplementedError(f"ffn {self.ffn}: a multiple of 16 expected")
         self.vocab_padded = (self.vocab + 3) // 4 * 4
-        self.eps = 1e-5
-        sd = _canonical_decoder(state_dict)
         D, I = self.width, self.ffn
         want = {"token_embedding.weight": (self.vocab, D), "positional_embedding": (self.ctx, D), "ln.weight": (D,), "ln.bias": (D,)}
         for i in range(self.layers):
@@ -538,24 +525,7 @@ class TextDecoder(nn.Module):
                 want[p + f"{a}_ln.weight"] = want[p + f"{a}_ln.bias"] = (D,)
             want.update({p + "mlp_ln.weight": (D,), p + "mlp_ln.bias": (D,), p + "mlp.0.weight": (I, D), p + "mlp.0.bias": (I,),
                          p + "mlp.2.weight": (D, I), p + "mlp.2.bias": (D,)})
-        for k, shape in want.items():
-            if k not in sd:
-                raise KeyError(f"TextDecoder: {k} missing from the state dict")
-            if tuple(sd[k].shape) != shape:
-                raise ValueError(f"TextDecoder: {k} has shape {tuple(sd[k].shape)}, expected {shape}")
-            self.register_parameter(k.replace(".", "/"), nn.Parameter(sd[k].detach().float().clone(), requires_grad=False))
-        self._cache = None
-
-    def _apply(self, fn, *a, **k):
-        self._cache = None
-        return super()._apply(fn, *a, **k)
-
-    def _p(self, name: str) -> torch.Tensor:
-        return self._parameters[name.replace(".", "/")]
-
-    @property
-    def device(self) -> torch.device:
-        return self._p("ln.weight").device
+        self._freeze(_canonical(state_dict, "text"), want)
 
     def prepared_weights(self) -> Dict[str, object]:
         """The operands the kernels read: fused query | key | value (zero key bias), fused cross key | value, the embedding zero-padded to a
@@ -594,29 +564,6 @@ class TextDecoder(nn.Module):
         c["layers"], c["desc"] = layers, desc
         return c
 
-    def _w(self):
-        if self._cache is None:
-            if self.device.type != "cuda":
-                raise RuntimeError(f"{_NAME}.TextDecoder runs on MI355X only (no CPU fallback); move the model to a GPU")
-            self._cache = self.prepared_weights()
-        return self._cache
-
-    def _linear(self, x, w, bias, act=0, resid=None):
-        out = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
-        AudioEncoder._gemm(x.data_ptr(), x.shape[1], w, bias, out.data_ptr(), w.shape[0], x.shape[0], x.device, act=act, resid=resid)
-        return out
-
-    def _ln_linear(self, x, gamma, beta, w, bias, act=0):
-        M, K = x.shape
-        N = w.shape[0]
-        if M <= 256 and K % 256 == 0 and K <= 1024 and (N < 8192 or (K == 768 and M <= 32)):
-            out = torch.empty((M, N), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.load().hirest_gemm_f32_ln(x.data_ptr(), K, None, None, None, gamma.data_ptr(), beta.data_ptr(), self.eps, None, 0,
-                                                      w.data_ptr(), K, bias.data_ptr(), None, 0, out.data_ptr(), N, M, N, K, act,
-                                                      ops.stream_ptr()), "hirest_gemm_f32_ln")
-            return out
-        return self._linear(ops.layernorm(x, gamma, beta, self.eps, torch.empty_like(x)), w, bias, act=act)
-
     @torch.no_grad()
     def cross_kv(self, xa: torch.Tensor):
         """``xa [n_windows, Tk, D]`` -> per layer ``[n_windows, Tk, 2 D]``: the layer's ``key(xa) | value(xa)``, computed once per window"""
@@ -624,7 +571,7 @@ class TextDecoder(nn.Module):
         W, Tk, D = xa.shape
         rows = xa.to(self.device, torch.float32).contiguous().view(W * Tk, D)
         with torch.cuda.device(self.device):
-            return [self._linear(rows, c[f"ckv_w.{i}"], c[f"ckv_b.{i}"]).view(W, Tk, 2 * D) for i in range(self.layers)]
+            return [_linear(rows, c[f"ckv_w.{i}"], c[f"ckv_b.{i}"]).view(W, Tk, 2 * D) for i in range(self.layers)]
 
     def _sequences(self, tokens: torch.Tensor, cross_kv, Tk: int, keep=None):
         """[B, T] tokens (sequence b against window b of cross_kv) -> [B * T, D] states before ``ln``; ``keep(i, qkv)`` sees every layer's
@@ -638,33 +585,32 @@ class TextDecoder(nn.Module):
                                                 ops.stream_ptr()), "hirest_embedding_fwd_f32")
         for i in range(self.layers):
             p = f"blocks.{i}."
-            qkv = self._ln_linear(x, c[p + "attn_ln.weight"], c[p + "attn_ln.bias"], c[f"qkv_w.{i}"], c[f"qkv_b.{i}"])
+            qkv = _ln_linear(x, c[p + "attn_ln.weight"], c[p + "attn_ln.bias"], c[f"qkv_w.{i}"], c[f"qkv_b.{i}"])
             if keep is not None:
                 keep(i, qkv)
             att = torch.empty((B * T, D), dtype=torch.float32, device=dev)
             _lib.check(lib.hirest_attention_f32_qkv(qkv.data_ptr(), 3 * D, qkv.data_ptr() + 4 * D, qkv.data_ptr() + 8 * D, 3 * D, att.data_ptr(), B, T,
                                                     T, H, 64, 0.125, 0.0, _CAUSAL_PENALTY, ops.stream_ptr()), "hirest_attention_f32_qkv")
-            x = self._linear(att, c[p + "attn.out.weight"], c[p + "attn.out.bias"], resid=x)
-            q = self._ln_linear(x, c[p + "cross_attn_ln.weight"], c[p + "cross_attn_ln.bias"], c[p + "cross_attn.query.weight"],
-                                c[p + "cross_attn.query.bias"])
+            x = _linear(att, c[p + "attn.out.weight"], c[p + "attn.out.bias"], resid=x)
+            q = _ln_linear(x, c[p + "cross_attn_ln.weight"], c[p + "cross_attn_ln.bias"], c[p + "cross_attn.query.weight"],
+                           c[p + "cross_attn.query.bias"])
             kv = cross_kv[i]
             _lib.check(lib.hirest_attention_f32_qkv(q.data_ptr(), D, kv.data_ptr(), kv.data_ptr() + 4 * D, 2 * D, att.data_ptr(), B, T, Tk, H, 64,
                                                     0.125, 0.0, 0.0, ops.stream_ptr()), "hirest_attention_f32_qkv")
-            x = self._linear(att, c[p + "cross_attn.out.weight"], c[p + "cross_attn.out.bias"], resid=x)
-            hid = self._ln_linear(x, c[p + "mlp_ln.weight"], c[p + "mlp_ln.bias"], c[p + "mlp.0.weight"], c[p + "mlp.0.bias"], act=1)
-            x = self._linear(hid, c[p + "mlp.2.weight"], c[p + "mlp.2.bias"], resid=x)
+            x = _linear(att, c[p + "cross_attn.out.weight"], c[p + "cross_attn.out.bias"], resid=x)
+            hid = _ln_linear(x, c[p + "mlp_ln.weight"], c[p + "mlp_ln.bias"], c[p + "mlp.0.weight"], c[p + "mlp.0.bias"], act=1)
+            x = _linear(hid, c[p + "mlp.2.weight"], c[p + "mlp.2.bias"], resid=x)
         return x
 
     def _head(self, x: torch.Tensor) -> torch.Tensor:
         c = self._w()
-        return self._ln_linear(x, c["ln_g"], c["ln_b"], c["tok"], c["lm_b"])
+        return _ln_linear(x, c["ln_g"], c["ln_b"], c["tok"], c["lm_b"])
 
     @torch.no_grad()
     def forward(self, tokens: torch.Tensor, xa: Optional[torch.Tensor], kv_cache: Optional[KVCache] = None) -> torch.Tensor:
         """``tokens [B, T]``, ``xa [B, Tk, D]`` -> logits ``[B, T, n_vocab]``.  With ``kv_cache`` (``xa`` is then the cache's own): an empty
         cache takes the shared prompt ``[1, T]`` and returns ``[1, T, n_vocab]``; a filled one takes ``[R, 1]`` and returns ``[R, 1, n_vocab]``."""
-        if self.device.type != "cuda":
-            raise RuntimeError(f"{_NAME}.TextDecoder runs on MI355X only (no CPU fallback); move the model to a GPU")
+        self._require_gpu()
         if tokens.ndim == 1:
             tokens = tokens[None]
         B, T = tokens.shape
@@ -687,24 +633,26 @@ class TextDecoder(nn.Module):
             return kc.logits.view(B, 1, self.vocab_padded)[..., :self.vocab]
 
     @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor, kc: KVCache) -> torch.Tensor:
-        """The prompt ``[1, T]`` shared by every row of an empty cache, once: fills positions 0 .. T - 1 of all rows' caches (broadcast) and
-        returns the prompt's logits ``[T, vocab_padded]``."""
+    def prefill(self, tokens: torch.Tensor, kc: KVCache, rows: Optional[slice] = None, window: Optional[int] = None) -> torch.Tensor:
+        """The prompt ``[1, T]`` shared by every row of an empty cache, once: fills positions 0 .. T - 1 of all rows' caches (broadcast),
+        sets ``kc.length`` and returns the prompt's logits ``[T, vocab_padded]``.  With ``window`` (the decoding loop's per-row cache over
+        several windows): the same for the slice ``rows`` against that window's cross keys / values; ``kc.length`` stays."""
         T = int(tokens.shape[-1])
         if kc.length != 0:
             raise ValueError("prefill of a cache that already holds positions")
-        if kc.n_windows != 1:
+        if window is None and kc.n_windows != 1:
             raise NotImplementedError("prefill of rows over several windows: one window per cache is what decode() drives")
         if T > min(kc.T_max, self.ctx):
             raise ValueError(f"a prompt of {T} tokens does not fit the cache's {kc.T_max} positions")
-        D = self.width
+        D, w, rows = self.width, window or 0, rows if rows is not None else slice(None)
 
         def keep(i, qkv):          # the prompt's keys / values, the same for every candidate row of the window
-            kc.self_k[i][:, :T] = qkv[:, D:2 * D]
-            kc.self_v[i][:, :T] = qkv[:, 2 * D:]
+            kc.self_k[i][rows, :T] = qkv[:, D:2 * D]
+            kc.self_v[i][rows, :T] = qkv[:, 2 * D:]
         with torch.cuda.device(self.device):
-            x = self._sequences(tokens.view(1, T), kc.cross_kv, kc.Tk, keep)
-            kc.length = T
+            x = self._sequences(tokens.view(1, T), [kv[w:w + 1] for kv in kc.cross_kv], kc.Tk, keep)
+            if window is None:
+                kc.length = T
             return self._head(x)
 
     def step(self, ids: torch.Tensor, kc: KVCache) -> torch.Tensor:
@@ -929,84 +877,6 @@ def _initial_tokens(tokenizer: Tokenizer, options: DecodingOptions, n_ctx: int) 
     return tokens, tokens.index(tokenizer.sot)
 
 
-@torch.no_grad()
-def decode(model: "Whisper", mel: torch.Tensor, options: DecodingOptions = DecodingOptions(), *, return_candidates: bool = False):
-    """``whisper.decode``: one 30-second window ``[n_mels, 3000]`` (or encoder states ``[Tk, D]``) or a batch of them -> a
-    ``DecodingResult`` (a list for a batch).  Greedy at temperature 0; at temperature > 0 ``best_of`` candidates per window are sampled
-    and the one with the highest ``sum_logprobs / length`` is returned.  The loop enqueues ``hirest_whisper_decode_step`` +
-    ``hirest_whisper_step_tail`` per token and reads nothing back but the pinned stamp; tokens and sums are read once at the end.
-    ``return_candidates``: also every candidate's (tokens, sum_logprobs) per window (tests)."""
-    tokenizer = model.tokenizer
-    if tokenizer is None:
-        raise ValueError("the model has no tokenizer: load_model(path, tokenizer=...) or set model.tokenizer")
-    single = mel.ndim == 2
-    if single:
-        mel = mel[None]
-    dec, dev = model.decoder, model.device
-    n_audio_ctx = model.dims["n_audio_ctx"]
-    with torch.cuda.device(dev):
-        if mel.shape[-2:] == (n_audio_ctx, model.dims["n_audio_state"]):
-            xa = mel.to(dev, torch.float32)
-        else:
-            xa = model.encoder(mel)
-        initial, sot_index = _initial_tokens(tokenizer, options, dec.ctx)
-        sample_begin = len(initial)
-        sample_len = options.sample_len or dec.ctx // 2
-        group = (options.best_of or 1) if options.temperature > 0 else 1
-        T_max = min(dec.ctx, sample_begin + sample_len)
-        steps = T_max - sample_begin
-        if steps <= 0:
-            raise ValueError(f"a prompt of {sample_begin} tokens leaves no room to sample in a context of {dec.ctx}")
-        lib = _lib.load()
-        results, everything = [], []
-        for w in range(xa.shape[0]):                                  # (batching windows into one loop is a later step)
-            kc = KVCache(dec, xa[w:w + 1], torch.zeros(group, dtype=torch.int32), T_max)
-            params, mask = tail_params(tokenizer, options, dec.vocab, dec.vocab_padded, n_audio_ctx, 0, dev)
-            padded = dec.prefill(torch.tensor([initial], dtype=torch.int32), kc)            # [T, vocab_padded]
-            state = new_row_state(group, dev)
-            tokens = torch.full((group, steps), tokenizer.eot, dtype=torch.int32, device=dev)
-            ids = torch.empty((group,), dtype=torch.int32, device=dev)
-            stamp = torch.zeros(1, dtype=torch.int32).pin_memory()
-            first = torch.empty((group, dec.vocab_padded), dtype=torch.float32, device=dev)
-            first.copy_(padded[sample_begin - 1].expand(group, -1))
-            no_speech = None
-            if sot_index != sample_begin - 1 and tokenizer.no_speech is not None:
-                # Whisper reads no_speech_prob at the sot position: one tail call on that row, into a scratch state
-                scratch, sid = new_row_state(1, dev), torch.empty(1, dtype=torch.int32, device=dev)
-                row = padded[sot_index].contiguous()
-                _lib.check(lib.hirest_whisper_step_tail(row.data_ptr(), dec.vocab_padded, 1, dec.vocab_padded, 0, 0, C.byref(params),
-                                                        scratch.data_ptr(), sid.data_ptr(), None, None, None, ops.stream_ptr()), "hirest_whisper_step_tail")
-                no_speech = scratch
-            logits = first
-            for step in range(steps):
-                params.serial = step
-                _lib.check(lib.hirest_whisper_step_tail(logits.data_ptr(), dec.vocab_padded, group, dec.vocab_padded, step, steps, C.byref(params),
-                                                        state.data_ptr(), ids.data_ptr(), tokens.data_ptr(), None, stamp.data_ptr(), ops.stream_ptr()),
-                           "hirest_whisper_step_tail")
-                s = int(stamp[0])                                     # whatever step has landed by now: no wait
-                if (s & 1) or step == steps - 1:
-                    break
-                logits = dec.step(ids, kc)
-            torch.cuda.current_stream().synchronize()
-            toks, st = tokens.cpu().numpy(), state.cpu()
-            sums = st[:, 5].view(torch.float32).tolist()
-            nsp = (no_speech.cpu() if no_speech is not None else st)[0, 6:7].view(torch.float32).item()
-            cands = []
-            for g in range(group):
-                row = toks[g].tolist()
-                cands.append((row[:row.index(tokenizer.eot)] if tokenizer.eot in row else row, sums[g]))
-            best = max(range(group), key=lambda g: (cands[g][1] / max(len(cands[g][0]), 1), -g))
-            t, lp = cands[best]
-            text = tokenizer.decode(t).strip()
-            results.append(DecodingResult(audio_features=xa[w], language=tokenizer.language or "en", tokens=t, text=text,
-                                          avg_logprob=lp / (len(t) + 1), no_speech_prob=nsp, temperature=options.temperature,
-                                          compression_ratio=compression_ratio(text) if text else 0.0))
-            everything.append(cands)
-    if return_candidates:
-        return (results[0], everything[0]) if single else (results, everything)
-    return results[0] if single else results
-
-
 _PER_WINDOW_OPTIONS = ("prompt", "temperature", "best_of", "seed")     # what may differ between the windows of one decode_many call
 _ROWS_PER_CALL = 256           # hirest_gemm_f32_ln's forms, which the step's LayerNorm GEMMs rely on, take up to 256 rows
 FILES_IN_FLIGHT = 16           # transcribe_many's default: the largest of the sweep in DESIGN §4.17, where windows/s was still growing
@@ -1023,19 +893,30 @@ def new_row_ctl(rows, device) -> torch.Tensor:
 
 
 @torch.no_grad()
+def decode(model: "Whisper", mel: torch.Tensor, options: DecodingOptions = DecodingOptions(), *, return_candidates: bool = False):
+    """``whisper.decode``: one 30-second window ``[n_mels, 3000]`` (or encoder states ``[Tk, D]``) or a batch of them -> a
+    ``DecodingResult`` (a list for a batch).  Greedy at temperature 0; at temperature > 0 ``best_of`` candidates per window are sampled
+    and the one with the highest ``sum_logprobs / length`` is returned.  A window is one run of the decoding loop (``_decode_rows``) over
+    its candidate rows.  A batch runs one loop per window, in order; whoever wants the windows in one loop calls ``decode_many()``.
+    ``return_candidates``: also every candidate's (tokens, sum_logprobs) per window (tests)."""
+    single = mel.ndim == 2
+    if single:
+        mel = mel[None]
+    results, everything = _decode_windows(model, mel, [options] * int(mel.shape[0]), 0)          # 0 rows fit beside a window: one per loop
+    if return_candidates:
+        return (results[0], everything[0]) if single else (results, everything)
+    return results[0] if single else results
+
+
+@torch.no_grad()
 def decode_many(model: "Whisper", mels, options: Union[DecodingOptions, Sequence[DecodingOptions]] = DecodingOptions(), *,
                 return_candidates: bool = False):
-    """``decode`` for W windows that need not share their options — the current windows of W files — in ONE decoding loop: ``mels`` W
-    spectrograms ``[n_mels, 3000]`` or encoder states ``[Tk, D]`` (a tensor or a sequence of them), ``options`` one ``DecodingOptions`` or
-    W of them.  ``prompt``, ``temperature``, ``best_of`` and ``seed`` may differ between windows; any other field that does raises
-    ValueError.  One encoder call and one cross key / value projection for all windows, one cache of all candidate rows, the B = 1
-    prefill per window, then per token ``hirest_whisper_decode_step_rows`` + ``hirest_whisper_step_tail_rows`` over all rows — each at
-    its own position, with its own temperature, seed and remaining room, kept in a device record per row — until no row is active.
-    Returns a list of W ``DecodingResult`` with the values ``decode`` gives window by window, bit for bit; ``return_candidates`` as
-    ``decode``'s.  More than 256 candidate rows are split into consecutive loops."""
-    tokenizer = model.tokenizer
-    if tokenizer is None:
-        raise ValueError("the model has no tokenizer: load_model(path, tokenizer=...) or set model.tokenizer")
+    """``decode`` for W windows that need not share their options — the current windows of W files — in ONE run of the decoding loop:
+    ``mels`` W spectrograms ``[n_mels, 3000]`` or encoder states ``[Tk, D]`` (a tensor or a sequence of them), ``options`` one
+    ``DecodingOptions`` or W of them.  ``prompt``, ``temperature``, ``best_of`` and ``seed`` may differ between windows; any other field
+    that does raises ValueError.  Returns a list of W ``DecodingResult`` with the values ``decode`` gives window by window, bit for bit
+    (the same loop, whose rows do not depend on their neighbours); ``return_candidates`` as ``decode``'s.  More than 256 candidate rows
+    are split into consecutive loops."""
     mel = mels if torch.is_tensor(mels) else torch.stack([m.to(model.device) for m in mels])
     if mel.ndim != 3:
         raise ValueError(f"decode_many takes W windows [W, n_mels, frames] or [W, Tk, D], not a tensor of shape {tuple(mel.shape)}")
@@ -1046,9 +927,18 @@ def decode_many(model: "Whisper", mels, options: Union[DecodingOptions, Sequence
     for f in dataclasses.fields(DecodingOptions):
         if f.name not in _PER_WINDOW_OPTIONS and any(getattr(o, f.name) != getattr(opts[0], f.name) for o in opts):
             raise ValueError(f"decode_many: {f.name} differs between the windows of one call (only {', '.join(_PER_WINDOW_OPTIONS)} may)")
-    dec, dev = model.decoder, model.device
-    n_audio_ctx = model.dims["n_audio_ctx"]
-    plans = []                                                        # per window: initial tokens, sot index, steps, candidate rows
+    results, everything = _decode_windows(model, mel, opts, _ROWS_PER_CALL)
+    return (results, everything) if return_candidates else results
+
+
+def _decode_windows(model, mel, opts, rows_per_loop):
+    """What ``decode`` and ``decode_many`` share: the plan of every window (initial tokens, sot index, step budget cut by the context,
+    candidate rows), one encoder call for all of them, and consecutive windows — as many as fit ``rows_per_loop`` candidate rows, at
+    least one — through ``_decode_rows``.  -> (results, candidates), one entry per window."""
+    tokenizer, dec, dev = model.tokenizer, model.decoder, model.device
+    if tokenizer is None:
+        raise ValueError("the model has no tokenizer: load_model(path, tokenizer=...) or set model.tokenizer")
+    plans = []
     for o in opts:
         initial, sot_index = _initial_tokens(tokenizer, o, dec.ctx)
         steps = min(dec.ctx, len(initial) + (o.sample_len or dec.ctx // 2)) - len(initial)
@@ -1057,27 +947,30 @@ def decode_many(model: "Whisper", mels, options: Union[DecodingOptions, Sequence
         plans.append((initial, sot_index, steps, (o.best_of or 1) if o.temperature > 0 else 1))
     results, everything = [], []
     with torch.cuda.device(dev):
-        if mel.shape[-2:] == (n_audio_ctx, model.dims["n_audio_state"]):
+        if mel.shape[-2:] == (model.dims["n_audio_ctx"], model.dims["n_audio_state"]):
             xa = mel.to(dev, torch.float32)
         else:
             xa = model.encoder(mel)
         w0 = 0
-        while w0 < W:                                                 # consecutive windows, as many as fit the row limit (at least one)
+        while w0 < len(plans):
             w1, rows = w0 + 1, plans[w0][3]
-            while w1 < W and rows + plans[w1][3] <= _ROWS_PER_CALL:
+            while w1 < len(plans) and rows + plans[w1][3] <= rows_per_loop:
                 rows += plans[w1][3]
                 w1 += 1
             res, cands = _decode_rows(model, xa[w0:w1], opts[w0:w1], plans[w0:w1])
             results += res
             everything += cands
             w0 = w1
-    return (results, everything) if return_candidates else results
+    return results, everything
 
 
 def _decode_rows(model, xa, opts, plans):
-    """one loop over the candidate rows of ``xa``'s windows (decode_many)"""
+    """THE decoding loop, over the candidate rows of ``xa``'s windows: one cross key / value projection for all windows, one cache of
+    all rows, the B = 1 prefill per window, then per token ``hirest_whisper_step_tail_rows`` + ``hirest_whisper_decode_step_rows`` over
+    all rows — each at its own position, with its own temperature, seed and remaining room, kept in a device record per row — until
+    no row is active.  Nothing is read back in the loop but the pinned stamp; tokens and sums are read once at the end."""
     tokenizer, dec, dev, lib = model.tokenizer, model.decoder, model.device, _lib.load()
-    D, Vp = dec.width, dec.vocab_padded
+    Vp = dec.vocab_padded
     first_row = np.cumsum([0] + [p[3] for p in plans]).tolist()
     R = first_row[-1]
     T_max = max(len(initial) + steps for initial, _, steps, _ in plans)
@@ -1090,15 +983,11 @@ def _decode_rows(model, xa, opts, plans):
     no_speech, ctl_rows = [], []
     for w, (initial, sot_index, steps, group) in enumerate(plans):
         r0, T = first_row[w], len(initial)
-
-        def keep(i, qkv):          # the prompt's keys / values, the same for every candidate row of the window
-            kc.self_k[i][r0:r0 + group, :T] = qkv[:, D:2 * D]
-            kc.self_v[i][r0:r0 + group, :T] = qkv[:, 2 * D:]
-        x = dec._sequences(torch.tensor([initial], dtype=torch.int32), [kv[w:w + 1] for kv in kc.cross_kv], kc.Tk, keep)
-        padded = dec._head(x)                                         # [T, vocab_padded]
+        padded = dec.prefill(torch.tensor([initial], dtype=torch.int32), kc, rows=slice(r0, r0 + group), window=w)      # [T, vocab_padded]
         first[r0:r0 + group].copy_(padded[T - 1].expand(group, -1))
         scratch = None
-        if sot_index != T - 1 and tokenizer.no_speech is not None:    # no_speech_prob is read at the sot position, as decode() does
+        if sot_index != T - 1 and tokenizer.no_speech is not None:
+            # Whisper reads no_speech_prob at the sot position: one lock-step tail call on that row, into a scratch state
             scratch, sid = new_row_state(1, dev), torch.empty(1, dtype=torch.int32, device=dev)
             row = padded[sot_index].contiguous()
             _lib.check(lib.hirest_whisper_step_tail(row.data_ptr(), Vp, 1, Vp, 0, 0, C.byref(params), scratch.data_ptr(), sid.data_ptr(), None,
@@ -1190,20 +1079,11 @@ def load_model(path: str, device: Optional[Union[str, torch.device]] = None, tok
     """A local OpenAI ``.pt`` checkpoint or a Hugging Face model directory -> ``Whisper``.  There are no model names and no downloads: a
     bare name (``'small.en'``) raises FileNotFoundError saying so.  ``tokenizer``: a ``Tokenizer`` or a directory with ``vocab.json`` and
     ``merges.txt`` (default: the model directory itself when it has them; a ``.pt`` carries no vocabulary)."""
-    if os.path.isdir(path):
-        with open(os.path.join(path, "config.json")) as f:
-            config = json.load(f)
-        model = Whisper(config, _load_weights(path))
-        if tokenizer is None and os.path.isfile(os.path.join(path, "vocab.json")):
-            tokenizer = path
-    elif os.path.isfile(path):
-        ckpt = torch.load(path, map_location="cpu")
-        if not (isinstance(ckpt, dict) and "dims" in ckpt and "model_state_dict" in ckpt):
-            raise ValueError(f"{path}: not a Whisper checkpoint (a dict with 'dims' and 'model_state_dict')")
-        model = Whisper(ckpt["dims"], ckpt["model_state_dict"])
-    else:
-        raise FileNotFoundError(f"{path!r} is neither a local .pt checkpoint nor a model directory: model names are not resolved and "
-                                "nothing is downloaded (no network access) — download the model beforehand and pass its path")
+    dims, sd, is_dir = _read_checkpoint(path, ": model names are not resolved and nothing is downloaded (no network access) — download "
+                                              "the model beforehand and pass its path")
+    model = Whisper(dims, sd)
+    if is_dir and tokenizer is None and os.path.isfile(os.path.join(path, "vocab.json")):
+        tokenizer = path
     if isinstance(tokenizer, (str, os.PathLike)):
         multilingual = model.is_multilingual
         tokenizer = Tokenizer.from_dir(os.fspath(tokenizer), language="en" if multilingual else None, task="transcribe" if multilingual else None)

@@ -1,6 +1,8 @@
 """Windows of several files in one decoding loop: the per-row forms of the in-place self-attention and of the step tail,
 decode_many() and transcribe_many().  Every comparison is equality with the single-window path — hirest_attention_f32_decode_inplace,
-hirest_whisper_step_tail, decode(), transcribe() — which tests/test_gpu_whisper_dec.py pins to fp64 transformers: no tolerances here."""
+hirest_whisper_step_tail, decode(), transcribe() — which tests/test_gpu_whisper_dec.py pins to fp64 transformers: no tolerances here.
+decode() runs the per-row loop too, one window at a time, so every decode() reference is also held equal to the lock-step loop over
+TextDecoder.prefill / step (tests/_whisper_lockstep.py)."""
 import ctypes as C
 import wave
 
@@ -9,6 +11,7 @@ import pytest
 import torch
 
 import test_gpu_whisper_dec as S
+from _whisper_lockstep import lockstep_decode
 from hirest_amd import _lib, ops, synth, whisper
 
 pytestmark = pytest.mark.gpu
@@ -182,6 +185,8 @@ def test_decode_many_equals_decode(dev, monkeypatch):
             whisper.DecodingOptions(temperature=0.0, prompt=prompt9)]
     want = [whisper.decode(m, w, o, return_candidates=True) for w, o in zip(windows, opts)]
     assert len(want[1][1]) == 5 and max(len(t) for t, _ in want[1][1]) <= 23
+    for (res, cands), w, o in zip(want, windows, opts):               # the per-row loop of one window against the lock-step loop
+        assert (cands, res.no_speech_prob) == lockstep_decode(m, w, o)
     assert want[0][0].tokens == z["greedy_00_tokens"].tolist() and want[2][0].tokens == z["greedy_10_tokens"].tolist()
     for order in ([0, 1, 2], [2, 1, 0], [0, 1, 2]):                    # as given, reversed, and a second run
         res, cands = whisper.decode_many(m, [windows[i] for i in order], [opts[i] for i in order], return_candidates=True)
@@ -200,11 +205,24 @@ def test_decode_many_equals_decode(dev, monkeypatch):
         assert all(same_result(res[i], want[i][0]) and cands[i] == want[i][1] for i in range(3)), limit
 
 
+def test_decode_of_a_batch_equals_decode_of_each_window(dev):
+    m = model("q", dev)
+    _, xa, z, _, _ = S.decoder("q", dev)
+    o = whisper.DecodingOptions(temperature=0.4, best_of=5, seed=5, prompt=z["prompt9"].tolist())
+    res, cands = whisper.decode(m, xa, o, return_candidates=True)
+    assert isinstance(res, list) and len(res) == len(cands) == xa.shape[0] == 2
+    for w in range(2):
+        one, one_c = whisper.decode(m, xa[w], o, return_candidates=True)
+        assert same_result(res[w], one) and cands[w] == one_c and torch.equal(res[w].audio_features, xa[w])
+    assert all(same_result(a, b) for a, b in zip(whisper.decode(m, xa, o), res))
+
+
 def test_decode_many_of_one_window_equals_decode(dev):
     m = model("p", dev)
     _, xa, z, _, _ = S.decoder("p", dev)
     for o in (whisper.DecodingOptions(temperature=0.0), whisper.DecodingOptions(temperature=0.4, best_of=5, seed=5, prompt=z["prompt9"].tolist())):
         want, want_c = whisper.decode(m, xa[0], o, return_candidates=True)
+        assert (want_c, want.no_speech_prob) == lockstep_decode(m, xa[0], o)
         (got,), (got_c,) = whisper.decode_many(m, xa[:1], [o], return_candidates=True)
         assert same_result(got, want) and got_c == want_c
     assert whisper.decode(m, xa[0], whisper.DecodingOptions(temperature=0.0)).tokens == z["greedy_00_tokens"].tolist()

@@ -24,7 +24,7 @@ forward's error (bar 4):
     w384 / w512 / w1024 / w1280   teacher-forced 0.68 / 1.43 / 2.11 / 1.29, stepped through the cache 0.76 / 1.48 / 2.01 / 1.34; 40 rows
                             equal 3 rows bit for bit at all four
     s, decode()             the fixture's 8 tokens, avg_logprob -2.429613 (fp64 -2.429612), no_speech_prob 1.073e-05 (fp64 1.073e-05);
-                            decode_many of 9 windows x 5 candidates equals 9 decode() calls
+                            decode_many of 9 windows x 5 candidates equals 9 lock-step loops of 5 rows (tests/_whisper_lockstep.py)
 No bit differed between the kernel families: nothing in the kernels had to change.  
 """
 import numpy as np
@@ -33,6 +33,7 @@ import torch
 
 import _whisper_dec_ref as R
 import test_gpu_whisper_dec as S
+from _whisper_lockstep import lockstep_decode
 from test_gpu_whisper_many import same_result
 from hirest_amd import synth, whisper
 
@@ -184,10 +185,16 @@ def test_decode_and_decode_many_at_small_en_width(dev):
     assert res.temperature == 0.0 and res.text == model.tokenizer.decode(want).strip()
     windows = [xa[w % 3] for w in range(9)]
     opts = [whisper.DecodingOptions(temperature=0.4, best_of=5, seed=11 + w) for w in range(9)]
-    single = [whisper.decode(model, w, o, return_candidates=True) for w, o in zip(windows, opts)]
-    assert all(len(c) == 5 for _, c in single) and len({tuple(t) for _, c in single for t, _ in c}) > 9
+    # the references: the lock-step loop of each window alone, 5 rows (R <= 32: the other kernel family than the 45 rows below)
+    single = [lockstep_decode(model, w, o) for w, o in zip(windows, opts)]
+    assert all(len(c) == 5 for c, _ in single) and len({tuple(t) for c, _ in single for t, _ in c}) > 9
     many, cands = whisper.decode_many(model, windows, opts, return_candidates=True)
     assert len(many) == len(cands) == 9
     for w in range(9):
-        assert same_result(many[w], single[w][0]), (w, many[w].tokens, single[w][0].tokens, many[w].avg_logprob, single[w][0].avg_logprob)
-        assert cands[w] == single[w][1], w
+        assert cands[w] == single[w][0] and many[w].no_speech_prob == single[w][1], (w, cands[w], single[w])
+        t, lp = max(single[w][0], key=lambda c: c[1] / max(len(c[0]), 1))        # the pick among the reference's candidates (first on ties)
+        assert (many[w].tokens, many[w].avg_logprob, many[w].temperature) == (t, lp / (len(t) + 1), 0.4), (w, many[w].tokens, t)
+        assert many[w].text == model.tokenizer.decode(t).strip()
+    for w in (0, 4):                                                  # decode(): the same loop with one window's 5 rows
+        res, res_c = whisper.decode(model, windows[w], opts[w], return_candidates=True)
+        assert same_result(res, many[w]) and res_c == single[w][0] and res.no_speech_prob == single[w][1], w

@@ -4,7 +4,8 @@ windows per second through ``log_mel_spectrogram`` + ``AudioEncoder.forward`` fo
 front end, the convolution stem and the blocks (each timed on its own, a device synchronise closing every timed window), and the
 encoder's rate as a fraction of the 157-TFLOP/s fp32 MFMA peak DESIGN.md uses for the joint model.  Operations are counted from the
 shapes.  Each figure is the median with the min .. max spread over the repeats.  The decode leg: W windows through one
-``decode_many`` loop against W sequential ``decode`` calls at small.en's decoder shape.
+run of the decoding loop (``decode_many``) against W one-window runs of the same loop (W sequential ``decode`` calls) at small.en's
+decoder shape.
 
     python tools/whisper_bench.py [--repeats 7] [--warmup 2] [--batches 1 8] [--legs encoder decode] [--windows 1 2 4 8 16]
 """
@@ -56,8 +57,9 @@ def timed(fn, repeats, warmup, min_window=0.25):
 
 def decode_leg(a, dev):
     """W windows of small.en's shape (random weights, random encoder states) with best_of 5 and 64 forced steps — the eot embedding is
-    biased so far down that no row ends — through one decode_many() loop against W sequential decode() calls, the single-window path, in
-    the same process; and the same two with one step, which is the prefill and everything else a window costs before its loop."""
+    biased so far down that no row ends — through one decode_many() loop against W sequential decode() calls, which are W one-window
+    runs of the same loop, in the same process; and the same two with one step, which is the prefill and everything else a window
+    costs before its loop."""
     cfg = synth._dec_config(768, 12, 12, 1500, 51864, 448)
     eot, steps = 50256, 64
     sd = synth.whisper_decoder_state_dict(cfg, 83, eot, -8.0)
@@ -69,7 +71,7 @@ def decode_leg(a, dev):
     one = whisper.DecodingOptions(temperature=0.4, best_of=5, seed=5, sample_len=1)
     xa_all = synth.whisper_audio_states(cfg, max(a.windows), 7).to(dev)
     print(f"decode: small.en's decoder shape, best_of 5, {steps} forced steps, medians of {a.repeats} after {a.warmup} warm-up calls")
-    print("   W | decode_many: windows/s  ms/step  prefill share | W x decode: windows/s  ms/step  prefill share | ratio")
+    print("   W | decode_many: windows/s  ms/step  prefill share | W x decode (W one-window loops): windows/s  ms/step  prefill share | ratio")
     table = {}
     for W in a.windows:
         xa = xa_all[:W]
