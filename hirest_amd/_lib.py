@@ -470,6 +470,8 @@ _SIGNATURES = {
     "hirest_whisper_decode_step_rows": (C.c_int, [C.POINTER(WhisperDecoder), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                                   C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hirest_whisper_language_tail": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
     "hirest_vision_workspace_bytes": (C.c_size_t, [C.POINTER(VisionTower), C.c_int32]),
     "hirest_vision_forward": (C.c_int, [C.POINTER(VisionTower), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),

@@ -3,7 +3,8 @@
 // pick, the row's bookkeeping) with its state on the device — and the C-side step that strings them together with the exact-fp32
 // GEMMs.  The in-place self-attention form lives beside the kernel it shares its body with (joint.hip).  The `_rows` entry points
 //  are the same step and tail for rows of several windows, each with its own position, step, temperature and seed in a
-// device record (hirest_whisper_row_ctl).
+// device record (hirest_whisper_row_ctl).  Language detection is one per-row step at position 0 and the small softmax
+// over the language tokens' columns below (whisper_language_tail_kernel).
 #include "common.h"
 #include <math.h>
 
@@ -331,6 +332,47 @@ __global__ __launch_bounds__(64) void whisper_stamp_rows_kernel(const hirest_whi
     if (threadIdx.x == 0) *done_host = ((call + 1) << 1) | (none ? 1 : 0);
 }
 
+// Language detection: the softmax of a row of logits over the L <= 128 language columns alone, and its argmax.  One
+// wave per row; lane l holds table entries l and l + 64.  The maximum is the tail's pick (strict > over ascending ids, then the xor
+// tree with the lower id on ties), the sum a lane's two terms in ascending order and then wave_sum's xor tree in double: fixed orders, so a row
+// has the same bits whatever else is in the call.  Only the table's columns are read; an id outside [0, V) counts as absent
+// (probability 0) and is never an address.
+__global__ __launch_bounds__(64) void whisper_language_tail_kernel(const float* __restrict__ logits, int64_t ldx, int V,
+                                                                  const int32_t* __restrict__ ids, int L, int32_t* __restrict__ lang_token,
+                                                                  float* __restrict__ probs) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const float* x = logits + (int64_t)r * ldx;
+    float v[2];
+    bool have[2];
+    float bv = -INFINITY; int bi = 0x7fffffff;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int j = lane + 64 * e;
+        const int id = j < L ? ids[j] : -1;
+        have[e] = id >= 0 && id < V;
+        v[e] = have[e] ? x[id] : -INFINITY;
+        if (have[e] && (bi == 0x7fffffff || v[e] > bv)) { bv = v[e]; bi = id; }      // (ascending ids: the first of equals stays)
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    // The denominator and the quotients in double: every quotient carries the denominator's rounding error whole, so a row's sum
+    // would miss 1 by what L - 1 fp32 additions lose (3e-7 at L = 100) while a single probability only shows it scaled by itself.
+    // Summed in double the sum is exact to fp32, each quotient is rounded once, and a row sums to 1 within those roundings.
+    float p[2];
+    double s = 0.0;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) { p[e] = have[e] ? expf(v[e] - bv) : 0.f; s += (double)p[e]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+        if (lane + 64 * e < L) probs[(int64_t)r * L + lane + 64 * e] = (float)((double)p[e] / s);
+    if (lane == 0) lang_token[r] = bi == 0x7fffffff ? -1 : bi;
+}
+
 __global__ __launch_bounds__(256) void gumbel_bits_kernel(uint32_t seed, uint32_t serial, int R, int V, uint32_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)R * V) return;
@@ -460,6 +502,15 @@ extern "C" int hirest_whisper_step_tail_rows(const float* logits, int64_t ldx, i
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(whisper_tail_rows_kernel, dim3(R), dim3(1024), 0, s, logits, ldx, (int)V, ld_tokens, c, ctl, state, next_ids, tokens, logprobs);
     if (done_host) hipLaunchKernelGGL(whisper_stamp_rows_kernel, dim3(1), dim3(64), 0, s, ctl, (int)R, (int)call, done_host);
+    return hirest_launch_status();
+}
+
+extern "C" int hirest_whisper_language_tail(const float* logits, int64_t ldx, int32_t R, int32_t V, const int32_t* language_ids, int32_t L,
+                                            int32_t* lang_token, float* probs, void* stream) {
+    if (!logits || !language_ids || !lang_token || !probs || R <= 0 || V <= 0) return HIREST_E_BADARG;
+    if (L < 1 || L > 128 || ldx < V) return HIREST_E_SHAPE;
+    hipLaunchKernelGGL(whisper_language_tail_kernel, dim3(R), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), logits, ldx, (int)V, language_ids,
+                       (int)L, lang_token, probs);
     return hirest_launch_status();
 }
 

@@ -9,6 +9,7 @@ tokens, 0.34 TFLOP per 30 s window) and the part Whisper's users call directly::
     model.embed_audio(mel) / model.encoder(mel)                   ->  AudioEncoder.embed_audio / AudioEncoder.forward
 
     whisper.load_model / model.decode / whisper.transcribe / utils.write_srt  ->  the same names here (sampling branch; no beam search)
+    whisper.detect_language / tokenizer.LANGUAGES / TO_LANGUAGE_CODE          ->  the same names here
 
 Whisper is not under the reference tree; the front end restates ``whisper/audio.py`` and the encoder ``whisper/model.py::AudioEncoder``
 from the published definitions, pinned against ``transformers``' WhisperFeatureExtractor / WhisperEncoder (tests/golden/whisper_*.npz).
@@ -29,6 +30,7 @@ Whisper's ``decoder(tokens, xa, kv_cache)`` surface; the lock-step loop over the
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import dataclasses
 import functools
@@ -670,6 +672,41 @@ class TextDecoder(_FrozenWeights):
 # the tokenizer
 # ---------------------------------------------------------------------------------------------------------------------------------
 
+# whisper/tokenizer.py's tables: language code -> name in the order of the language tokens, and name or alias -> code
+LANGUAGES = {
+    "en": "english", "zh": "chinese", "de": "german", "es": "spanish", "ru": "russian", "ko": "korean", "fr": "french", "ja": "japanese",
+    "pt": "portuguese", "tr": "turkish", "pl": "polish", "ca": "catalan", "nl": "dutch", "ar": "arabic", "sv": "swedish", "it": "italian",
+    "id": "indonesian", "hi": "hindi", "fi": "finnish", "vi": "vietnamese", "he": "hebrew", "uk": "ukrainian", "el": "greek", "ms": "malay",
+    "cs": "czech", "ro": "romanian", "da": "danish", "hu": "hungarian", "ta": "tamil", "no": "norwegian", "th": "thai", "ur": "urdu",
+    "hr": "croatian", "bg": "bulgarian", "lt": "lithuanian", "la": "latin", "mi": "maori", "ml": "malayalam", "cy": "welsh", "sk": "slovak",
+    "te": "telugu", "fa": "persian", "lv": "latvian", "bn": "bengali", "sr": "serbian", "az": "azerbaijani", "sl": "slovenian",
+    "kn": "kannada", "et": "estonian", "mk": "macedonian", "br": "breton", "eu": "basque", "is": "icelandic", "hy": "armenian",
+    "ne": "nepali", "mn": "mongolian", "bs": "bosnian", "kk": "kazakh", "sq": "albanian", "sw": "swahili", "gl": "galician",
+    "mr": "marathi", "pa": "punjabi", "si": "sinhala", "km": "khmer", "sn": "shona", "yo": "yoruba", "so": "somali", "af": "afrikaans",
+    "oc": "occitan", "ka": "georgian", "be": "belarusian", "tg": "tajik", "sd": "sindhi", "gu": "gujarati", "am": "amharic",
+    "yi": "yiddish", "lo": "lao", "uz": "uzbek", "fo": "faroese", "ht": "haitian creole", "ps": "pashto", "tk": "turkmen", "nn": "nynorsk",
+    "mt": "maltese", "sa": "sanskrit", "lb": "luxembourgish", "my": "myanmar", "bo": "tibetan", "tl": "tagalog", "mg": "malagasy",
+    "as": "assamese", "tt": "tatar", "haw": "hawaiian", "ln": "lingala", "ha": "hausa", "ba": "bashkir", "jw": "javanese",
+    "su": "sundanese", "yue": "cantonese"}
+TO_LANGUAGE_CODE = {
+    **{name: code for code, name in LANGUAGES.items()},
+    "burmese": "my", "valencian": "ca", "flemish": "nl", "haitian": "ht", "letzeburgesch": "lb", "pushto": "ps", "panjabi": "pa",
+    "moldavian": "ro", "moldovan": "ro", "sinhalese": "si", "castilian": "es", "mandarin": "zh"}
+_LANGUAGE_TOKEN = re.compile(r"<\|([a-z]{2,3})\|>")
+
+
+def language_code(language: str) -> str:
+    """A language code, name or alias in any letter case ("de", "German", "castilian", "EN") -> its code; ValueError naming the value
+    for anything else."""
+    if isinstance(language, str):
+        key = language.strip().lower()
+        if key in LANGUAGES:
+            return key
+        if key in TO_LANGUAGE_CODE:
+            return TO_LANGUAGE_CODE[key]
+    raise ValueError(f"unsupported language: {language!r}")
+
+
 class Tokenizer:
     """Whisper's tokenizer over the project's byte-level BPE (``bytebpe.ByteBPETokenizer``): GPT-2's vocabulary and merges plus
     Whisper's special tokens; the 1501 timestamp tokens ``<|0.00|>`` .. ``<|30.00|>`` follow ``<|notimestamps|>``.
@@ -725,6 +762,62 @@ class Tokenizer:
         if self.task is not None:
             seq.append(self.transcribe if self.task == "transcribe" else self.translate)
         return tuple(seq)
+
+    @functools.cached_property
+    def _language_table(self):
+        """(ids ascending, their codes): the special tokens ``<|xx|>`` / ``<|xxx|>`` this vocabulary has whose code is a language —
+        99 in the first multilingual vocabularies, 100 with ``yue``, none in an English-only one"""
+        found = []
+        for s, i in self.specials.items():
+            m = _LANGUAGE_TOKEN.fullmatch(s)
+            if m and m.group(1) in LANGUAGES:
+                found.append((i, m.group(1)))
+        found.sort()
+        return tuple(i for i, _ in found), tuple(c for _, c in found)
+
+    @property
+    def all_language_tokens(self) -> Tuple[int, ...]:
+        return self._language_table[0]
+
+    @property
+    def all_language_codes(self) -> Tuple[str, ...]:
+        return self._language_table[1]
+
+    @property
+    def multilingual(self) -> bool:
+        """Whether this tokenizer was set up as a multilingual checkpoint's: it has language tokens AND was given a language or a task.
+        Which tokens exist does not decide it — the English-only vocabularies of the released ``*.en`` checkpoints carry ``<|en|>`` ..
+        ``<|su|>`` as well — but how the tokenizer was configured, as in Whisper, whose ``get_tokenizer`` leaves language and task at
+        None for an English-only model: ``load_model`` does the same, ``with_language(None, "transcribe")`` is multilingual with the
+        language to be detected."""
+        return bool(self.all_language_tokens) and (self.language is not None or self.task is not None)
+
+    @property
+    def language_token(self) -> int:
+        """the id of ``<|language|>`` for this tokenizer's language (Whisper's ``language_token``)"""
+        if self.language is None:
+            raise ValueError("this tokenizer does not have a language configured")
+        return self.to_language_token(self.language)
+
+    def to_language_token(self, language: str) -> int:
+        token = self.specials.get(f"<|{language}|>")
+        if token is None or token not in self.all_language_tokens:
+            raise KeyError(f"language {language!r} not found in the tokenizer")
+        return token
+
+    def with_language(self, language: Optional[str], task: Optional[str] = "transcribe") -> "Tokenizer":
+        """Whisper's ``get_tokenizer(multilingual, language=, task=)`` from this one: a copy with that language (a code, name or alias;
+        None: to be detected) and task (transcribe, as Whisper's default for a multilingual model, or translate) that shares the BPE
+        and every table; this tokenizer is not changed.  ``with_language(None, None)`` is the English-only configuration."""
+        if language is not None:
+            language = language_code(language)
+            if self.all_language_tokens and language not in self.all_language_codes:
+                raise ValueError(f"unsupported language: {language!r} has no token in this vocabulary")
+        if task not in (None, "transcribe", "translate"):
+            raise ValueError(f"unsupported task: {task!r} (transcribe or translate)")
+        other = copy.copy(self)
+        other.language, other.task = language, task
+        return other
 
     def encode(self, text: str) -> List[int]:
         return self.bpe.tokenize_ids(text)
@@ -782,8 +875,8 @@ class Tokenizer:
 
 @dataclasses.dataclass(frozen=True)
 class DecodingOptions:
-    task: str = "transcribe"
-    language: Optional[str] = None
+    task: str = "transcribe"                  # or "translate"; "transcribe" yields to a tokenizer made with with_language(.., "translate")
+    language: Optional[str] = None            # a code, name or alias; None: the tokenizer's, else detected (multilingual tokenizers only)
     temperature: float = 0.0
     sample_len: Optional[int] = None          # maximum number of tokens to sample (default: half the text context)
     best_of: Optional[int] = None             # independent candidates when temperature > 0
@@ -821,6 +914,7 @@ class DecodingResult:
     no_speech_prob: float = float("nan")
     temperature: float = float("nan")
     compression_ratio: float = float("nan")
+    language_probs: Optional[Dict[str, float]] = None      # detect_language's, where decode() detected the window's language
 
 
 def compression_ratio(text: str) -> float:
@@ -867,8 +961,37 @@ def new_row_state(R: int, device) -> torch.Tensor:
     return st.to(device)
 
 
-def _initial_tokens(tokenizer: Tokenizer, options: DecodingOptions, n_ctx: int) -> Tuple[List[int], int]:
-    tokens = list(tokenizer.sot_sequence)
+def _prompt_language(tokenizer: Tokenizer, options: DecodingOptions) -> Optional[str]:
+    """The code of the language a window's prompt names on a multilingual tokenizer: ``options.language`` (a code, name or
+    alias) when given, else the tokenizer's own; None: neither names one, and ``decode`` detects it."""
+    if options.language is not None:
+        return language_code(options.language)
+    return tokenizer.language
+
+
+def _initial_tokens(tokenizer: Tokenizer, options: DecodingOptions, n_ctx: int, language: Optional[str] = None) -> Tuple[List[int], int]:
+    """(a window's initial tokens, the index of ``<|startoftranscript|>`` among them).  A multilingual tokenizer (``Tokenizer.
+    multilingual``) gets Whisper's ``sot, <|language|>, <|task|>``: the language is ``language`` (what ``decode`` detected) or
+    ``_prompt_language``'s, the task is ``options.task`` and, where that is left at "transcribe", the task the tokenizer was given
+    (``with_language(.., "translate")``) — so ``DecodingOptions(task="transcribe")`` cannot ask a tokenizer made for translation to
+    transcribe: give the model ``tokenizer.with_language(language, "transcribe")`` instead.  An English-only tokenizer ignores both
+    options, whatever tokens its vocabulary has, and the prompt starts with its own ``sot_sequence``."""
+    if tokenizer.multilingual:
+        language = language or _prompt_language(tokenizer, options)
+        if language is None:
+            raise ValueError("no language: neither options.language nor the tokenizer names one (decode() detects it before it builds the prompt)")
+        task = options.task if options.task != "transcribe" else tokenizer.task or "transcribe"
+        if task not in ("transcribe", "translate"):
+            raise NotImplementedError(f"task {task!r} is not built: transcribe or translate")
+        task_token = tokenizer.transcribe if task == "transcribe" else tokenizer.translate
+        if task_token is None:
+            raise ValueError(f"the special-token table has no <|{task}|>")
+        try:
+            tokens = [tokenizer.sot, tokenizer.to_language_token(language), task_token]
+        except KeyError as e:
+            raise ValueError(f"unsupported language: {language!r} has no token in this vocabulary") from e
+    else:
+        tokens = list(tokenizer.sot_sequence)
     if options.without_timestamps:
         tokens.append(tokenizer.no_timestamps)
     if options.prompt:                                                # (an empty prompt — a file's first window — adds no sot_prev either)
@@ -877,7 +1000,7 @@ def _initial_tokens(tokenizer: Tokenizer, options: DecodingOptions, n_ctx: int) 
     return tokens, tokens.index(tokenizer.sot)
 
 
-_PER_WINDOW_OPTIONS = ("prompt", "temperature", "best_of", "seed")     # what may differ between the windows of one decode_many call
+_PER_WINDOW_OPTIONS = ("prompt", "temperature", "best_of", "seed", "language")     # what may differ between the windows of one decode_many call
 _ROWS_PER_CALL = 256           # hirest_gemm_f32_ln's forms, which the step's LayerNorm GEMMs rely on, take up to 256 rows
 FILES_IN_FLIGHT = 16           # transcribe_many's default: the largest of the sweep in DESIGN §4.17, where windows/s was still growing
 
@@ -892,13 +1015,72 @@ def new_row_ctl(rows, device) -> torch.Tensor:
     return torch.from_numpy(ctl).to(device)
 
 
+def _audio_states(model, mel: torch.Tensor) -> torch.Tensor:
+    """windows ``[W, n_mels, 3000]`` through the encoder, in one call — or, already encoder states ``[W, Tk, D]``, as they are"""
+    if mel.shape[-2:] == (model.dims["n_audio_ctx"], model.dims["n_audio_state"]):
+        return mel.to(model.device, torch.float32)
+    return model.encoder(mel)
+
+
+@torch.no_grad()
+def detect_language(model: "Whisper", mel: torch.Tensor, tokenizer: Optional[Tokenizer] = None):
+    """``whisper.detect_language``: one window ``[n_mels, 3000]`` (or its encoder states ``[Tk, D]``) or a batch of W of them ->
+    ``(language_tokens, language_probs)``: the id of the most probable language token per window (an int64 tensor ``[W]`` on the host)
+    and per window a dict code -> probability over the tokenizer's languages (the softmax of the ``<|startoftranscript|>`` position's
+    logits over the language tokens alone); a tensor without dimensions and one dict for a single window.  ValueError when the
+    tokenizer is not multilingual (``Tokenizer.multilingual``: no language tokens, or an English-only checkpoint's configuration).
+
+    One encoder call and one cross key / value projection for all windows, ONE pass of ``<|startoftranscript|>`` at position 0 through
+    the per-row decode step with row w attending window w (a cache of one position), ``hirest_whisper_language_tail`` on its logits,
+    and one read-back.  A window's values do not depend on the others of the call."""
+    tokenizer = tokenizer if tokenizer is not None else getattr(model, "tokenizer", None)
+    if tokenizer is None:
+        raise ValueError("the model has no tokenizer: load_model(path, tokenizer=...) or detect_language(..., tokenizer=...)")
+    table, codes = tokenizer.all_language_tokens, tokenizer.all_language_codes
+    if not tokenizer.multilingual:                                    # (Whisper's check, too, is of how the tokenizer was configured)
+        raise ValueError("this model doesn't have language tokens so it can't perform lang id: the tokenizer has none, or is English-only's")
+    L = len(table)
+    single = mel.ndim == 2
+    if single:
+        mel = mel[None]
+    dec, dev, lib = model.decoder, model.device, _lib.load()
+    if L > 128 or table[-1] >= dec.vocab:
+        raise ValueError(f"{L} language tokens up to id {table[-1]}: at most 128, inside the vocabulary of {dec.vocab}")
+    with torch.cuda.device(dev):
+        xa = _audio_states(model, mel)
+        W = int(xa.shape[0])
+        ids_table = torch.tensor(table, dtype=torch.int32, device=dev)
+        found = torch.empty((W,), dtype=torch.int32, device=dev)
+        probs = torch.empty((W, L), dtype=torch.float32, device=dev)
+        for r0 in range(0, W, _ROWS_PER_CALL):
+            R = min(_ROWS_PER_CALL, W - r0)
+            kc = KVCache(dec, xa[r0:r0 + R], torch.arange(R, dtype=torch.int32), 1, per_row=True)
+            ctl = new_row_ctl([(0, 0, 1, 0, 0, 0.0)] * R, dev)                   # every row at position 0
+            ids = torch.full((R,), tokenizer.sot, dtype=torch.int32, device=dev)
+            _lib.check(lib.hirest_whisper_decode_step_rows(C.byref(dec._w()["desc"]), R, ctl.data_ptr(), ids.data_ptr(), kc.k_ptrs, kc.v_ptrs,
+                                                           kc.T_max, kc.x_ptrs, kc.n_windows, kc.Tk, kc.row_window.data_ptr(),
+                                                           kc.logits.data_ptr(), kc.ws.data_ptr(), kc.ws.numel(), ops.stream_ptr()),
+                       "hirest_whisper_decode_step_rows")
+            _lib.check(lib.hirest_whisper_language_tail(kc.logits.data_ptr(), dec.vocab_padded, R, dec.vocab, ids_table.data_ptr(), L,
+                                                        found[r0:].data_ptr(), probs[r0:].data_ptr(), ops.stream_ptr()),
+                       "hirest_whisper_language_tail")
+        tokens, rows = found.cpu().to(torch.int64), probs.cpu().tolist()          # the call's only read-back, after every pass is enqueued
+    dicts = [dict(zip(codes, row)) for row in rows]
+    return (tokens[0], dicts[0]) if single else (tokens, dicts)
+
+
 @torch.no_grad()
 def decode(model: "Whisper", mel: torch.Tensor, options: DecodingOptions = DecodingOptions(), *, return_candidates: bool = False):
     """``whisper.decode``: one 30-second window ``[n_mels, 3000]`` (or encoder states ``[Tk, D]``) or a batch of them -> a
     ``DecodingResult`` (a list for a batch).  Greedy at temperature 0; at temperature > 0 ``best_of`` candidates per window are sampled
     and the one with the highest ``sum_logprobs / length`` is returned.  A window is one run of the decoding loop (``_decode_rows``) over
     its candidate rows.  A batch runs one loop per window, in order; whoever wants the windows in one loop calls ``decode_many()``.
-    ``return_candidates``: also every candidate's (tokens, sum_logprobs) per window (tests)."""
+    With a multilingual tokenizer (``Tokenizer.multilingual``: what ``load_model`` gives a multilingual checkpoint) the prompt names
+    ``options.language`` (else the tokenizer's language) and ``options.task`` (transcribe or translate; left at "transcribe" it
+    yields to the task the tokenizer was made with, so a ``with_language(.., "translate")`` tokenizer translates whatever
+    ``options.task`` says — see ``_initial_tokens``); an English-only one ignores both.  Where neither names a language, the windows' languages are detected first, in one ``detect_language``
+    pass, and ``result.language`` / ``result.language_probs`` say what was found.  ``task="lang_id"`` is not built: call
+    ``detect_language``.  ``return_candidates``: also every candidate's (tokens, sum_logprobs) per window (tests)."""
     single = mel.ndim == 2
     if single:
         mel = mel[None]
@@ -913,7 +1095,7 @@ def decode_many(model: "Whisper", mels, options: Union[DecodingOptions, Sequence
                 return_candidates: bool = False):
     """``decode`` for W windows that need not share their options — the current windows of W files — in ONE run of the decoding loop:
     ``mels`` W spectrograms ``[n_mels, 3000]`` or encoder states ``[Tk, D]`` (a tensor or a sequence of them), ``options`` one
-    ``DecodingOptions`` or W of them.  ``prompt``, ``temperature``, ``best_of`` and ``seed`` may differ between windows; any other field
+    ``DecodingOptions`` or W of them.  ``prompt``, ``temperature``, ``best_of``, ``seed`` and ``language`` may differ between windows; any other field
     that does raises ValueError.  Returns a list of W ``DecodingResult`` with the values ``decode`` gives window by window, bit for bit
     (the same loop, whose rows do not depend on their neighbours); ``return_candidates`` as ``decode``'s.  More than 256 candidate rows
     are split into consecutive loops."""
@@ -938,33 +1120,40 @@ def _decode_windows(model, mel, opts, rows_per_loop):
     tokenizer, dec, dev = model.tokenizer, model.decoder, model.device
     if tokenizer is None:
         raise ValueError("the model has no tokenizer: load_model(path, tokenizer=...) or set model.tokenizer")
+    codes = tokenizer.all_language_codes if tokenizer.multilingual else ()
+    # per window (language code, detect_language's probabilities): (None, None) on an English-only tokenizer
+    langs = [(_prompt_language(tokenizer, o) if codes else None, None) for o in opts]
+    detect = [w for w, (code, _) in enumerate(langs) if codes and code is None]
     plans = []
-    for o in opts:
-        initial, sot_index = _initial_tokens(tokenizer, o, dec.ctx)
+    for o, (code, _) in zip(opts, langs):
+        # (a window whose language is still to be detected is planned with a stand-in: the prompt's length does not depend on it)
+        initial, sot_index = _initial_tokens(tokenizer, o, dec.ctx, code or (codes[0] if codes else None))
         steps = min(dec.ctx, len(initial) + (o.sample_len or dec.ctx // 2)) - len(initial)
         if steps <= 0:
             raise ValueError(f"a prompt of {len(initial)} tokens leaves no room to sample in a context of {dec.ctx}")
         plans.append((initial, sot_index, steps, (o.best_of or 1) if o.temperature > 0 else 1))
     results, everything = [], []
     with torch.cuda.device(dev):
-        if mel.shape[-2:] == (model.dims["n_audio_ctx"], model.dims["n_audio_state"]):
-            xa = mel.to(dev, torch.float32)
-        else:
-            xa = model.encoder(mel)
+        xa = _audio_states(model, mel)
+        if detect:                                                    # all of the call's undetermined windows in one pass, before any prefill
+            found, probs = detect_language(model, xa[detect], tokenizer)
+            for w, token, p in zip(detect, found.tolist(), probs):
+                langs[w] = (codes[tokenizer.all_language_tokens.index(token)], p)
+                plans[w][0][plans[w][1] + 1] = token
         w0 = 0
         while w0 < len(plans):
             w1, rows = w0 + 1, plans[w0][3]
             while w1 < len(plans) and rows + plans[w1][3] <= rows_per_loop:
                 rows += plans[w1][3]
                 w1 += 1
-            res, cands = _decode_rows(model, xa[w0:w1], opts[w0:w1], plans[w0:w1])
+            res, cands = _decode_rows(model, xa[w0:w1], opts[w0:w1], plans[w0:w1], langs[w0:w1])
             results += res
             everything += cands
             w0 = w1
     return results, everything
 
 
-def _decode_rows(model, xa, opts, plans):
+def _decode_rows(model, xa, opts, plans, langs):
     """THE decoding loop, over the candidate rows of ``xa``'s windows: one cross key / value projection for all windows, one cache of
     all rows, the B = 1 prefill per window, then per token ``hirest_whisper_step_tail_rows`` + ``hirest_whisper_decode_step_rows`` over
     all rows — each at its own position, with its own temperature, seed and remaining room, kept in a device record per row — until
@@ -1025,9 +1214,9 @@ def _decode_rows(model, xa, opts, plans):
         best = max(range(group), key=lambda g: (cands[g][1] / max(len(cands[g][0]), 1), -g))
         t, lp = cands[best]
         text = tokenizer.decode(t).strip()
-        results.append(DecodingResult(audio_features=xa[w], language=tokenizer.language or "en", tokens=t, text=text,
+        results.append(DecodingResult(audio_features=xa[w], language=langs[w][0] or tokenizer.language or "en", tokens=t, text=text,
                                       avg_logprob=lp / (len(t) + 1), no_speech_prob=nsp, temperature=opts[w].temperature,
-                                      compression_ratio=compression_ratio(text) if text else 0.0))
+                                      compression_ratio=compression_ratio(text) if text else 0.0, language_probs=langs[w][1]))
         everything.append(cands)
     return results, everything
 
@@ -1068,6 +1257,9 @@ class Whisper(nn.Module):
     def decode(self, mel, options: DecodingOptions = DecodingOptions()):
         return decode(self, mel, options)
 
+    def detect_language(self, mel, tokenizer: Optional[Tokenizer] = None):
+        return detect_language(self, mel, tokenizer)
+
     def transcribe(self, audio, **kw):
         return transcribe(self, audio, **kw)
 
@@ -1104,15 +1296,11 @@ class _FileWalk:
         self.tokenizer = tokenizer = decode_options.pop("tokenizer", None) or getattr(model, "tokenizer", None)
         if tokenizer is None:
             raise ValueError("no tokenizer: load_model(path, tokenizer=...) or transcribe(..., tokenizer=...)")
+        # A multilingual tokenizer (``Tokenizer.multilingual``): the code of ``language=`` — a code, name or alias — or None until
+        # ``_detect_file_languages`` has looked at the file's first window.  English-only: "en" whatever was asked.
+        self.model, self.multilingual = model, tokenizer.multilingual
         language = decode_options.get("language")
-        if getattr(model, "is_multilingual", False):
-            if language is None:
-                raise NotImplementedError("language detection is not built: pass language= for a multilingual model")
-        else:
-            language = "en"
-        if isinstance(language, str) and language.lower() == "english":
-            language = "en"
-        self.language = language
+        self.language = (language_code(language) if language is not None else None) if self.multilingual else "en"
         dims = model.dims
         if torch.is_tensor(audio) and audio.ndim == 2:
             self.mel = audio
@@ -1130,12 +1318,23 @@ class _FileWalk:
         if initial_prompt is not None:
             self.all_tokens.extend(tokenizer.encode(" " + initial_prompt.strip()))
 
+    @property
+    def finished(self) -> bool:
+        return self.seek >= self.content_frames
+
+    def first_window(self) -> torch.Tensor:
+        return pad_or_trim(self.mel[:, :N_FRAMES], N_FRAMES)
+
     def next_request(self):
-        if self.seek >= self.content_frames:
+        if self.finished:
             return None
         t = self.temperatures[self.attempt]
         kw = dict(self.decode_options)
         kw["prompt"] = self.all_tokens[self.reset_since:]
+        if self.multilingual:
+            if self.language is None:                                 # (nobody detected it together with other files')
+                _detect_file_languages(self.model, [self])
+            kw["language"] = self.language                            # every window of the file decodes in the file's language
         for k in (("beam_size", "patience") if t > 0 else ("best_of",)):      # the sampling branch has no beams, the greedy one no candidates
             kw.pop(k, None)
         return pad_or_trim(self.mel[:, self.seek:self.seek + N_FRAMES], N_FRAMES), DecodingOptions(**kw, temperature=float(t))
@@ -1195,8 +1394,22 @@ class _FileWalk:
             self.reset_since = len(self.all_tokens)
 
     def result(self) -> Dict[str, object]:
+        if self.multilingual and self.language is None:               # a file without a window to decode still names its language
+            _detect_file_languages(self.model, [self])
         text_tokens = [t for s in self.all_segments for t in s["tokens"] if t < self.tokenizer.eot]
         return {"text": self.tokenizer.decode(text_tokens), "segments": self.all_segments, "language": self.language}
+
+
+def _detect_file_languages(model, walks) -> None:
+    """Whisper's rule, once per file and not per window: a file of a multilingual model whose ``language`` is None takes the language
+    detected on its first 30 seconds.  All of ``walks`` that still wait for theirs go through ONE ``detect_language`` call."""
+    waiting = [w for w in walks if w.multilingual and w.language is None]
+    if not waiting:
+        return
+    tokenizer = waiting[0].tokenizer
+    tokens, _ = detect_language(model, torch.stack([w.first_window() for w in waiting]), tokenizer)
+    for w, token in zip(waiting, tokens.tolist()):
+        w.language = tokenizer.all_language_codes[tokenizer.all_language_tokens.index(token)]
 
 
 def transcribe(model, audio, **kw):
@@ -1206,7 +1419,10 @@ def transcribe(model, audio, **kw):
     skip, segments cut at consecutive timestamp pairs, ``seek`` advanced to the last timestamp or by the whole window; the prompt of
     the next window is the text so far, reset after a window decoded above temperature 0.5.  Keywords: ``temperature`` (one or a tuple,
     default 0.0 .. 1.0 in steps of 0.2), ``compression_ratio_threshold`` (2.4), ``logprob_threshold`` (-1.0), ``no_speech_threshold``
-    (0.6), ``condition_on_previous_text`` (True), ``initial_prompt``, ``verbose``, ``tokenizer``; the rest are ``DecodingOptions``."""
+    (0.6), ``condition_on_previous_text`` (True), ``initial_prompt``, ``verbose``, ``tokenizer``; the rest are ``DecodingOptions``.
+    With a multilingual model ``language`` is a code, name or alias, or None: the language detected on the file's first 30 seconds
+    (``detect_language``, once per file) — every window decodes in it and the result's ``"language"`` is its code; ``task`` is
+    "transcribe" or "translate".  An English-only model ignores both: ``"language"`` is "en"."""
     walk = _FileWalk(model, audio, **kw)
     while True:
         request = walk.next_request()
@@ -1219,16 +1435,17 @@ def transcribe_many(model, audios, *, files_in_flight: int = FILES_IN_FLIGHT, **
     """``transcribe()`` of every item of ``audios`` (keywords as ``transcribe``'s, the same for all), with the current windows of up
     to ``files_in_flight`` files decoded together by ``decode_many``: a file's windows stay in order, files are independent.  After a
     round every file takes its result (a fallback is simply its request of the next round); a file that ends hands its slot to the
-    next one.  Returns the files' dicts in input order, each equal to ``transcribe()``'s."""
+    next one.  The files that take a slot in the same round and name no language (a multilingual model, ``language=None``) have their
+    first windows detected in one ``detect_language`` call (a file without content never takes a slot: its language is detected by a
+    call of its own when its result is taken).  Returns the files' dicts in input order, each equal to ``transcribe()``'s."""
     if files_in_flight < 1:
         raise ValueError(f"files_in_flight = {files_in_flight}: at least one file")
     audios = list(audios)
     out: List[Optional[Dict[str, object]]] = [None] * len(audios)
     waiting = iter(range(len(audios)))
-    slots: List[Optional[tuple]] = [None] * files_in_flight          # (file index, its walk, its request)
 
     def seat(walk_of_slot):
-        """the slot's file with its next request; a file without one is finished and the next waiting file takes the slot"""
+        """the slot's (file index, its walk) while it has windows left; a finished file hands the slot to the next waiting one"""
         while True:
             if walk_of_slot is None:
                 i = next(waiting, None)
@@ -1236,18 +1453,23 @@ def transcribe_many(model, audios, *, files_in_flight: int = FILES_IN_FLIGHT, **
                     return None
                 walk_of_slot = (i, _FileWalk(model, audios[i], **kw))
             i, walk = walk_of_slot
-            request = walk.next_request()
-            if request is not None:
-                return i, walk, request
+            if not walk.finished:
+                return walk_of_slot
             out[i] = walk.result()
             walk_of_slot = None
-    slots = [seat(None) for _ in slots]
+
+    def seat_all(slots):
+        slots = [seat(s) for s in slots]
+        _detect_file_languages(model, [s[1] for s in slots if s is not None])          # the newly seated files' languages, together
+        return slots
+    slots = seat_all([None] * files_in_flight)
     while any(s is not None for s in slots):
         live = [s for s in slots if s is not None]
-        results = decode_many(model, [s[2][0] for s in live], [s[2][1] for s in live])
-        for (i, walk, _), result in zip(live, results):
+        requests = [walk.next_request() for _, walk in live]
+        results = decode_many(model, [r[0] for r in requests], [r[1] for r in requests])
+        for (_, walk), result in zip(live, results):
             walk.accept(result)
-        slots = [seat(s[:2]) if s is not None else None for s in slots]
+        slots = seat_all(slots)
     return out
 
 

@@ -1355,6 +1355,15 @@ typedef struct hirest_whisper_row_ctl {
 int hirest_whisper_step_tail_rows(const float* logits, int64_t ldx, int32_t R, int32_t V, int32_t call, int64_t ld_tokens,
                                   const hirest_whisper_tail_params* params, hirest_whisper_row_ctl* ctl, hirest_whisper_row_state* state,
                                   int32_t* next_ids, int32_t* tokens, float* logprobs, int32_t* done_host, void* stream);
+/* Language detection: for R rows of logits [R, V] (row stride ldx >= V), the softmax over the L language columns alone.
+ * language_ids: L device ints, ascending, 1 <= L <= 128 (the tokenizer's language tokens).  lang_token[r] = the id with the largest
+ * logit (the lower id on ties); probs[r * L + j] = exp(x[ids[j]] - max) / sum_j exp(x[ids[j]] - max).  One wave per row; the sum runs
+ * over a lane's entries j = lane, lane + 64 in that order and then over the xor-shuffle tree of the tail, so a row's bits do not
+ * depend on R or on its neighbours.  The sum and the quotients are taken in double and each probability is rounded to fp32 once: a
+ * row sums to 1 within those roundings, not within what L - 1 fp32 additions lose.  Only the L listed columns of a row are read; an id outside [0, V) counts as absent (its
+ * probability is 0, and lang_token is -1 when every id is).  Logits are expected finite. */
+int hirest_whisper_language_tail(const float* logits, int64_t ldx, int32_t R, int32_t V, const int32_t* language_ids, int32_t L,
+                                 int32_t* lang_token, float* probs, void* stream);
 /* out[r * V + v] = the generator's 24 bits for (seed, serial, row r, token v) (tests) */
 int hirest_whisper_gumbel_bits(uint32_t seed, uint32_t serial, int32_t R, int32_t V, uint32_t* out, void* stream);
 

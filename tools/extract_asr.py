@@ -6,6 +6,8 @@ reference's ``extraction/whisper_ASR/extract_ASR.py``, our own code against our 
 
 ``--model`` is a local OpenAI ``.pt`` checkpoint or a Hugging Face model directory, never a model name: nothing is downloaded.
 ``--tokenizer`` is a directory with ``vocab.json`` and ``merges.txt`` (default: the model directory).
+``--language`` is a language's name or code (default English, as the reference's), or ``auto`` / ``"Auto detection"``: a multilingual
+model then detects each file's language on its first 30 seconds.  ``--task translate`` writes English subtitles for any language.
 """
 import argparse
 import os
@@ -19,12 +21,25 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hirest_amd import whisper  # noqa: E402
 
 
+def language_argument(value: str):
+    """``--language``: "auto" / "Auto detection" (the reference's menu entry) -> None, anything else -> its language code"""
+    if value.strip().lower() in ("auto", "auto detection"):
+        return None
+    try:
+        return whisper.language_code(value)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--model", type=str, required=True, help="local .pt checkpoint or Hugging Face model directory")
     ap.add_argument("--audio_dir", type=str, required=True)
     ap.add_argument("--asr_dir", type=str, required=True)
     ap.add_argument("--tokenizer", type=str, default=None, help="directory with vocab.json and merges.txt (default: --model)")
+    ap.add_argument("--language", type=language_argument, default="en",
+                    help="a language's name or code, or 'auto' / 'Auto detection' (multilingual models: detected per file); default English")
+    ap.add_argument("--task", type=str, default="transcribe", choices=["transcribe", "translate"])
     ap.add_argument("--device", type=str, default="cuda")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--files_in_flight", type=int, default=whisper.FILES_IN_FLIGHT,
@@ -40,7 +55,7 @@ def main(argv=None):
     # the reference's option block.  Its first temperature is 0.15, so every window is sampled (best_of candidates) and the beam options
     # are never used: transcribe() drops them above temperature 0.
     temperature, temperature_increment_on_fallback = 0.15, 0.2
-    options = dict(language="English", task="transcribe", best_of=5, beam_size=5, patience=1.0, length_penalty=None, suppress_tokens="-1",
+    options = dict(language=args.language, task=args.task, best_of=5, beam_size=5, patience=1.0, length_penalty=None, suppress_tokens="-1",
                    initial_prompt=None, condition_on_previous_text=True, fp16=True, compression_ratio_threshold=2.4, logprob_threshold=-1.0,
                    no_speech_threshold=0.6, seed=args.seed)
     temperatures = tuple(np.arange(temperature, 1.0 + 1e-6, temperature_increment_on_fallback))

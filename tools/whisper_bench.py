@@ -5,9 +5,11 @@ front end, the convolution stem and the blocks (each timed on its own, a device 
 encoder's rate as a fraction of the 157-TFLOP/s fp32 MFMA peak DESIGN.md uses for the joint model.  Operations are counted from the
 shapes.  Each figure is the median with the min .. max spread over the repeats.  The decode leg: W windows through one
 run of the decoding loop (``decode_many``) against W one-window runs of the same loop (W sequential ``decode`` calls) at small.en's
-decoder shape.
+decoder shape.  The detect leg: ``detect_language`` of W windows at multilingual small's decoder shape and the pieces of
+that call; the step leg: the one ``hirest_whisper_decode_step_rows`` call inside it, alone.
 
-    python tools/whisper_bench.py [--repeats 7] [--warmup 2] [--batches 1 8] [--legs encoder decode] [--windows 1 2 4 8 16]
+    python tools/whisper_bench.py [--repeats 7] [--warmup 2] [--batches 1 8] [--legs encoder decode detect step] [--windows 1 2 4 8 16]
+                                  [--detect_windows 1 16]
 """
 import argparse
 import json
@@ -92,19 +94,104 @@ def decode_leg(a, dev):
     return table
 
 
+def step_rows_setup(model, xa, sot):
+    """what one ``hirest_whisper_decode_step_rows`` call of <|startoftranscript|> at position 0 needs, row w against window w: the work
+    inside ``detect_language``, set up outside the timed call.  Uses nothing that ``detect_language`` brought, so the same function times
+    the step on a commit without it."""
+    import ctypes as C
+    from hirest_amd import _lib, ops
+    dec, dev, R = model.decoder, model.device, int(xa.shape[0])
+    kc = whisper.KVCache(dec, xa, torch.arange(R, dtype=torch.int32), 1, per_row=True)
+    ctl = whisper.new_row_ctl([(0, 0, 1, 0, 0, 0.0)] * R, dev)
+    ids = torch.full((R,), sot, dtype=torch.int32, device=dev)
+    lib, desc = _lib.load(), C.byref(dec._w()["desc"])
+
+    def step():
+        _lib.check(lib.hirest_whisper_decode_step_rows(desc, R, ctl.data_ptr(), ids.data_ptr(), kc.k_ptrs, kc.v_ptrs, kc.T_max, kc.x_ptrs,
+                                                       kc.n_windows, kc.Tk, kc.row_window.data_ptr(), kc.logits.data_ptr(), kc.ws.data_ptr(),
+                                                       kc.ws.numel(), ops.stream_ptr()), "hirest_whisper_decode_step_rows")
+    return step, (kc, ctl, ids)
+
+
+def small_decoder_model(dev, languages):
+    """multilingual small's decoder shape (768 wide, 12 heads, 12 layers, 1500 audio positions, 51865 tokens) with random weights
+    behind a one-layer encoder that is not run; ``languages`` language tokens in the slots after <|startoftranscript|>"""
+    cfg = synth._dec_config(768, 12, 12, 1500, 51865, 448)
+    eot = 50256
+    sd = synth.whisper_decoder_state_dict(cfg, 83, eot, 0.0)
+    sd.update({"encoder." + k: v for k, v in synth.whisper_encoder_state_dict({**cfg, "encoder_layers": 1}, 73).items()})
+    sp = synth.whisper_special_tokens(eot)
+    if languages:
+        sp.update({f"<|{code}|>": eot + 2 + i for i, code in enumerate(list(whisper.LANGUAGES)[:languages])})
+    tok = whisper.Tokenizer(*synth.whisper_vocab(eot), sp, language="en" if languages else None, task="transcribe" if languages else None)
+    return whisper.Whisper({**cfg, "encoder_layers": 1}, sd, tok).to(dev), cfg
+
+
+def detect_leg(a, dev):
+    """``detect_language`` of W windows' encoder states at multilingual small's decoder shape, 99 languages, per call and per window;
+    beside it the pieces of the same call, each timed on its own with a device synchronise closing every timed window: the cross key /
+    value projection of the W windows (``TextDecoder.cross_kv``: 12 GEMMs of [W * 1500, 768] x [768, 1536]), ONE
+    ``hirest_whisper_decode_step_rows`` call at R = W — the decoder pass itself — and ``hirest_whisper_language_tail``.  What is left
+    of the call after the three is the host: the cache and workspace allocations, the records' upload and the read-back."""
+    from hirest_amd import _lib, ops
+    model, cfg = small_decoder_model(dev, 99)
+    tok, lib = model.tokenizer, _lib.load()
+    xa_all = synth.whisper_audio_states(cfg, max(a.detect_windows), 7).to(dev)
+    print(f"detect: multilingual small's decoder shape, 99 languages, medians of {a.repeats} after {a.warmup} warm-up calls (min .. max)")
+    table = {}
+    for W in a.detect_windows:
+        xa = xa_all[:W]
+        tokens, probs = whisper.detect_language(model, xa)
+        assert tokens.shape == (W,) and all(abs(sum(p.values()) - 1.0) < 1e-5 for p in probs)
+        whole = timed(lambda: whisper.detect_language(model, xa), a.repeats, a.warmup)
+        cross = timed(lambda: model.decoder.cross_kv(xa), a.repeats, a.warmup)
+        step, keep = step_rows_setup(model, xa, tok.sot)
+        step_t = timed(step, a.repeats, a.warmup)
+        logits, L = keep[0].logits, len(tok.all_language_tokens)
+        ids = torch.tensor(tok.all_language_tokens, dtype=torch.int32, device=dev)
+        out_t, out_p = torch.empty(W, dtype=torch.int32, device=dev), torch.empty((W, L), dtype=torch.float32, device=dev)
+        tail = timed(lambda: _lib.check(lib.hirest_whisper_language_tail(logits.data_ptr(), model.decoder.vocab_padded, W, model.decoder.vocab,
+                                                                         ids.data_ptr(), L, out_t.data_ptr(), out_p.data_ptr(), ops.stream_ptr()),
+                                        "hirest_whisper_language_tail"), a.repeats, a.warmup)
+        med = statistics.median
+        rest = med(whole) - med(cross) - med(step_t) - med(tail)
+        print(f"  W = {W:2d}: detect_language {spread(whole)} = {med(whole) / W * 1e3:.3f} ms per window")
+        print(f"          cross_kv {spread(cross)}, decode_step_rows at R = W {spread(step_t)}, language_tail {spread(tail, 1e6, 'us')}, "
+              f"the rest (host) {rest * 1e3:.3f} ms")
+        table[str(W)] = {"detect_ms": [round(x * 1e3, 4) for x in whole], "detect_ms_per_window": med(whole) / W * 1e3,
+                         "cross_kv_ms": [round(x * 1e3, 4) for x in cross], "step_rows_ms": [round(x * 1e3, 4) for x in step_t],
+                         "language_tail_us": [round(x * 1e6, 3) for x in tail], "rest_ms": rest * 1e3}
+    return table
+
+
+def step_leg(a, dev):
+    """one ``hirest_whisper_decode_step_rows`` call at R = W alone (``step_rows_setup``): runs on a commit without ``detect_language``"""
+    model, cfg = small_decoder_model(dev, 0)
+    xa_all = synth.whisper_audio_states(cfg, max(a.detect_windows), 7).to(dev)
+    table = {}
+    for W in a.detect_windows:
+        step, keep = step_rows_setup(model, xa_all[:W], model.tokenizer.sot)
+        t = timed(step, a.repeats, a.warmup)
+        print(f"step: hirest_whisper_decode_step_rows at R = W = {W:2d}, position 0, T_max 1: {spread(t)}")
+        table[str(W)] = {"step_rows_ms": [round(x * 1e3, 4) for x in t]}
+    return table
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8])
-    ap.add_argument("--legs", nargs="+", choices=["encoder", "decode"], default=["encoder", "decode"])
+    ap.add_argument("--legs", nargs="+", choices=["encoder", "decode", "detect", "step"], default=["encoder", "decode"])
     ap.add_argument("--windows", type=int, nargs="+", default=[1, 2, 4, 8, 16], help="windows per decode_many() call of the decode leg")
+    ap.add_argument("--detect_windows", type=int, nargs="+", default=[1, 16], help="windows per detect_language() call of the detect leg")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("whisper_bench needs an MI355X: there is nothing to measure without one")
     dev = torch.device("cuda:0")
     if "encoder" not in a.legs:
-        print(json.dumps({"device": torch.cuda.get_device_name(0), "decode": decode_leg(a, dev)}))
+        legs = {"decode": decode_leg, "detect": detect_leg, "step": step_leg}
+        print(json.dumps({"device": torch.cuda.get_device_name(0), **{leg: legs[leg](a, dev) for leg in a.legs}}))
         return
     cfg = synth.WHISPER_SMALL_EN
     enc = whisper.AudioEncoder(cfg, synth.whisper_encoder_state_dict(cfg, 73)).to(dev)
@@ -132,8 +219,9 @@ def main():
                                      "windows_per_s": 1.0 / per_window, "front_end_share": t_front / per_window,
                                      "encoder_tflops": B * (stem_flop + block_flop) / t_whole / 1e12,
                                      "fraction_of_fp32_mfma_peak": B * (stem_flop + block_flop) / t_whole / FP32_MFMA_PEAK}
-    if "decode" in a.legs:
-        result["decode"] = decode_leg(a, dev)
+    for leg, fn in (("decode", decode_leg), ("detect", detect_leg), ("step", step_leg)):
+        if leg in a.legs:
+            result[leg] = fn(a, dev)
     print(json.dumps(result))
 
 
