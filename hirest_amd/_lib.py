@@ -135,7 +135,15 @@ class WhisperTailParams(C.Structure):
                [("temperature", C.c_float), ("seed", C.c_uint32), ("serial", C.c_uint32), ("suppress_mask", C.c_void_p)]
 
 
-WHISPER_ROW_STATE_WORDS = 8      # hirest_whisper_row_state: n_sampled, last, penult, last_timestamp, completed | sum_logprobs, no_speech_prob, last_logprob
+class DtwProblem(C.Structure):
+    """hirest_dtw_problem (include/hirest_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("N", C.c_int32), ("M", C.c_int32), ("negate", C.c_int32), ("reserved", C.c_int32),
+                ("path", C.c_void_p), ("path_len", C.c_void_p), ("cost", C.c_void_p), ("ldc", C.c_int64)]
+
+
+DTW_MAX_N, DTW_MAX_M = 256, 4096     # HIREST_DTW_MAX_N, HIREST_DTW_MAX_M
+
+WHISPER_ROW_STATE_WORDS = 8     # hirest_whisper_row_state: n_sampled, last, penult, last_timestamp, completed | sum_logprobs, no_speech_prob, last_logprob
 WHISPER_ROW_CTL_WORDS = 8        # hirest_whisper_row_ctl: position, step, max_steps, draw_row, seed (uint32) | temperature (float) | 2 reserved
 
 
@@ -472,6 +480,14 @@ _SIGNATURES = {
                                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hirest_whisper_language_tail": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                C.c_void_p]),
+    "hirest_whisper_alignment_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "hirest_whisper_alignment_matrix": (C.c_int, [C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32,
+                                                  C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hirest_median_filter_mean_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                C.c_void_p]),
+    "hirest_dtw_workspace_bytes": (C.c_size_t, [C.POINTER(DtwProblem), C.c_int32]),
+    "hirest_dtw_f32": (C.c_int, [C.POINTER(DtwProblem), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hirest_vision_workspace_bytes": (C.c_size_t, [C.POINTER(VisionTower), C.c_int32]),
     "hirest_vision_forward": (C.c_int, [C.POINTER(VisionTower), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),

@@ -10,6 +10,7 @@ tokens, 0.34 TFLOP per 30 s window) and the part Whisper's users call directly::
 
     whisper.load_model / model.decode / whisper.transcribe / utils.write_srt  ->  the same names here (sampling branch; no beam search)
     whisper.detect_language / tokenizer.LANGUAGES / TO_LANGUAGE_CODE          ->  the same names here
+    transcribe(word_timestamps=True) / whisper.timing.find_alignment, dtw ..  ->  the same names here
 
 Whisper is not under the reference tree; the front end restates ``whisper/audio.py`` and the encoder ``whisper/model.py::AudioEncoder``
 from the published definitions, pinned against ``transformers``' WhisperFeatureExtractor / WhisperEncoder (tests/golden/whisper_*.npz).
@@ -37,6 +38,7 @@ import functools
 import json
 import os
 import re
+import string
 import types
 import wave
 import zlib
@@ -58,6 +60,9 @@ N_SAMPLES = CHUNK_LENGTH * SAMPLE_RATE          # 480000 samples in a 30-second 
 N_FRAMES = N_SAMPLES // HOP_LENGTH              # 3000 frames in a mel spectrogram input
 
 _NAME = "hirest_amd.whisper"
+TOKENS_PER_SECOND = SAMPLE_RATE // HOP_LENGTH // 2      # 50 encoder positions (and timestamp tokens) per second
+PREPEND_PUNCTUATIONS = "\"'“¿([{-"                       # whisper.transcribe's defaults
+APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
 _TIMESTAMP = re.compile(r"<\|\d+\.\d\d\|>")
 
 
@@ -575,9 +580,10 @@ class TextDecoder(_FrozenWeights):
         with torch.cuda.device(self.device):
             return [_linear(rows, c[f"ckv_w.{i}"], c[f"ckv_b.{i}"]).view(W, Tk, 2 * D) for i in range(self.layers)]
 
-    def _sequences(self, tokens: torch.Tensor, cross_kv, Tk: int, keep=None):
+    def _sequences(self, tokens: torch.Tensor, cross_kv, Tk: int, keep=None, keep_cross_q=None):
         """[B, T] tokens (sequence b against window b of cross_kv) -> [B * T, D] states before ``ln``; ``keep(i, qkv)`` sees every layer's
-        packed q | k | v rows (the prefill takes its cache rows from them)"""
+        packed q | k | v rows (the prefill takes its cache rows from them), ``keep_cross_q(i, q)`` every layer's cross-attention query
+        rows ``[B * T, D]`` (the word alignment takes its attention weights from them); without them nothing is kept"""
         c, lib = self._w(), _lib.load()
         B, T = tokens.shape
         D, H, dev = self.width, self.heads, self.device
@@ -596,6 +602,8 @@ class TextDecoder(_FrozenWeights):
             x = _linear(att, c[p + "attn.out.weight"], c[p + "attn.out.bias"], resid=x)
             q = _ln_linear(x, c[p + "cross_attn_ln.weight"], c[p + "cross_attn_ln.bias"], c[p + "cross_attn.query.weight"],
                            c[p + "cross_attn.query.bias"])
+            if keep_cross_q is not None:
+                keep_cross_q(i, q)
             kv = cross_kv[i]
             _lib.check(lib.hirest_attention_f32_qkv(q.data_ptr(), D, kv.data_ptr(), kv.data_ptr() + 4 * D, 2 * D, att.data_ptr(), B, T, Tk, H, 64,
                                                     0.125, 0.0, 0.0, ops.stream_ptr()), "hirest_attention_f32_qkv")
@@ -693,6 +701,7 @@ TO_LANGUAGE_CODE = {
     "burmese": "my", "valencian": "ca", "flemish": "nl", "haitian": "ht", "letzeburgesch": "lb", "pushto": "ps", "panjabi": "pa",
     "moldavian": "ro", "moldovan": "ro", "sinhalese": "si", "castilian": "es", "mandarin": "zh"}
 _LANGUAGE_TOKEN = re.compile(r"<\|([a-z]{2,3})\|>")
+_UNICODE_SPLIT_LANGUAGES = frozenset(("zh", "ja", "th", "lo", "my", "yue"))      # written without spaces: words are unicode pieces
 
 
 def language_code(language: str) -> str:
@@ -848,6 +857,41 @@ class Tokenizer:
     def decode_with_timestamps(self, ids) -> str:
         """timestamp tokens rendered as ``<|1.08|>`` (0.02 s per token)"""
         return self._decode(ids, True)
+
+    def split_to_word_tokens(self, tokens):
+        """Whisper's ``split_to_word_tokens``: ``(words, word_tokens)``.  zh, ja, th, lo, my and yue split on unicode boundaries, every
+        other language (and no language) on spaces."""
+        if self.language in _UNICODE_SPLIT_LANGUAGES:
+            return self.split_tokens_on_unicode(tokens)
+        return self.split_tokens_on_spaces(tokens)
+
+    def split_tokens_on_unicode(self, tokens):
+        """a piece ends where the tokens so far decode to complete characters (no U+FFFD that the whole text does not have there)"""
+        full = self.decode_with_timestamps(tokens)
+        words, word_tokens, current, offset = [], [], [], 0
+        for token in tokens:
+            current.append(int(token))
+            decoded = self.decode_with_timestamps(current)
+            if "\ufffd" not in decoded or full[offset + decoded.index("\ufffd")] == "\ufffd":
+                words.append(decoded)
+                word_tokens.append(current)
+                current = []
+                offset += len(decoded)
+        return words, word_tokens
+
+    def split_tokens_on_spaces(self, tokens):
+        """the unicode pieces joined into words: a new word starts at a piece that starts with a space, is punctuation alone, or is a
+        special token"""
+        words, word_tokens = [], []
+        for piece, piece_tokens in zip(*self.split_tokens_on_unicode(tokens)):
+            special = piece_tokens[0] >= self.eot
+            if special or piece.startswith(" ") or piece.strip() in string.punctuation or not words:
+                words.append(piece)
+                word_tokens.append(piece_tokens)
+            else:
+                words[-1] += piece
+                word_tokens[-1].extend(piece_tokens)
+        return words, word_tokens
 
     @functools.cached_property
     def non_speech_tokens(self):
@@ -1236,6 +1280,27 @@ class Whisper(nn.Module):
         self.dims = {"n_mels": e.n_mels, "n_audio_ctx": e.ctx, "n_audio_state": e.width, "n_audio_head": e.heads, "n_audio_layer": e.layers,
                      "n_vocab": d.vocab, "n_text_ctx": d.ctx, "n_text_state": d.width, "n_text_head": d.heads, "n_text_layer": d.layers}
         self.tokenizer = tokenizer
+        # The heads whose cross-attention the word alignment reads (``find_alignment``): every head of the last half of the layers,
+        # Whisper's own default.  The released checkpoints' tuned lists are not shipped: ``set_alignment_heads`` takes them.
+        self.alignment_heads = torch.zeros((d.layers, d.heads), dtype=torch.bool)
+        self.alignment_heads[d.layers // 2:] = True
+
+    def set_alignment_heads(self, mask_or_pairs) -> None:
+        """Replace ``alignment_heads``: a bool mask ``[layers, heads]`` or a sequence of (layer, head) pairs"""
+        d = self.decoder
+        if torch.is_tensor(mask_or_pairs) and mask_or_pairs.dtype == torch.bool or isinstance(mask_or_pairs, np.ndarray) and mask_or_pairs.dtype == bool:
+            mask = torch.as_tensor(mask_or_pairs).cpu().clone()
+            if tuple(mask.shape) != (d.layers, d.heads):
+                raise ValueError(f"a mask of shape {tuple(mask.shape)}: [{d.layers}, {d.heads}] expected")
+        else:
+            mask = torch.zeros((d.layers, d.heads), dtype=torch.bool)
+            for layer, head in mask_or_pairs:
+                if not (0 <= int(layer) < d.layers and 0 <= int(head) < d.heads):
+                    raise ValueError(f"(layer {layer}, head {head}): the decoder has {d.layers} layers of {d.heads} heads")
+                mask[int(layer), int(head)] = True
+        if not bool(mask.any()):
+            raise ValueError("no alignment head selected")
+        self.alignment_heads = mask
 
     @property
     def device(self) -> torch.device:
@@ -1292,7 +1357,9 @@ class _FileWalk:
     def __init__(self, model, audio, *, temperature: Union[float, Tuple[float, ...]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
                  compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
                  no_speech_threshold: Optional[float] = 0.6, condition_on_previous_text: bool = True, initial_prompt: Optional[str] = None,
-                 verbose=None, **decode_options):
+                 verbose=None, word_timestamps: bool = False, prepend_punctuations: str = PREPEND_PUNCTUATIONS,
+                 append_punctuations: str = APPEND_PUNCTUATIONS, **decode_options):
+        self.word_timestamps, self.punctuations = bool(word_timestamps), (prepend_punctuations, append_punctuations)
         self.tokenizer = tokenizer = decode_options.pop("tokenizer", None) or getattr(model, "tokenizer", None)
         if tokenizer is None:
             raise ValueError("no tokenizer: load_model(path, tokenizer=...) or transcribe(..., tokenizer=...)")
@@ -1365,6 +1432,7 @@ class _FileWalk:
                 not (logprob_threshold is not None and result.avg_logprob > logprob_threshold):
             self.seek = seek + segment_size                           # silence: skip the window
             return
+        n_before = len(self.all_segments)
         is_ts = [t >= tb for t in tokens]
         single_ending = is_ts[-2:] == [False, True]
         cuts = [i + 1 for i in range(len(tokens) - 1) if is_ts[i] and is_ts[i + 1]]
@@ -1389,6 +1457,19 @@ class _FileWalk:
             seek += segment_size
         if seek <= window_start:                                      # (a last pair that closes at <|0.00|>, possible only without the
             seek = window_start + segment_size                        #  monotonic rule, would decode the same window for ever)
+        if self.word_timestamps and len(self.all_segments) > n_before:
+            # One alignment per settled window, on the window's own states when decode() handed them back.  ``seek`` stays where the
+            # timestamp tokens put it (Whisper moves it to the last word's end; here every field but "words" is what it is without).
+            states = result.audio_features
+            if states is None:
+                states = pad_or_trim(self.mel[:, window_start:window_start + N_FRAMES], N_FRAMES)
+            tok = self.tokenizer
+            if self.multilingual:
+                task = self.decode_options.get("task", "transcribe")
+                tok = tok.with_language(self.language, task if task != "transcribe" else tok.task or "transcribe")
+            # (a file's last sliver of one frame still has the one key its words are put at)
+            add_word_timestamps(self.all_segments[n_before:], self.model, tok, states, max(segment_size, 2), prepend_punctuations=self.punctuations[0],
+                                append_punctuations=self.punctuations[1])
         self.seek = seek                                              # (after the segments: they carry the window's own seek)
         if not self.condition_on_previous_text or result.temperature > 0.5:
             self.reset_since = len(self.all_tokens)
@@ -1420,6 +1501,10 @@ def transcribe(model, audio, **kw):
     the next window is the text so far, reset after a window decoded above temperature 0.5.  Keywords: ``temperature`` (one or a tuple,
     default 0.0 .. 1.0 in steps of 0.2), ``compression_ratio_threshold`` (2.4), ``logprob_threshold`` (-1.0), ``no_speech_threshold``
     (0.6), ``condition_on_previous_text`` (True), ``initial_prompt``, ``verbose``, ``tokenizer``; the rest are ``DecodingOptions``.
+    ``word_timestamps=True`` (with ``prepend_punctuations`` / ``append_punctuations``, Whisper's defaults): every settled window that
+    yielded segments is aligned once (``add_word_timestamps``: one teacher-forced pass) and each of its segments gains
+    ``"words": [{"word", "start", "end", "probability"}]``; ``seek``, tokens, text and every other field are what they are without the
+    option — Whisper moves ``seek`` to the last word's end, which is deliberately not done here.
     With a multilingual model ``language`` is a code, name or alias, or None: the language detected on the file's first 30 seconds
     (``detect_language``, once per file) — every window decodes in it and the result's ``"language"`` is its code; ``task`` is
     "transcribe" or "translate".  An English-only model ignores both: ``"language"`` is "en"."""
@@ -1493,3 +1578,239 @@ def write_srt(segments, file) -> None:
 
 
 utils = types.SimpleNamespace(write_srt=write_srt, format_timestamp=format_timestamp)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# word-level timestamps (whisper/timing.py's names)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+@dataclasses.dataclass
+class WordTiming:
+    word: str
+    tokens: List[int]
+    start: float
+    end: float
+    probability: float
+
+
+def median_filter(x: torch.Tensor, width: int) -> torch.Tensor:
+    """``whisper.timing.median_filter``: a median filter of odd ``width`` (at most 31) along the last axis of a device tensor, reflect
+    padding of ``width // 2`` on both sides; a last axis of at most ``width // 2`` elements comes back unfiltered (Whisper's early
+    return).  fp32; the median is selected, so the values are exact."""
+    if width < 1 or width % 2 != 1:
+        raise ValueError(f"width {width}: an odd filter width expected")
+    dev = _gpu_device(x.device, "median_filter")
+    w = x.to(torch.float32).contiguous()
+    n = int(w.shape[-1])
+    rows = w.numel() // max(n, 1)
+    if w.numel() == 0:
+        return w.clone()
+    out = torch.empty_like(w)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().hirest_median_filter_mean_f32(w.data_ptr(), 1, rows, n, int(width), 0, rows, out.data_ptr(), ops.stream_ptr()),
+                   "hirest_median_filter_mean_f32")
+    return out
+
+
+def dtw_many(xs, *, negate: bool = False, return_cost: bool = False):
+    """``dtw`` of several matrices in one launch (one workgroup each): a list of ``(text_indices, time_indices)``, with ``return_cost``
+    of ``(text_indices, time_indices, cost [N, M] on the device)``.  ``negate``: of ``-x`` without forming it."""
+    lib = _lib.load()
+    if not xs:
+        return []
+    dev = _gpu_device(xs[0].device, "dtw")
+    xs = [x if x.dtype == torch.float32 and x.stride(-1) == 1 else x.to(torch.float32).contiguous() for x in xs]
+    probs = (_lib.DtwProblem * len(xs))()
+    keep = []
+    for p, x in zip(probs, xs):
+        if x.ndim != 2 or not (1 <= x.shape[0] <= _lib.DTW_MAX_N and 1 <= x.shape[1] <= _lib.DTW_MAX_M):
+            raise ValueError(f"dtw of a matrix of shape {tuple(x.shape)}: [N <= {_lib.DTW_MAX_N}, M <= {_lib.DTW_MAX_M}] expected")
+        N, M = int(x.shape[0]), int(x.shape[1])
+        path = torch.empty((N + M + 1, 2), dtype=torch.int32, device=dev)          # the last row's first word: the path's length
+        cost = torch.empty((N, M), dtype=torch.float32, device=dev) if return_cost else None
+        p.x, p.ldx, p.N, p.M, p.negate = x.data_ptr(), x.stride(0) if N > 1 else M, N, M, int(negate)
+        p.path, p.path_len = path.data_ptr(), path[N + M].data_ptr()
+        p.cost, p.ldc = (cost.data_ptr(), M) if return_cost else (None, 0)
+        keep.append((path, cost))
+    with torch.cuda.device(dev):
+        ws = torch.empty((int(lib.hirest_dtw_workspace_bytes(probs, len(xs))),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.hirest_dtw_f32(probs, len(xs), ws.data_ptr(), ws.numel(), ops.stream_ptr()), "hirest_dtw_f32")
+        out = []
+        for path, cost in keep:
+            host = path.cpu().numpy()                                              # one read-back per problem: the path and its length
+            steps = host[:int(host[-1, 0])]
+            out.append((steps[:, 0].copy(), steps[:, 1].copy()) + ((cost,) if return_cost else ()))
+    return out
+
+
+def dtw(x: torch.Tensor):
+    """``whisper.timing.dtw``: the minimum-cost monotone path through ``x [N, M]`` (a device tensor, N <= 256, M <= 4096) as
+    ``(text_indices, time_indices)``, numpy arrays.  Recurrence and backtrace run on the device (``hirest_dtw_f32``); ties go the way
+    Whisper's go (diagonal only when strictly smallest, then up only when strictly smallest, else left)."""
+    return dtw_many([x])[0]
+
+
+def alignment_matrix(queries, cross_kv, pairs, n_keys: int, *, heads: int, qk_scale: float = 1.0, medfilt_width: int = 7, row0: int = 0,
+                     n_rows: Optional[int] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hirest_whisper_alignment_matrix`` for one window: ``queries`` per layer the cross-attention query rows ``[T, D]``, ``cross_kv``
+    per layer the window's ``key | value`` rows ``[Tk, 2 D]``, ``pairs`` the selected (layer, head) -> fp32 ``[n_rows, n_keys]``: the
+    selected heads' softmax over the first ``n_keys`` keys, normalised per key over the T tokens, median-filtered along the keys,
+    averaged over the heads."""
+    lib = _lib.load()
+    layers, T, Tk = len(queries), int(queries[0].shape[0]), int(cross_kv[0].shape[0])
+    dev = _gpu_device(queries[0].device, "alignment_matrix")
+    n_rows = T - row0 if n_rows is None else n_rows
+    pairs = [(int(l), int(h)) for l, h in pairs]
+    for t in list(queries) + list(cross_kv):
+        if t.dtype != torch.float32 or t.stride(-1) != 1:
+            raise ValueError("fp32 rows with unit stride expected")
+    P = C.c_void_p * layers
+    q_ptrs, kv_ptrs = P(*(t.data_ptr() for t in queries)), P(*(t.data_ptr() for t in cross_kv))
+    sel = (C.c_int32 * (2 * len(pairs)))(*(v for pair in pairs for v in pair))
+    need = int(lib.hirest_whisper_alignment_workspace_bytes(len(pairs), T, n_keys))
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+        out = torch.empty((max(n_rows, 0), max(n_keys, 0)), dtype=torch.float32, device=dev)
+        _lib.check(lib.hirest_whisper_alignment_matrix(q_ptrs, queries[0].stride(0), kv_ptrs, layers, heads, Tk, sel, len(pairs), T, n_keys,
+                                                       float(qk_scale), int(medfilt_width), row0, n_rows, out.data_ptr(), workspace.data_ptr(),
+                                                       workspace.numel(), ops.stream_ptr()), "hirest_whisper_alignment_matrix")
+    return out
+
+
+def _split_words(tokenizer: Tokenizer, text_tokens: List[int], segment_lengths=None):
+    """Whisper's ``split_to_word_tokens(text_tokens + [eot])`` — or, given the segments' token counts, the same per segment, so that
+    no word spans two segments"""
+    if not segment_lengths:
+        return tokenizer.split_to_word_tokens(list(text_tokens) + [tokenizer.eot])
+    if sum(segment_lengths) != len(text_tokens):
+        raise ValueError(f"segment lengths {list(segment_lengths)} for {len(text_tokens)} text tokens")
+    words, word_tokens, at = [], [], 0
+    for k, n in enumerate(segment_lengths):
+        piece = list(text_tokens[at:at + n]) + ([tokenizer.eot] if k == len(segment_lengths) - 1 else [])
+        at += n
+        if piece:
+            w, t = tokenizer.split_to_word_tokens(piece)
+            words += w
+            word_tokens += t
+    return words, word_tokens
+
+
+def words_from_path(words, word_tokens, text_indices, time_indices, token_probs) -> List[WordTiming]:
+    """steps 6 to 8 of ``find_alignment``: the times at which the path enters a new token, the words' boundaries among them"""
+    boundaries = np.pad(np.cumsum([len(t) for t in word_tokens[:-1]]), (1, 0))
+    jumps = np.pad(np.diff(text_indices), (1, 0), constant_values=1).astype(bool)
+    jump_times = time_indices[jumps] / TOKENS_PER_SECOND
+    starts, ends = jump_times[boundaries[:-1]], jump_times[boundaries[1:]]
+    probs = [float(np.mean(token_probs[i:j])) for i, j in zip(boundaries[:-1], boundaries[1:])]
+    return [WordTiming(w, list(t), float(s), float(e), p) for w, t, s, e, p in zip(words, word_tokens, starts, ends, probs)]
+
+
+@torch.no_grad()
+def find_alignment(model: "Whisper", tokenizer: Tokenizer, text_tokens: List[int], mel_or_states: torch.Tensor, num_frames: int, *,
+                   medfilt_width: int = 7, qk_scale: float = 1.0, segment_lengths=None, details: Optional[dict] = None) -> List[WordTiming]:
+    """``whisper.timing.find_alignment``: the words of ``text_tokens`` (text ids only) with the times at which one window's audio
+    (``[n_mels, 3000]``, or its encoder states ``[Tk, D]``) says them.  One teacher-forced pass of ``sot_sequence, <|notimestamps|>,
+    text, eot`` keeps every layer's cross-attention queries; ``hirest_whisper_alignment_matrix`` turns those of ``model.
+    alignment_heads`` into the ``[len(text) + 1, num_frames // 2]`` matrix; ``dtw`` of its negative gives the path; a word starts
+    and ends where the path enters its first token and the next word's.  ``probability`` is the mean over the word's tokens of the
+    softmax, over the text ids (columns below eot, as Whisper takes them), of the logits that predict them.  At most one word
+    (the text's words and eot's): an empty list.  ``segment_lengths``: see ``add_word_timestamps``.  ``details``: a dict that
+    receives the matrix, the path and the token probabilities (tests)."""
+    text_tokens = [int(t) for t in text_tokens]
+    if not text_tokens:
+        return []
+    words, word_tokens = _split_words(tokenizer, text_tokens, segment_lengths)
+    if len(word_tokens) <= 1:
+        return []
+    dec, dev = model.decoder, model.device
+    sot = list(tokenizer.sot_sequence)
+    tokens = sot + [tokenizer.no_timestamps] + text_tokens + [tokenizer.eot]
+    T, n = len(tokens), len(text_tokens)
+    if T > dec.ctx:
+        raise ValueError(f"{n} text tokens make a sequence of {T}: the decoder has {dec.ctx} positions")
+    if n + 1 > _lib.DTW_MAX_N:
+        raise ValueError(f"{n} text tokens: the alignment takes up to {_lib.DTW_MAX_N - 1}")
+    states = mel_or_states if mel_or_states.ndim == 3 else mel_or_states[None]
+    with torch.cuda.device(dev):
+        xa = _audio_states(model, states)[:1]
+        Tk = int(xa.shape[1])
+        n_keys = int(num_frames) // 2
+        if not 1 <= n_keys <= min(Tk, _lib.DTW_MAX_M):
+            raise ValueError(f"num_frames {num_frames}: between 2 and {2 * min(Tk, _lib.DTW_MAX_M)} expected")
+        cross_kv = dec.cross_kv(xa)
+        queries: List[torch.Tensor] = []
+        x = dec._sequences(torch.tensor([tokens], dtype=torch.int32), cross_kv, Tk, keep_cross_q=lambda i, q: queries.append(q))
+        logits = dec._head(x)[len(sot):len(sot) + n, :tokenizer.eot]
+        ids = torch.tensor(text_tokens, dtype=torch.int64, device=dev)
+        token_probs = torch.softmax(logits, dim=-1).gather(1, ids[:, None])[:, 0]
+        pairs = model.alignment_heads.nonzero().tolist()
+        matrix = alignment_matrix(queries, [kv[0] for kv in cross_kv], pairs, n_keys, heads=dec.heads, qk_scale=qk_scale,
+                                  medfilt_width=medfilt_width, row0=len(sot), n_rows=n + 1)
+        (text_indices, time_indices), = dtw_many([matrix], negate=True)
+        token_probs = token_probs.cpu().numpy()
+    if details is not None:
+        details.update(matrix=matrix, text_indices=text_indices, time_indices=time_indices, token_probs=token_probs, words=words,
+                       word_tokens=word_tokens)
+    return words_from_path(words, word_tokens, text_indices, time_indices, token_probs)
+
+
+def merge_punctuations(alignment: List[WordTiming], prepended: str = PREPEND_PUNCTUATIONS, appended: str = APPEND_PUNCTUATIONS) -> None:
+    """``whisper.timing.merge_punctuations``, in place: a word that is a space and a ``prepended`` character joins the word after it,
+    a word that is an ``appended`` character joins the word before it (unless that ends with a space); the joined word keeps its own
+    times, the absorbed one is left with an empty word and no tokens."""
+    i, j = len(alignment) - 2, len(alignment) - 1
+    while i >= 0:
+        previous, following = alignment[i], alignment[j]
+        if previous.word.startswith(" ") and previous.word.strip() in prepended:
+            following.word = previous.word + following.word
+            following.tokens = previous.tokens + following.tokens
+            previous.word, previous.tokens = "", []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(alignment):
+        previous, following = alignment[i], alignment[j]
+        if not previous.word.endswith(" ") and following.word in appended:
+            previous.word = previous.word + following.word
+            previous.tokens = previous.tokens + following.tokens
+            following.word, following.tokens = "", []
+        else:
+            i = j
+        j += 1
+
+
+def add_word_timestamps(segments, model: "Whisper", tokenizer: Tokenizer, mel: torch.Tensor, num_frames: int, *,
+                        prepend_punctuations: str = PREPEND_PUNCTUATIONS, append_punctuations: str = APPEND_PUNCTUATIONS, **kwargs) -> None:
+    """``whisper.timing.add_word_timestamps`` for the segments of ONE window (``mel``: the window, or its encoder states): one
+    ``find_alignment`` over the window's text tokens, the punctuations merged, the words handed to the segments by token count, the
+    window's time offset (``segments[0]["seek"]``) added and times rounded to 1/100 s; each segment gains ``"words"``.
+
+    Where this differs from Whisper, on purpose: words are split per segment and punctuation merges inside a segment, so a word never
+    spans two segments and a segment's words concatenate to its text; the segment's bounds are kept and the words' times are clipped
+    into them (Whisper moves the segment's bounds to its words); Whisper's median-duration clamps on long words and its
+    pause heuristics are NOT built."""
+    segments = list(segments)
+    if not segments:
+        return
+    per_segment = [[t for t in s["tokens"] if t < tokenizer.eot] for s in segments]
+    text_tokens = [t for tokens in per_segment for t in tokens]
+    alignment = find_alignment(model, tokenizer, text_tokens, mel, num_frames, segment_lengths=[len(t) for t in per_segment], **kwargs)
+    offset = segments[0]["seek"] * HOP_LENGTH / SAMPLE_RATE
+    at = 0
+    for segment, tokens in zip(segments, per_segment):
+        first, saved = at, 0
+        while at < len(alignment) and saved < len(tokens):
+            saved += len(alignment[at].tokens)
+            at += 1
+        mine = alignment[first:at]
+        merge_punctuations(mine, prepend_punctuations, append_punctuations)
+        lo, hi = segment["start"], segment["end"]
+        segment["words"] = [{"word": w.word, "start": min(max(round(offset + w.start, 2), lo), hi), "end": min(max(round(offset + w.end, 2), lo), hi),
+                             "probability": w.probability} for w in mine if w.word]
+
+
+timing = types.SimpleNamespace(median_filter=median_filter, dtw=dtw, dtw_many=dtw_many, alignment_matrix=alignment_matrix,
+                               find_alignment=find_alignment, merge_punctuations=merge_punctuations, add_word_timestamps=add_word_timestamps,
+                               WordTiming=WordTiming)

@@ -1404,6 +1404,46 @@ int hirest_whisper_decode_step_rows(const hirest_whisper_decoder* d, int32_t R, 
                                     float* const* self_k, float* const* self_v, int32_t T_max, const float* const* cross_kv, int32_t n_windows,
                                     int32_t Tk, const int32_t* row_window, float* logits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Whisper word-level timestamps (csrc/whisper_align.hip, hirest_amd/whisper.py): the alignment matrix of one window from
+ * the cross-attention of a teacher-forced pass, and dynamic time warping.  Every reduction has a fixed order: a window's matrix has
+ * the same bits on every run, whatever the workspace held before.
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+size_t hirest_whisper_alignment_workspace_bytes(int32_t n_sel, int32_t T, int32_t n_keys);     /* the [n_sel, T, n_keys] weights */
+/* q: HOST array [layers] of cross-attention query rows [T, heads * 64] (row stride ldq floats); kv: HOST array [layers] of the
+ * window's key | value rows [Tk, 2 * heads * 64] (16-byte aligned; what hirest_whisper_decode_step's cross_kv holds for the window).
+ * sel: HOST array [n_sel][2] of (layer, head).  Only keys j < n_keys <= Tk are read.  medfilt_width odd, <= 31; heads <= 64.
+ *   w[s, t, :]   = softmax_j(q_t . k_j * 0.125 * qk_scale) over j < n_keys                 (head width 64)
+ *   w[s, :, j]   = (w - mean_t) / std_t, the population standard deviation over the T tokens
+ *   w[s, t, :]   = median filter of medfilt_width along j, reflect padding of width / 2 (unfiltered when n_keys <= width / 2)
+ *   matrix[r, j] = mean over s, in ascending s order, of w[s, row0 + r, j]                  matrix: [n_rows, n_keys]
+ * Pointers of layers without a selected head are not read. */
+int hirest_whisper_alignment_matrix(const float* const* q, int64_t ldq, const float* const* kv, int32_t layers, int32_t heads, int32_t Tk,
+                                    const int32_t* sel, int32_t n_sel, int32_t T, int32_t n_keys, float qk_scale, int32_t medfilt_width,
+                                    int32_t row0, int32_t n_rows, float* matrix, void* workspace, size_t workspace_bytes, void* stream);
+/* The last two steps alone on a given w [n_sel, T, n_keys] (contiguous): out[r, j] = mean over s of the median-filtered
+ * w[s, row0 + r, j].  With n_sel = 1 this is a median filter along the last axis, exact (the median is selected, not computed). */
+int hirest_median_filter_mean_f32(const float* w, int32_t n_sel, int32_t T, int32_t n_keys, int32_t width, int32_t row0, int32_t n_rows,
+                                  float* out, void* stream);
+
+/* Dynamic time warping of x [N, M] (row stride ldx floats; negate: of -x), 1 <= N <= 256, 1 <= M <= 4096.  cost[0, 0] = 0, +inf on
+ * the rest of the border; for i, j >= 1 with c0 = cost[i-1, j-1], c1 = cost[i-1, j], c2 = cost[i, j-1]: (c0, trace 0) if c0 < c1 and
+ * c0 < c2, else (c1, trace 1) if c1 < c0 and c1 < c2, else (c2, trace 2); cost[i, j] = x[i-1, j-1] + c, one fp32 addition — the bits
+ * of a sequential fp32 evaluation.  The backtrace runs on the device from (N, M) with trace[0, :] = 2 and trace[:, 0] = 1: it emits
+ * (i - 1, j - 1), moves by the trace (0: i--, j--; 1: i--; 2: j--) until (0, 0), and the list is reversed.
+ * path: device [N + M, 2] int32, the first *path_len rows written; path_len: device int32; cost: NULL or device [N, M] (row stride
+ * ldc), cost[i-1, j-1] of the recurrence.  One workgroup per problem; problems: HOST array. */
+#define HIREST_DTW_MAX_N 256
+#define HIREST_DTW_MAX_M 4096
+typedef struct hirest_dtw_problem {
+    const float* x; int64_t ldx;
+    int32_t N, M, negate, reserved;
+    int32_t* path; int32_t* path_len;
+    float* cost; int64_t ldc;
+} hirest_dtw_problem;
+size_t hirest_dtw_workspace_bytes(const hirest_dtw_problem* problems, int32_t n_problems);     /* 0 for sizes outside the limits */
+int hirest_dtw_f32(const hirest_dtw_problem* problems, int32_t n_problems, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,8 +8,11 @@ reference's ``extraction/whisper_ASR/extract_ASR.py``, our own code against our 
 ``--tokenizer`` is a directory with ``vocab.json`` and ``merges.txt`` (default: the model directory).
 ``--language`` is a language's name or code (default English, as the reference's), or ``auto`` / ``"Auto detection"``: a multilingual
 model then detects each file's language on its first 30 seconds.  ``--task translate`` writes English subtitles for any language.
+``--word_timestamps`` also writes ``<name>.json`` beside each ``.srt``: the segments with their words (``word``, ``start``, ``end``,
+``probability``); the ``.srt`` is what it is without the option.
 """
 import argparse
+import json
 import os
 import sys
 from pathlib import Path
@@ -44,6 +47,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--files_in_flight", type=int, default=whisper.FILES_IN_FLIGHT,
                     help="files whose current windows are decoded together (whisper.transcribe_many); 1: one file at a time (whisper.transcribe)")
+    ap.add_argument("--word_timestamps", action="store_true", help="align every window's words (whisper.timing) and write <name>.json")
     args = ap.parse_args(argv)
     if args.files_in_flight < 1:
         ap.error("--files_in_flight must be at least 1")
@@ -57,7 +61,7 @@ def main(argv=None):
     temperature, temperature_increment_on_fallback = 0.15, 0.2
     options = dict(language=args.language, task=args.task, best_of=5, beam_size=5, patience=1.0, length_penalty=None, suppress_tokens="-1",
                    initial_prompt=None, condition_on_previous_text=True, fp16=True, compression_ratio_threshold=2.4, logprob_threshold=-1.0,
-                   no_speech_threshold=0.6, seed=args.seed)
+                   no_speech_threshold=0.6, seed=args.seed, word_timestamps=args.word_timestamps)
     temperatures = tuple(np.arange(temperature, 1.0 + 1e-6, temperature_increment_on_fallback))
 
     out_dir = Path(args.asr_dir)
@@ -70,6 +74,11 @@ def main(argv=None):
     for wav, result in zip(wavs, results):
         with open(out_dir / (wav.stem + ".srt"), "w", encoding="utf-8") as f:
             whisper.utils.write_srt(result["segments"], file=f)
+        if args.word_timestamps:
+            keep = ("id", "seek", "start", "end", "text", "words")
+            with open(out_dir / (wav.stem + ".json"), "w", encoding="utf-8") as f:
+                json.dump({"language": result["language"], "segments": [{k: s[k] for k in keep} for s in result["segments"]]}, f,
+                          ensure_ascii=False, indent=1)
         print(f"{wav.name}: {len(result['segments'])} segments")
 
 

@@ -6,10 +6,12 @@ encoder's rate as a fraction of the 157-TFLOP/s fp32 MFMA peak DESIGN.md uses fo
 shapes.  Each figure is the median with the min .. max spread over the repeats.  The decode leg: W windows through one
 run of the decoding loop (``decode_many``) against W one-window runs of the same loop (W sequential ``decode`` calls) at small.en's
 decoder shape.  The detect leg: ``detect_language`` of W windows at multilingual small's decoder shape and the pieces of
-that call; the step leg: the one ``hirest_whisper_decode_step_rows`` call inside it, alone.
+that call; the step leg: the one ``hirest_whisper_decode_step_rows`` call inside it, alone.  The align leg:
+``hirest_whisper_alignment_matrix`` and ``hirest_dtw_f32`` for one window at small.en's shape (12 layers, 72 selected heads, 1500 keys)
+with 50 and 220 tokens, each timed on its own, beside the numpy restatement of both on the CPU (tests/_whisper_align_ref.py, fp32).
 
-    python tools/whisper_bench.py [--repeats 7] [--warmup 2] [--batches 1 8] [--legs encoder decode detect step] [--windows 1 2 4 8 16]
-                                  [--detect_windows 1 16]
+    python tools/whisper_bench.py [--repeats 7] [--warmup 2] [--batches 1 8] [--legs encoder decode detect step align]
+                                  [--windows 1 2 4 8 16] [--detect_windows 1 16] [--align_tokens 50 220]
 """
 import argparse
 import json
@@ -177,20 +179,57 @@ def step_leg(a, dev):
     return table
 
 
+def align_leg(a, dev):
+    """One window's alignment at small.en's shape: the cross-attention queries of T tokens in 12 layers, the heads of the last 6 layers
+    (72 pairs), 1500 keys, filter width 7 -> the [T - 2, 1500] matrix (``hirest_whisper_alignment_matrix``, five kernels in 9
+    launches) and the path through its negative (``hirest_dtw_f32`` with the read-back of the path, as ``dtw`` returns it); inputs
+    are seeded at unit scale and stay resident.  The CPU column is the numpy restatement of the same two steps in fp32, once."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import numpy as np
+    import _whisper_align_ref as A
+    L, H, Tk, D = 12, 12, 1500, 768
+    pairs = [(l, h) for l in range(L // 2, L) for h in range(H)]
+    kv = [synth.tensor(f"bench.align.kv.{l}", (Tk, 2 * D), 1.0, 7) for l in range(L)]
+    kv_dev = [t.to(dev) for t in kv]
+    print(f"align: small.en's shape, {len(pairs)} heads, {Tk} keys, medians of {a.repeats} after {a.warmup} warm-up calls (min .. max)")
+    table = {}
+    for T in a.align_tokens:
+        q = [synth.tensor(f"bench.align.q.{l}", (T, D), 1.0, 8) for l in range(L)]
+        q_dev = [t.to(dev) for t in q]
+        ws = torch.empty((len(pairs) * T * Tk * 4,), dtype=torch.uint8, device=dev)
+        run = lambda: whisper.alignment_matrix(q_dev, kv_dev, pairs, Tk, heads=H, row0=1, n_rows=T - 2, workspace=ws)
+        matrix = run()
+        t_matrix = timed(run, a.repeats, a.warmup)
+        t_dtw = timed(lambda: whisper.dtw_many([matrix], negate=True), a.repeats, a.warmup)
+        t0 = time.perf_counter()
+        ref = A.alignment_matrix([t.numpy() for t in q], [t.numpy() for t in kv], pairs, Tk, row0=1, n_rows=T - 2, dtype=np.float32)
+        t1 = time.perf_counter()
+        ti, tj = A.dtw(-matrix.cpu().numpy(), dtype=np.float32)
+        t2 = time.perf_counter()
+        gi, gj = whisper.dtw_many([matrix], negate=True)[0]
+        assert gi.tolist() == ti.tolist() and gj.tolist() == tj.tolist() and float(np.abs(ref - matrix.cpu().numpy()).max()) < 1e-4
+        print(f"  T = {T:3d}: alignment matrix {spread(t_matrix)}, dtw [{T - 2}, {Tk}] with its read-back {spread(t_dtw)}; "
+              f"numpy on the CPU: matrix {(t1 - t0) * 1e3:.0f} ms, dtw {(t2 - t1) * 1e3:.0f} ms")
+        table[str(T)] = {"matrix_ms": [round(x * 1e3, 4) for x in t_matrix], "dtw_ms": [round(x * 1e3, 4) for x in t_dtw],
+                         "numpy_matrix_ms": (t1 - t0) * 1e3, "numpy_dtw_ms": (t2 - t1) * 1e3}
+    return table
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8])
-    ap.add_argument("--legs", nargs="+", choices=["encoder", "decode", "detect", "step"], default=["encoder", "decode"])
+    ap.add_argument("--legs", nargs="+", choices=["encoder", "decode", "detect", "step", "align"], default=["encoder", "decode"])
     ap.add_argument("--windows", type=int, nargs="+", default=[1, 2, 4, 8, 16], help="windows per decode_many() call of the decode leg")
     ap.add_argument("--detect_windows", type=int, nargs="+", default=[1, 16], help="windows per detect_language() call of the detect leg")
+    ap.add_argument("--align_tokens", type=int, nargs="+", default=[50, 220], help="tokens of the teacher-forced pass of the align leg")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("whisper_bench needs an MI355X: there is nothing to measure without one")
     dev = torch.device("cuda:0")
     if "encoder" not in a.legs:
-        legs = {"decode": decode_leg, "detect": detect_leg, "step": step_leg}
+        legs = {"decode": decode_leg, "detect": detect_leg, "step": step_leg, "align": align_leg}
         print(json.dumps({"device": torch.cuda.get_device_name(0), **{leg: legs[leg](a, dev) for leg in a.legs}}))
         return
     cfg = synth.WHISPER_SMALL_EN
@@ -219,7 +258,7 @@ def main():
                                      "windows_per_s": 1.0 / per_window, "front_end_share": t_front / per_window,
                                      "encoder_tflops": B * (stem_flop + block_flop) / t_whole / 1e12,
                                      "fraction_of_fp32_mfma_peak": B * (stem_flop + block_flop) / t_whole / FP32_MFMA_PEAK}
-    for leg, fn in (("decode", decode_leg), ("detect", detect_leg), ("step", step_leg)):
+    for leg, fn in (("decode", decode_leg), ("detect", detect_leg), ("step", step_leg), ("align", align_leg)):
         if leg in a.legs:
             result[leg] = fn(a, dev)
     print(json.dumps(result))
