@@ -1747,6 +1747,8 @@ int epilogue_operand_status(const hirest_gemm_args& a) {
     if (epi_is_fused(e) && (!a.aux0 || !a.aux1)) return HIREST_E_BADARG;
     if ((e == HIREST_EPI_BIAS_RESID_LNSTATS_F32 || e == HIREST_EPI_BIAS_RESID2_LNSTATS) && a.N % 8 != 0) return HIREST_E_SHAPE;   // 16-B stores of the bf16 copy
     if (e == HIREST_EPI_BIAS_RESID2_LNSTATS && a.ldo % 8 != 0) return HIREST_E_SHAPE;
+    // the straight-line fold epilogues address a wave's 128 output rows with 32-bit byte offsets below HX_OOB
+    if (epi_is_lnfold(e) && HIREST_LNFOLD_BUFFER_EPILOGUE && a.ldo >= ((int64_t)1 << 22)) return HIREST_E_SHAPE;
     return 0;
 }
 

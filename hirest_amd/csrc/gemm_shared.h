@@ -59,6 +59,9 @@ constexpr int Q_WOFF = T_BM * Q_BK * 2;
 #ifndef HIREST_S2_BUFFER_EPILOGUE
 #define HIREST_S2_BUFFER_EPILOGUE 1      // 0: round 5's flat-address form of the two-array residual epilogue (A/B builds)
 #endif
+#ifndef HIREST_LNFOLD_BUFFER_EPILOGUE
+#define HIREST_LNFOLD_BUFFER_EPILOGUE 1  // 0: the flat-address, predicated store side of the LN-fold consumers in the ping-pong kernels (A/B builds)
+#endif
 #ifndef HIREST_S2_RD
 #define HIREST_S2_RD 2                   // residual look-ahead (16-row passes) of the two-array residual epilogue in gemm_pq256
 #endif
@@ -380,6 +383,98 @@ __device__ __forceinline__ f32x4 load_row_stats(const GemmP& p, int Mw, int lane
     return f32x4{v0[0], v0[1], v1[0], v1[1]};
 }
 
+// LN-fold consumers of the ping-pong kernels (HIREST_EPI_LNFOLD_BF16 / _GELU_BF16, 64-column wave tiles, statistics and bias | column-sum slices
+// already in LDS), straight-line form: the arithmetic of epilogue_p's OUT_BF16 branch, operation for operation, with
+//   * one buffer descriptor per wave and tile over out[Mw .. Mw + rows) x [Nw .. Nw + cols): rows at or past M fall behind num_records and are
+//     dropped by the range check, so no row predicate exists;
+//   * ONE per-lane byte offset, set up once per tile and advanced by the constant 8-row step per store (a literal scalar offset of 0: see
+//     epilogue_lnstats2 for the SGPR-offset store hazard) — no multiply in the pass loop;
+//   * FULL (the wave's 64 columns lie inside N; the caller decides once per tile, wave-uniformly): no column predicate at all, two 16-B stores per
+//     pass.  !FULL: the column predicates are folded into the per-lane offsets once per tile (out of range = dropped), a second offset serves the
+//     8-B store of the chunk that holds only 4 columns (N % 8 == 4);
+//   * the LDS round trip of the transpose under arithmetic: the read-back of pass mi is issued, pass mi + 1's values are computed into registers
+//     (8 VGPRs), then pass mi is stored and pass mi + 1 staged.  The LDS executes a wave's DS operations in issue order, so the staging writes
+//     behind the read-back cannot overtake it.
+template <int EPI, int NM, bool FULL>
+__device__ __forceinline__ void epilogue_lnfold_bf16(const GemmP& p, f32x4 (&acc)[8][4], char* stg, int Mw, int Nw, int lane) {
+    const int srow = lane & 15, kg = lane >> 4, sw = lane & 7;   // sw = srow & 7
+    const int rr = lane >> 3, rc = lane & 7;                     // read-back: row (it*8 + rr), 16-B chunk rc
+    const int ldo = (int)p.ldo;
+    int rows = p.M - Mw; rows = rows < NM * 16 ? rows : NM * 16;     // > 0: the caller checked that this wave's block holds rows and columns
+    int cols = p.N - Nw; cols = (FULL || cols > 64) ? 64 : cols;
+    const __amdgpu_buffer_rsrc_t rs = hx_rsrc(reinterpret_cast<const bf16_t*>(p.out) + ((int64_t)Mw * ldo + Nw),
+                                              ((unsigned)(rows - 1) * (unsigned)ldo + (unsigned)cols) * 2u);
+    const unsigned step = 16u * (unsigned)ldo;                       // bytes per 8 rows
+    unsigned v16 = (unsigned)(rr * ldo + rc * 8) * 2u, v8 = HX_OOB;
+    if constexpr (!FULL) {
+        const int n = Nw + rc * 8;
+        v8 = (n + 8 > p.N && n + 4 <= p.N) ? v16 : HX_OOB;
+        v16 = n + 8 <= p.N ? v16 : HX_OOB;
+    }
+    asm volatile("" : "+v"(v16), "+v"(v8));
+    f32x4 bv[4], sv[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const f32x4 b = *reinterpret_cast<const f32x4*>(stg + P_BCS + (n * 16 + 4 * kg) * 4);
+        bv[n] = p.bias ? b : f32x4{0.f, 0.f, 0.f, 0.f};
+        sv[n] = *reinterpret_cast<const f32x4*>(stg + P_BCS + 256 + (n * 16 + 4 * kg) * 4);
+    }
+    auto values = [&](int mi, f32x2 mr, bf16x4 (&o)[4]) {            // pass mi of this lane: 4 columns of row mi*16 + srow in each 16-column tile
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            // LayerNorm folded into the GEMM: rstd * x~ W'^T + (b' - rstd * mean * rowsum(W'))
+            const float c = -mr[0] * mr[1];                          // whole-vector forms: two v_pk_fma_f32 each
+            // (spelled as the two fused multiply-adds -ffp-contract=fast makes of acc * rstd + (s * c + b'): left to the vectoriser, the first
+            // pass of this form came out as separate multiplies and adds for some elements)
+            f32x4 v = __builtin_elementwise_fma(acc[mi][n], f32x4{mr[1], mr[1], mr[1], mr[1]}, __builtin_elementwise_fma(sv[n], f32x4{c, c, c, c}, bv[n]));
+            if constexpr (EPI == HIREST_EPI_LNFOLD_GELU_BF16) {
+                const f32x2 g0 = gelu_erf2(f32x2{v[0], v[1]}), g1 = gelu_erf2(f32x2{v[2], v[3]});
+                v = f32x4{g0[0], g0[1], g1[0], g1[1]};
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[n][e] = (bf16_t)v[e];
+        }
+    };
+    auto stage = [&](const bf16x4 (&o)[4]) {
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+            *reinterpret_cast<bf16x4*>(stg + srow * 128 + (((n * 2 + (kg >> 1)) ^ sw) << 4) + (kg & 1) * 8) = o[n];
+    };
+    bf16x4 o[4];
+    f32x2 mr_next = *reinterpret_cast<const f32x2*>(stg + P_STG + srow * 8);      // (mean, rstd) of row mi*16 + srow, read one pass ahead of its use
+    values(0, mr_next, o);
+    if (NM > 1) mr_next = *reinterpret_cast<const f32x2*>(stg + P_STG + (16 + srow) * 8);
+    stage(o);
+    HX_LDS_ORDER();
+#pragma unroll
+    for (int mi = 0; mi < NM; ++mi) {
+        u32x4 rb[2];
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int r = it * 8 + rr;
+            rb[it] = *reinterpret_cast<const u32x4*>(stg + r * 128 + ((rc ^ (r & 7)) << 4));
+        }
+        __builtin_amdgcn_sched_barrier(0);                           // the read-back is in flight while the next pass is computed
+        if (mi + 1 < NM) {
+            const f32x2 mr = mr_next;
+            if (mi + 2 < NM) mr_next = *reinterpret_cast<const f32x2*>(stg + P_STG + ((mi + 2) * 16 + srow) * 8);
+            values(mi + 1, mr, o);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        HX_LDS_ORDER();
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            __builtin_amdgcn_raw_buffer_store_b128(rb[it], rs, v16, 0, 2);
+            if constexpr (!FULL) __builtin_amdgcn_raw_buffer_store_b64(u32x2{rb[it][0], rb[it][1]}, rs, v8, 0, 0);
+            v16 += step;
+            if constexpr (!FULL) v8 += step;
+            asm volatile("" : "+v"(v16), "+v"(v8));                  // a running offset: left visible, all 16 are hoisted out of the tile loop (16 VGPRs)
+        }
+        if (mi + 1 < NM) stage(o);
+        HX_LDS_ORDER();
+    }
+}
+
 // SREG (gemm_d2, whose two workgroups per CU leave no LDS for them): the (mean, rstd) pairs of the lane's NM rows go
 // straight from global memory (L2-resident, written by hirest_ln_stats_finalize) into registers at the start of the epilogue.
 // BLDS (with PRE, LN-fold epilogues of 64-column wave tiles): the caller has also brought bias[Nw .. Nw + 63] | colsum[Nw .. Nw + 63] into LDS at
@@ -396,6 +491,13 @@ __device__ __forceinline__ void epilogue_p(const GemmP& p, f32x4 (&acc)[8][NI], 
         return;
     }
     constexpr bool FOLD = epi_is_lnfold(EPI);
+    if constexpr (FOLD && BLDS && PRE && !SREG && HIREST_LNFOLD_BUFFER_EPILOGUE) {
+        // the ping-pong kernels' consumers: straight-line store side.  Mw, Nw are wave-uniform, so this is one scalar branch per tile; in the
+        // towers (N % 64 == 0) every tile takes the first form
+        if (Nw + 64 <= p.N) epilogue_lnfold_bf16<EPI, NM, true>(p, acc, stg, Mw, Nw, lane);
+        else epilogue_lnfold_bf16<EPI, NM, false>(p, acc, stg, Mw, Nw, lane);
+        return;
+    }
     constexpr bool OUT_BF16 = (EPI == HIREST_EPI_BIAS_BF16 || EPI == HIREST_EPI_BIAS_GELU_BF16 || EPI == HIREST_EPI_BIAS_QGELU_BF16 || FOLD);
     const int srow = lane & 15, kg = lane >> 4, sw = lane & 7;   // sw = srow & 7
     const int rr = lane >> 3, rc = lane & 7;                     // read-back: row (it*8 + rr), 16-B chunk rc

@@ -69,7 +69,7 @@ enum hirest_epilogue {
                                         (mean, rstd) rows */
     HIREST_EPI_LNFOLD_BF16 = 7,      /* consumer: A = that bf16 copy, W = W', bias = b', aux0 = f32 [M,2] (mean, rstd; the buffer
                                         must be readable up to an EVEN number of rows, i.e. M + 1 rows when M is odd),
-                                        aux1 = s [N];  out bf16 = rstd * (acc - mean * s) + b' */
+                                        aux1 = s [N];  out bf16 = rstd * (acc - mean * s) + b'; ldo < 2^22 (HIREST_E_SHAPE) */
     HIREST_EPI_LNFOLD_GELU_BF16 = 8, /* same, then gelu_erf */
     HIREST_EPI_BIAS_GELU_SPLIT2 = 9, /* HIREST_GEMM_X3 only: out bf16 [M, 2N] = nn.GELU()(acc + bias) (erf form in fp32 by the bf16 towers' degree-8
                                         exp2 polynomial, csrc/common.h gelu_erf2: max abs error 1.1e-6 against exact erff, which the separate
