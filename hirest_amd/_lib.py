@@ -141,6 +141,11 @@ class DtwProblem(C.Structure):
                 ("path", C.c_void_p), ("path_len", C.c_void_p), ("cost", C.c_void_p), ("ldc", C.c_int64)]
 
 
+class WhisperPrefillSeq(C.Structure):
+    """hirest_whisper_prefill_seq (include/hirest_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("offset", "length", "window", "first_row", "n_rows", "sot_index")] + [("reserved", C.c_int32 * 2)]
+
+
 DTW_MAX_N, DTW_MAX_M = 256, 4096     # HIREST_DTW_MAX_N, HIREST_DTW_MAX_M
 
 WHISPER_ROW_STATE_WORDS = 8     # hirest_whisper_row_state: n_sampled, last, penult, last_timestamp, completed | sum_logprobs, no_speech_prob, last_logprob
@@ -480,6 +485,18 @@ _SIGNATURES = {
                                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hirest_whisper_language_tail": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                C.c_void_p]),
+    "hirest_embedding_varlen_fwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.POINTER(WhisperPrefillSeq), C.c_int32, C.c_void_p]),
+    "hirest_attention_f32_varlen_causal": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.POINTER(WhisperPrefillSeq), C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "hirest_attention_f32_varlen_cross": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                                    C.POINTER(WhisperPrefillSeq), C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
+    "hirest_whisper_prefill_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.POINTER(WhisperPrefillSeq), C.c_int32, C.c_void_p]),
+    "hirest_whisper_prefill_workspace_bytes": (C.c_size_t, [C.POINTER(WhisperDecoder), C.c_int32, C.c_int32]),
+    "hirest_whisper_prefill_rows": (C.c_int, [C.POINTER(WhisperDecoder), C.c_int32, C.POINTER(WhisperPrefillSeq), C.c_void_p, C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hirest_whisper_alignment_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "hirest_whisper_alignment_matrix": (C.c_int, [C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32,
                                                   C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32,

@@ -6,6 +6,7 @@
 // device record (hirest_whisper_row_ctl).  Language detection is one per-row step at position 0 and the small softmax
 // over the language tokens' columns below (whisper_language_tail_kernel).
 #include "common.h"
+#include "whisper_shared.h"
 #include <math.h>
 
 namespace {
@@ -437,7 +438,7 @@ Ws plan(const hirest_whisper_decoder* d, int R, int Tk, bool rows = false) {
 int ln_gemm(const float* X, const float* g, const float* b, float* ln_scratch, const float* W, const float* bias, float* out, int R, int N,
             int K, int act, void* stream) {
     const float eps = 1e-5f;
-    if (R <= 256 && K % 256 == 0 && K <= 1024 && (N < 8192 || (K == 768 && R <= 32)))
+    if (whisper_ln_gemm_fused(R, N, K))
         return hirest_gemm_f32_ln(X, K, nullptr, nullptr, nullptr, g, b, eps, nullptr, 0, W, K, bias, nullptr, 0, out, N, R, N, K, act, stream);
     CK(hirest_layernorm(X, K, nullptr, g, b, eps, ln_scratch, K, 1, R, K, stream));
     return hirest_gemm_f32(ln_scratch, K, W, K, bias, nullptr, 0, nullptr, 0, out, N, R, N, K, act, stream);

@@ -735,6 +735,10 @@ WHISPER_DEC_CASES.update({"s": (WHISPER_DEC_S, 8000, 84, 3),
                           "w1024": (_dec_config(1024, 16, 1, 70, 200, 16), 100, 87, 1),
                           "w1280": (_dec_config(1280, 20, 1, 70, 200, 16), 100, 88, 1)})
 WHISPER_DEC_WIDTH_CASES = ("s", "w384", "w512", "w1024", "w1280")
+# A text context of 160, so that prompts of more than one and more than two 64-query attention blocks exist (65 and 130 tokens:
+# tests/test_gpu_whisper_prefill.py).  (config, eot, decoder seed, windows) as an entry of WHISPER_DEC_CASES, kept out of that table:
+# it has no fixture — the yardstick of a ragged prefill is the per-window prefill of the same weights.
+WHISPER_DEC_LONG = (_dec_config(128, 2, 1, 70, 200, 160), 100, 89, 3)
 
 
 def whisper_decoder_shapes(c: dict) -> Dict[str, Tuple[int, ...]]:

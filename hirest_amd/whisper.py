@@ -329,8 +329,8 @@ def _linear(x, w, bias, act=0, resid=None):
 def _ln_linear(x, gamma, beta, w, bias, act=0):
     """act(LayerNorm(x) W^T + bias): inside one GEMM where hirest_gemm_f32_ln has a form for the shape (up to 256 rows, K a multiple of
     256 up to 1024; from 8192 columns on — an LM head — only small.en's K = 768 up to 32 rows), else hirest_layernorm + hirest_gemm_f32:
-    the same bits either way.  The condition is that of ``ln_gemm`` in csrc/whisper_dec.hip, its C twin behind the decode step: the two
-    have to stay the same.  No encoder product reaches 8192 columns (its N is 3 width, width or ffn)."""
+    the same bits either way.  The condition is ``whisper_ln_gemm_fused`` of csrc/whisper_shared.h, its C twin behind the decode step and
+    the prefill: the two have to stay the same.  No encoder product reaches 8192 columns (its N is 3 width, width or ffn)."""
     M, K = x.shape
     N = w.shape[0]
     if M <= 256 and K % 256 == 0 and K <= 1024 and (N < 8192 or (K == 768 and M <= 32)):
@@ -478,6 +478,60 @@ def encode_file(path: str, encoder: AudioEncoder) -> torch.Tensor:
 _CAUSAL_PENALTY = -1.0e30      # added to scores of future keys in prefill: exp() of it is exactly 0 against any fp32 score, no overflow
 
 
+PREFILL_ROWS_PER_CALL = 4096   # packed prompt rows of one hirest_whisper_prefill_rows call: bounds its workspace
+
+
+def prefill_plan(prompts, first_rows, groups, windows, sot_indices=None, rows_per_call: int = PREFILL_ROWS_PER_CALL):
+    """The ``hirest_whisper_prefill_seq`` tables of ``TextDecoder.prefill_many``, a pure function: a list of calls, each a list of
+    ``(offset, length, window, first_row, n_rows, sot_index)`` in the prompts' order.  Offsets restart at 0 in every call; a call
+    takes consecutive prompts while they fit ``rows_per_call`` packed rows (at least one).  ``sot_index`` is -1 where none is given
+    or where it is the last position, whose logits are returned anyway."""
+    n = len(prompts)
+    sot_indices = [None] * n if sot_indices is None else list(sot_indices)
+    if not (len(first_rows) == len(groups) == len(windows) == len(sot_indices) == n) or n == 0:
+        raise ValueError("prefill_plan: one first row, group, window and sot index per prompt, and at least one prompt")
+    calls, cur, off = [], [], 0
+    for p, r0, g, w, sot in zip(prompts, first_rows, groups, windows, sot_indices):
+        T = len(p)
+        if T < 1:
+            raise ValueError("prefill_plan: an empty prompt")
+        if sot is not None and not 0 <= sot < T:
+            raise ValueError(f"prefill_plan: sot index {sot} outside a prompt of {T} tokens")
+        if cur and off + T > rows_per_call:
+            calls.append(cur)
+            cur, off = [], 0
+        cur.append((off, T, int(w), int(r0), int(g), -1 if sot is None or sot == T - 1 else int(sot)))
+        off += T
+    calls.append(cur)
+    return calls
+
+
+def window_row_ranges(row_window: Sequence[int], n_windows: int) -> List[Tuple[int, int]]:
+    """``row_window [R]`` -> per window (first row, row count); ValueError where a window's rows are not contiguous, where a window
+    has no row, or where a row names a window outside ``[0, n_windows)``."""
+    ranges = [None] * n_windows
+    for r, w in enumerate(row_window):
+        if not 0 <= w < n_windows:
+            raise ValueError(f"row {r} names window {w} of {n_windows}")
+        if ranges[w] is None:
+            ranges[w] = (r, 1)
+        elif ranges[w][0] + ranges[w][1] == r:
+            ranges[w] = (ranges[w][0], ranges[w][1] + 1)
+        else:
+            raise ValueError(f"the rows of window {w} are not contiguous (row {r} after row {ranges[w][0] + ranges[w][1] - 1})")
+    for w, rg in enumerate(ranges):
+        if rg is None:
+            raise ValueError(f"window {w} has no row")
+    return ranges
+
+
+def _seq_table(seqs):
+    table = (_lib.WhisperPrefillSeq * len(seqs))()
+    for t, (off, T, w, r0, g, sot) in zip(table, seqs):
+        t.offset, t.length, t.window, t.first_row, t.n_rows, t.sot_index = off, T, w, r0, g, sot
+    return table
+
+
 class KVCache:
     """What a decoding loop keeps between steps: per layer the preallocated self-attention cache ``[R, T_max, D]`` (key, value), the
     cross-attention ``key(xa) | value(xa)`` rows ``[n_windows, Tk, 2 D]``, ``row_window [R]`` and the number of filled positions.
@@ -507,8 +561,10 @@ class TextDecoder(_FrozenWeights):
     encoder's states, MLP), ``ln``, the tied-embedding LM head.  ``dims_or_config`` / ``state_dict`` as ``AudioEncoder``'s (either schema).
 
     ``forward(tokens, xa)`` runs whole sequences (teacher forcing, a window's prompt) through the full-sequence kernels.  With a
-    ``KVCache`` it fills the cache from a prompt shared by all rows (``tokens [1, T]`` or ``[T]``; the cache rows are broadcast) or, once
-    the cache holds positions, takes one new token per row (``tokens [R, 1]``) through ``hirest_whisper_decode_step``."""
+    ``KVCache`` it fills the cache from a prompt shared by all rows (``tokens [1, T]`` or ``[T]``; the cache rows are broadcast) — over
+    several windows from one prompt per window (``tokens [n_windows, T]``, Whisper's batched call) — or, once the cache holds
+    positions, takes one new token per row (``tokens [R, 1]``) through ``hirest_whisper_decode_step``.  ``prefill_many`` is the decoding
+    loop's prefill: prompts of different lengths for all its windows in one ``hirest_whisper_prefill_rows`` call."""
 
     def __init__(self, dims_or_config, state_dict: Dict[str, torch.Tensor]):
         super().__init__()
@@ -619,7 +675,9 @@ class TextDecoder(_FrozenWeights):
     @torch.no_grad()
     def forward(self, tokens: torch.Tensor, xa: Optional[torch.Tensor], kv_cache: Optional[KVCache] = None) -> torch.Tensor:
         """``tokens [B, T]``, ``xa [B, Tk, D]`` -> logits ``[B, T, n_vocab]``.  With ``kv_cache`` (``xa`` is then the cache's own): an empty
-        cache takes the shared prompt ``[1, T]`` and returns ``[1, T, n_vocab]``; a filled one takes ``[R, 1]`` and returns ``[R, 1, n_vocab]``."""
+        cache over one window takes the shared prompt ``[1, T]`` and returns ``[1, T, n_vocab]``, one over several windows takes a
+        prompt per window ``[n_windows, T]`` and returns ``[n_windows, T, n_vocab]``; a filled one takes ``[R, 1]`` and returns
+        ``[R, 1, n_vocab]``."""
         self._require_gpu()
         if tokens.ndim == 1:
             tokens = tokens[None]
@@ -634,9 +692,11 @@ class TextDecoder(_FrozenWeights):
                 return self._head(x).view(B, T, self.vocab_padded)[..., :self.vocab]
             kc = kv_cache
             if kc.length == 0:
-                if B != 1:
+                if kc.n_windows == 1 and B != 1:
                     raise ValueError("an empty cache is filled from ONE prompt shared by its rows: tokens [1, T]")
-                return self.prefill(tokens, kc).view(1, T, self.vocab_padded)[..., :self.vocab]
+                if kc.n_windows > 1 and B != kc.n_windows:
+                    raise ValueError(f"an empty cache over {kc.n_windows} windows is filled from one prompt per window: tokens [{kc.n_windows}, T]")
+                return self.prefill(tokens, kc).view(B, T, self.vocab_padded)[..., :self.vocab]
             if T != 1 or B != kc.R:
                 raise ValueError(f"a filled cache takes one new token per row: tokens [{kc.R}, 1]")
             self.step(tokens.to(self.device, torch.int32).contiguous().view(-1), kc)
@@ -646,15 +706,32 @@ class TextDecoder(_FrozenWeights):
     def prefill(self, tokens: torch.Tensor, kc: KVCache, rows: Optional[slice] = None, window: Optional[int] = None) -> torch.Tensor:
         """The prompt ``[1, T]`` shared by every row of an empty cache, once: fills positions 0 .. T - 1 of all rows' caches (broadcast),
         sets ``kc.length`` and returns the prompt's logits ``[T, vocab_padded]``.  With ``window`` (the decoding loop's per-row cache over
-        several windows): the same for the slice ``rows`` against that window's cross keys / values; ``kc.length`` stays."""
+        several windows): the same for the slice ``rows`` against that window's cross keys / values; ``kc.length`` stays.  Without
+        ``window`` on a cache over several windows: ``tokens [n_windows, T]``, prompt w for every row with ``row_window == w`` (a
+        window's rows must be contiguous: ValueError otherwise); returns ``[n_windows * T, vocab_padded]``."""
         T = int(tokens.shape[-1])
         if kc.length != 0:
             raise ValueError("prefill of a cache that already holds positions")
-        if window is None and kc.n_windows != 1:
-            raise NotImplementedError("prefill of rows over several windows: one window per cache is what decode() drives")
         if T > min(kc.T_max, self.ctx):
             raise ValueError(f"a prompt of {T} tokens does not fit the cache's {kc.T_max} positions")
-        D, w, rows = self.width, window or 0, rows if rows is not None else slice(None)
+        D = self.width
+        if window is None and kc.n_windows != 1:
+            if tokens.ndim != 2 or tokens.shape[0] != kc.n_windows:
+                raise ValueError(f"tokens of shape {tuple(tokens.shape)}: one prompt per window, [{kc.n_windows}, T], expected")
+            ranges = window_row_ranges(kc.row_window.tolist(), kc.n_windows)          # (a read-back; this is not the loop's path)
+            seqs = prefill_plan([[0] * T] * kc.n_windows, [r0 for r0, _ in ranges], [n for _, n in ranges], range(kc.n_windows),
+                                rows_per_call=kc.n_windows * T)[0]
+            table = _seq_table(seqs)
+
+            def scatter(i, qkv):       # every window's keys / values into its rows, one launch per layer
+                _lib.check(_lib.load().hirest_whisper_prefill_scatter(qkv.data_ptr() + 4 * D, qkv.data_ptr() + 8 * D, 3 * D, kc.self_k[i].data_ptr(),
+                                                                      kc.self_v[i].data_ptr(), kc.R, kc.T_max, D, table, len(seqs), ops.stream_ptr()),
+                           "hirest_whisper_prefill_scatter")
+            with torch.cuda.device(self.device):
+                x = self._sequences(tokens, kc.cross_kv, kc.Tk, scatter)
+                kc.length = T
+                return self._head(x)
+        w, rows = window or 0, rows if rows is not None else slice(None)
 
         def keep(i, qkv):          # the prompt's keys / values, the same for every candidate row of the window
             kc.self_k[i][rows, :T] = qkv[:, D:2 * D]
@@ -664,6 +741,37 @@ class TextDecoder(_FrozenWeights):
             if window is None:
                 kc.length = T
             return self._head(x)
+
+    @torch.no_grad()
+    def prefill_many(self, prompts: Sequence[Sequence[int]], kc: KVCache, first_rows: Sequence[int], groups: Sequence[int],
+                     windows: Sequence[int], sot_indices: Optional[Sequence[Optional[int]]] = None, rows_per_call: Optional[int] = None):
+        """The decoding loop's prefill: prompt s (a list of token ids, each of its own length) against window ``windows[s]``'s cross
+        keys / values fills positions ``0 .. len - 1`` of cache rows ``first_rows[s] .. first_rows[s] + groups[s] - 1`` — all prompts
+        as packed rows through ONE ``hirest_whisper_prefill_rows`` call (consecutive calls past ``rows_per_call`` packed rows,
+        ``PREFILL_ROWS_PER_CALL`` unless given), with the bits of ``prefill(tokens[1, T], kc, rows=, window=)`` prompt by prompt.  -> ``(logits_last [n_seq,
+        vocab_padded], logits_sot)``: the logits of every prompt's last position and, where ``sot_indices[s]`` names another position,
+        of that one (``None`` when no prompt does; rows of the others are not written).  ``kc.length`` stays."""
+        limit = min(kc.T_max, self.ctx)
+        for p in prompts:
+            if not 1 <= len(p) <= limit:
+                raise ValueError(f"a prompt of {len(p)} tokens does not fit the cache's {kc.T_max} positions (the decoder has {self.ctx})")
+        calls = prefill_plan(prompts, first_rows, groups, windows, sot_indices, rows_per_call or PREFILL_ROWS_PER_CALL)
+        lib, dev, Vp = _lib.load(), self.device, self.vocab_padded
+        desc = C.byref(self._w()["desc"])
+        with torch.cuda.device(dev):
+            last = torch.empty((len(prompts), Vp), dtype=torch.float32, device=dev)
+            sot = torch.empty((len(prompts), Vp), dtype=torch.float32, device=dev) if any(q[5] >= 0 for c in calls for q in c) else None
+            ids = torch.tensor([t for p in prompts for t in p], dtype=torch.int32).to(dev)
+            s0 = n0 = 0
+            for seqs in calls:
+                N = sum(q[1] for q in seqs)
+                ws = torch.empty((max(int(lib.hirest_whisper_prefill_workspace_bytes(desc, N, len(seqs))), 1),), dtype=torch.uint8, device=dev)
+                _lib.check(lib.hirest_whisper_prefill_rows(desc, len(seqs), _seq_table(seqs), ids.data_ptr() + 4 * n0, kc.k_ptrs, kc.v_ptrs, kc.R,
+                                                           kc.T_max, kc.x_ptrs, kc.n_windows, kc.Tk, last.data_ptr() + 4 * Vp * s0,
+                                                           sot.data_ptr() + 4 * Vp * s0 if sot is not None else None, ws.data_ptr(), ws.numel(),
+                                                           ops.stream_ptr()), "hirest_whisper_prefill_rows")
+                s0, n0 = s0 + len(seqs), n0 + N
+        return last, sot
 
     def step(self, ids: torch.Tensor, kc: KVCache) -> torch.Tensor:
         """one position for every row of the cache: ``ids`` int32 ``[R]`` on the device -> ``kc.logits [R, vocab_padded]``"""
@@ -1199,7 +1307,7 @@ def _decode_windows(model, mel, opts, rows_per_loop):
 
 def _decode_rows(model, xa, opts, plans, langs):
     """THE decoding loop, over the candidate rows of ``xa``'s windows: one cross key / value projection for all windows, one cache of
-    all rows, the B = 1 prefill per window, then per token ``hirest_whisper_step_tail_rows`` + ``hirest_whisper_decode_step_rows`` over
+    all rows, one ragged prefill of all windows' prompts (``prefill_many``), then per token ``hirest_whisper_step_tail_rows`` + ``hirest_whisper_decode_step_rows`` over
     all rows — each at its own position, with its own temperature, seed and remaining room, kept in a device record per row — until
     no row is active.  Nothing is read back in the loop but the pinned stamp; tokens and sums are read once at the end."""
     tokenizer, dec, dev, lib = model.tokenizer, model.decoder, model.device, _lib.load()
@@ -1212,18 +1320,20 @@ def _decode_rows(model, xa, opts, plans, langs):
     kc = KVCache(dec, xa, row_window, T_max, per_row=True)
     # the constants every window shares; temperature, seed, serial and sample_begin are the rows' own (hirest_whisper_row_ctl)
     params, mask = tail_params(tokenizer, opts[0], dec.vocab, Vp, model.dims["n_audio_ctx"], 0, dev)
-    first = torch.empty((R, Vp), dtype=torch.float32, device=dev)
+    # every window's prompt in one ragged pass: the caches, the logits of the last position and, where it is another one, of sot's
+    groups = [p[3] for p in plans]
+    want_sot = tokenizer.no_speech is not None
+    last, at_sot = dec.prefill_many([p[0] for p in plans], kc, first_row[:-1], groups, range(len(plans)),
+                                    [p[1] for p in plans] if want_sot else None)
+    first = last.index_select(0, kc.row_window) if R != len(plans) else last          # a window's candidate rows start from the same logits
     no_speech, ctl_rows = [], []
     for w, (initial, sot_index, steps, group) in enumerate(plans):
-        r0, T = first_row[w], len(initial)
-        padded = dec.prefill(torch.tensor([initial], dtype=torch.int32), kc, rows=slice(r0, r0 + group), window=w)      # [T, vocab_padded]
-        first[r0:r0 + group].copy_(padded[T - 1].expand(group, -1))
+        T = len(initial)
         scratch = None
-        if sot_index != T - 1 and tokenizer.no_speech is not None:
+        if sot_index != T - 1 and want_sot:
             # Whisper reads no_speech_prob at the sot position: one lock-step tail call on that row, into a scratch state
             scratch, sid = new_row_state(1, dev), torch.empty(1, dtype=torch.int32, device=dev)
-            row = padded[sot_index].contiguous()
-            _lib.check(lib.hirest_whisper_step_tail(row.data_ptr(), Vp, 1, Vp, 0, 0, C.byref(params), scratch.data_ptr(), sid.data_ptr(), None,
+            _lib.check(lib.hirest_whisper_step_tail(at_sot[w].data_ptr(), Vp, 1, Vp, 0, 0, C.byref(params), scratch.data_ptr(), sid.data_ptr(), None,
                                                     None, None, ops.stream_ptr()), "hirest_whisper_step_tail")
         no_speech.append(scratch)
         ctl_rows += [(T - 1, 0, steps, g, opts[w].seed, opts[w].temperature) for g in range(group)]

@@ -1405,6 +1405,59 @@ int hirest_whisper_decode_step_rows(const hirest_whisper_decoder* d, int32_t R, 
                                     int32_t Tk, const int32_t* row_window, float* logits, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------------
+ * Whisper prompt prefill for all windows of a decoding loop (csrc/whisper_prefill.hip, hirest_amd/whisper.py): the
+ * prompts run as packed rows [N, .], N = sum of their lengths, through hirest_gemm_f32(_ln) in hirest_whisper_decode_step's per-layer
+ * order and through the ragged kernels below.  Per sequence the arithmetic and its order are those of the one-prompt prefill
+ * (hirest_embedding_fwd_f32, hirest_attention_f32_qkv at B = 1, the same products): the same bits, whatever else the call holds and in
+ * whatever order.  No atomics; every reduction has a fixed order.
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+typedef struct hirest_whisper_prefill_seq {   /* HOST array, one per sequence */
+    int32_t offset, length;      /* packed rows [offset, offset + length): the ranges tile [0, N) in the array's order */
+    int32_t window;              /* whose cross keys / values it attends to; sequences may share one */
+    int32_t first_row, n_rows;   /* cache rows that receive its keys / values; the ranges of two sequences are disjoint */
+    int32_t sot_index;           /* >= 0 and != length - 1: also return that position's logits; else -1 */
+    int32_t reserved[2];
+} hirest_whisper_prefill_seq;
+/* Every entry point below returns HIREST_E_BADARG before any launch (no GPU needed) for a NULL pointer, n_seq <= 0, a length < 1 or
+ * past the call's limit, an offset that is not the end of the sequence before it (0 for the first), and — where the call uses the
+ * field — a window outside [0, n_windows) and a row range outside [0, R) or overlapping another sequence's; in every call, a sot_index
+ * that is >= length or == length - 1.  Each call says which fields it uses. */
+/* out[offset_s + j] = table[ids[offset_s + j]] + pos[j * D]: hirest_embedding_fwd_f32 with a position per packed row.  ids outside
+ * [0, vocab) are clamped.  Lengths up to max_pos.  Uses offset, length (and checks sot_index). */
+int hirest_embedding_varlen_fwd_f32(const int32_t* ids, const float* table, const float* pos, float* out, int32_t vocab, int32_t max_pos,
+                                    int32_t D, const hirest_whisper_prefill_seq* seqs, int32_t n_seq, void* stream);
+/* Causal self-attention of every sequence over its own packed rows, 64-wide heads: per query hirest_attention_f32_qkv(q + offset *
+ * ldq, ldq, k + offset * ldkv, v + offset * ldkv, ldkv, out + offset * H * 64, B = 1, Tq = Tk = length, ...)'s arithmetic in its order.
+ * out [N, H * 64]; k, v and out 16-byte aligned.  Uses offset, length. */
+int hirest_attention_f32_varlen_causal(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, float* out,
+                                       const hirest_whisper_prefill_seq* seqs, int32_t n_seq, int32_t H, float scale, float add_const,
+                                       float causal_penalty, void* stream);
+/* Cross-attention of every sequence's packed query rows against its window's key | value rows [Tk, 2 * H * 64] at kv + window *
+ * window_stride (hirest_attention_f32_cross_decode's layout): per query hirest_attention_f32_qkv(B = 1, Tq = length, Tk,
+ * causal_penalty = 0)'s arithmetic.  Uses offset, length, window. */
+int hirest_attention_f32_varlen_cross(const float* q, int64_t ldq, const float* kv, int64_t ldkv, int64_t window_stride, int32_t n_windows,
+                                      int32_t Tk, float* out, const hirest_whisper_prefill_seq* seqs, int32_t n_seq, int32_t H, float scale,
+                                      float add_const, void* stream);
+/* Position j < length of sequence s's key / value rows (k / v + (offset + j) * ld, D floats) -> position j of rows first_row ..
+ * first_row + n_rows - 1 of k_cache / v_cache [R, T_max, D], as 16-byte vectors.  Nothing else of a cache is written.  Lengths up to
+ * T_max.  Uses offset, length, first_row, n_rows. */
+int hirest_whisper_prefill_scatter(const float* k, const float* v, int64_t ld, float* k_cache, float* v_cache, int32_t R, int32_t T_max,
+                                   int32_t D, const hirest_whisper_prefill_seq* seqs, int32_t n_seq, void* stream);
+/* Bytes of workspace hirest_whisper_prefill_rows wants for n_rows_packed packed rows of n_seq sequences: the activations of the packed
+ * rows, the gathered rows of the LM head and, where a layer's product takes it, hirest_gemm_f32_ws's split-form scratch.  It does not
+ * depend on Tk (the cross keys / values are the caller's).  0 for a NULL descriptor, a width or MLP width <= 0, or a count <= 0. */
+size_t hirest_whisper_prefill_workspace_bytes(const hirest_whisper_decoder* d, int32_t n_rows_packed, int32_t n_seq);
+/* The prefill of n_seq prompts in one call.  ids: device, packed [N].  self_k / self_v / cross_kv / R / T_max / n_windows / Tk as
+ * hirest_whisper_decode_step_rows'; lengths up to min(max_pos, T_max).  Fills positions < length of every sequence's cache rows and
+ * writes logits_last[s] = the logits of its last position, and logits_sot[s] = those of position sot_index where sot_index >= 0
+ * (other rows of logits_sot are not written; logits_sot may be NULL when no sequence asks).  Both [n_seq, vocab_padded].  A workspace
+ * that is too small is HIREST_E_BADARG as well. */
+int hirest_whisper_prefill_rows(const hirest_whisper_decoder* d, int32_t n_seq, const hirest_whisper_prefill_seq* seqs, const int32_t* ids,
+                                float* const* self_k, float* const* self_v, int32_t R, int32_t T_max, const float* const* cross_kv,
+                                int32_t n_windows, int32_t Tk, float* logits_last, float* logits_sot, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
  * Whisper word-level timestamps (csrc/whisper_align.hip, hirest_amd/whisper.py): the alignment matrix of one window from
  * the cross-attention of a teacher-forced pass, and dynamic time warping.  Every reduction has a fixed order: a window's matrix has
  * the same bits on every run, whatever the workspace held before.

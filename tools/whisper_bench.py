@@ -5,13 +5,14 @@ front end, the convolution stem and the blocks (each timed on its own, a device 
 encoder's rate as a fraction of the 157-TFLOP/s fp32 MFMA peak DESIGN.md uses for the joint model.  Operations are counted from the
 shapes.  Each figure is the median with the min .. max spread over the repeats.  The decode leg: W windows through one
 run of the decoding loop (``decode_many``) against W one-window runs of the same loop (W sequential ``decode`` calls) at small.en's
-decoder shape.  The detect leg: ``detect_language`` of W windows at multilingual small's decoder shape and the pieces of
+decoder shape; ``--prompt-len N`` gives every window N previous tokens as its prompt (``transcribe()`` with
+``condition_on_previous_text`` carries up to 223), so that the prefill has a prompt to run.  The detect leg: ``detect_language`` of W windows at multilingual small's decoder shape and the pieces of
 that call; the step leg: the one ``hirest_whisper_decode_step_rows`` call inside it, alone.  The align leg:
 ``hirest_whisper_alignment_matrix`` and ``hirest_dtw_f32`` for one window at small.en's shape (12 layers, 72 selected heads, 1500 keys)
 with 50 and 220 tokens, each timed on its own, beside the numpy restatement of both on the CPU (tests/_whisper_align_ref.py, fp32).
 
     python tools/whisper_bench.py [--repeats 7] [--warmup 2] [--batches 1 8] [--legs encoder decode detect step align]
-                                  [--windows 1 2 4 8 16] [--detect_windows 1 16] [--align_tokens 50 220]
+                                  [--windows 1 2 4 8 16] [--prompt-len 0] [--detect_windows 1 16] [--align_tokens 50 220]
 """
 import argparse
 import json
@@ -63,7 +64,8 @@ def decode_leg(a, dev):
     """W windows of small.en's shape (random weights, random encoder states) with best_of 5 and 64 forced steps — the eot embedding is
     biased so far down that no row ends — through one decode_many() loop against W sequential decode() calls, which are W one-window
     runs of the same loop, in the same process; and the same two with one step, which is the prefill and everything else a window
-    costs before its loop."""
+    costs before its loop: that call's time is the "prefill ms" column.  ``--prompt-len N``: every window's prompt is <|startofprev|>,
+    N seeded text tokens (cut to the 223 the context admits) and <|startoftranscript|>; 0: <|startoftranscript|> alone."""
     cfg = synth._dec_config(768, 12, 12, 1500, 51864, 448)
     eot, steps = 50256, 64
     sd = synth.whisper_decoder_state_dict(cfg, 83, eot, -8.0)
@@ -71,11 +73,15 @@ def decode_leg(a, dev):
     tok = synth.whisper_tokenizer(eot)
     tok.decode = lambda ids: ""                                       # random weights pick ids the synthetic vocabulary cannot spell; no text is needed
     model = whisper.Whisper({**cfg, "encoder_layers": 1}, sd, tok).to(dev)                                 # the encoder is not run: states go in
-    full = whisper.DecodingOptions(temperature=0.4, best_of=5, seed=5, sample_len=steps)
-    one = whisper.DecodingOptions(temperature=0.4, best_of=5, seed=5, sample_len=1)
+    prompt = synth.token_ids("bench.decode.prompt", a.prompt_len, eot, 11).tolist() if a.prompt_len > 0 else None
+    full = whisper.DecodingOptions(temperature=0.4, best_of=5, seed=5, sample_len=steps, prompt=prompt)
+    one = whisper.DecodingOptions(temperature=0.4, best_of=5, seed=5, sample_len=1, prompt=prompt)
+    n_initial = len(whisper._initial_tokens(tok, full, cfg["max_target_positions"])[0])
     xa_all = synth.whisper_audio_states(cfg, max(a.windows), 7).to(dev)
-    print(f"decode: small.en's decoder shape, best_of 5, {steps} forced steps, medians of {a.repeats} after {a.warmup} warm-up calls")
-    print("   W | decode_many: windows/s  ms/step  prefill share | W x decode (W one-window loops): windows/s  ms/step  prefill share | ratio")
+    print(f"decode: small.en's decoder shape, best_of 5, {n_initial} initial tokens per window, {steps} forced steps, medians of {a.repeats} "
+          f"after {a.warmup} warm-up calls")
+    print("   W | decode_many: windows/s  ms/step  prefill ms  prefill share | W x decode (W one-window loops): windows/s  ms/step  prefill ms  "
+          "prefill share | ratio")
     table = {}
     for W in a.windows:
         xa = xa_all[:W]
@@ -86,13 +92,14 @@ def decode_leg(a, dev):
         many, many1 = med(lambda: whisper.decode_many(model, xa, full)), med(lambda: whisper.decode_many(model, xa, one))
         seq = med(lambda: [whisper.decode(model, xa[w], full) for w in range(W)])
         seq1 = med(lambda: [whisper.decode(model, xa[w], one) for w in range(W)])
-        row = {"many_windows_per_s": W / many, "many_ms_per_step": (many - many1) / (steps - 1) * 1e3, "many_prefill_share": many1 / many,
+        row = {"initial_tokens": n_initial, "many_windows_per_s": W / many, "many_ms_per_step": (many - many1) / (steps - 1) * 1e3,
+               "many_prefill_ms": many1 * 1e3, "many_prefill_share": many1 / many,
                "sequential_windows_per_s": W / seq, "sequential_ms_per_step": (seq - seq1) / (steps - 1) / W * 1e3,
-               "sequential_prefill_share": seq1 / seq}
+               "sequential_prefill_ms": seq1 * 1e3, "sequential_prefill_share": seq1 / seq}
         table[str(W)] = row
-        print(f"  {W:2d} | {row['many_windows_per_s']:22.2f}  {row['many_ms_per_step']:7.3f}  {row['many_prefill_share']:13.3f} | "
-              f"{row['sequential_windows_per_s']:21.2f}  {row['sequential_ms_per_step']:7.3f}  {row['sequential_prefill_share']:13.3f} | "
-              f"{seq / many:5.2f}")
+        print(f"  {W:2d} | {row['many_windows_per_s']:22.2f}  {row['many_ms_per_step']:7.3f}  {row['many_prefill_ms']:10.3f}  "
+              f"{row['many_prefill_share']:13.3f} | {row['sequential_windows_per_s']:21.2f}  {row['sequential_ms_per_step']:7.3f}  "
+              f"{row['sequential_prefill_ms']:10.3f}  {row['sequential_prefill_share']:13.3f} | {seq / many:5.2f}")
     return table
 
 
@@ -222,6 +229,7 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--legs", nargs="+", choices=["encoder", "decode", "detect", "step", "align"], default=["encoder", "decode"])
     ap.add_argument("--windows", type=int, nargs="+", default=[1, 2, 4, 8, 16], help="windows per decode_many() call of the decode leg")
+    ap.add_argument("--prompt-len", type=int, default=0, help="previous tokens in every window's prompt of the decode leg (0: none, as before)")
     ap.add_argument("--detect_windows", type=int, nargs="+", default=[1, 16], help="windows per detect_language() call of the detect leg")
     ap.add_argument("--align_tokens", type=int, nargs="+", default=[50, 220], help="tokens of the teacher-forced pass of the align leg")
     a = ap.parse_args()
