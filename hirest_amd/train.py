@@ -414,7 +414,7 @@ def _block_forward(P, p, i, x, wqkv, bqkv, B, T, heads, drop, seed, x3=False, x2
 
 def _block_backward(P, p, Ly, dout, G):
     """Backward of _block_forward through hirest_train_block_backward: dX products on the current stream, dW on the open side stream, the
-    twelve column sums appended to the open batch.  Returns d loss / d (block input)."""
+    eight column sums appended to the open batch.  Returns d loss / d (block input)."""
     lib = _lib.load()
     d = Ly["desc"]
     R, Hd, mlp = Ly["dims"]

@@ -1079,7 +1079,7 @@ int hirest_layernorm_f32_split2(const float* x, int64_t ldx, const float* add, i
  *             hpre = aa W1^T + b1;  hh = gelu(hpre);  x_pre = aa + drop(hh W2^T + b2);  out = LN2(x_pre)
  *   backward: dX products on `stream`; the four weight-gradient products dW = dY^T X on `side_stream` (NULL: on `stream`)
  *             behind an event that marks their dY complete — the caller joins the side stream before reading g_w*; the
- *             twelve column sums (bias and LayerNorm gradients) are APPENDED to `items` for one
+ *             eight column sums (g_bqkv, g_bo, g_b1, g_b2 and the two LayerNorm pairs) are APPENDED to `items` for one
  *             hirest_weighted_colsum_grouped_f32 by the caller once the whole backward is enqueued.
  * precision 0: exact fp32 products (hirest_gemm_f32*).  precision 1 ("bf16x3"): the forward products and the dX products on
  * split operands (HIREST_GEMM_X3 | HIREST_GEMM_X3_T128; weights split per call into `scratch`), dW stays fp32.

@@ -7,12 +7,14 @@ Bars (every one derived from the fp32 arithmetic of the operation, U = 2^-24 the
   * elementwise kernels: a few roundings of the operands' magnitude (a few ulp);
   * reductions of up to a few thousand terms: about 1e-5 of the row's scale, or the classic n * U * sum|terms| bound of an n-term
     fp32 sum where the kernel's summation depth is known.
-The dropout keep mask is restated in numpy (keep_scale below, the splitmix64 of (seed, index) of train.hip) and matched exactly.
+The dropout keep mask is restated in numpy (keep_scale of tests/_train_ref.py, the splitmix64 of (seed, index) of train.hip) and matched exactly.
 """
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from _train_ref import _rows_close, _within, keep_scale          # shared with tests/test_gpu_train_block.py
 
 pytestmark = pytest.mark.gpu
 
@@ -60,42 +62,6 @@ def _dev(dev, *ts):
 
 def _ok(rc, what):
     assert rc == 0, f"{what} returned {rc}"
-
-
-def _within(err, bar, what, at=None):
-    """err, bar: tensors of the same shape; prints the worst err / bar so that a run shows the margin (`at`: the input values,
-    reported at the worst element)."""
-    err, bar = err.double(), bar.double()
-    r = (err / bar.clamp_min(1e-300)).flatten()
-    i = int(r.argmax()) if r.numel() else 0
-    ratio = r[i].item() if r.numel() else 0.0
-    where = f" at input {at.flatten()[i].item():.6g}" if at is not None and r.numel() else ""
-    print(f"{what}: worst err/bar {ratio:.3g}{where}")
-    assert ratio <= 1.0 and not torch.isnan(err).any(), f"{what}: err/bar {ratio:.3g}{where}"
-
-
-def _rows_close(got, ref, tol, what, floor=1e-3):
-    """|got - ref| <= tol * (row scale), row = last dimension, scale = max |ref| over the row (at least floor * the tensor's
-    max, so that a row which is exactly zero in both is compared against the tensor's scale)."""
-    got, ref = got.double(), ref.double()
-    scale = ref.abs().amax(-1, keepdim=True).clamp_min(floor * ref.abs().max().item() + 1e-300)
-    _within((got - ref).abs(), tol * scale.expand_as(ref), what)
-
-
-# ---- the dropout keep mask, restated from train.hip's keep_scale ---------------------------------------------------------------
-def keep_scale(seed, idx, p):
-    """fp32 factor of element `idx` (uint64 array): 0 where dropped, fl(1 / (1 - p)) where kept, 1 everywhere at p = 0."""
-    idx = np.asarray(idx, dtype=np.uint64)
-    if p <= 0:
-        return np.ones(idx.shape, np.float32)
-    with np.errstate(over="ignore"):
-        z = idx + np.uint64((int(seed) & 0xFFFFFFFF) << 32) + np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    u = (z >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-    pf = np.float32(p)
-    return np.where(u < pf, np.float32(0), np.float32(1) / (np.float32(1) - pf)).astype(np.float32)
 
 
 def test_keep_scale_restatement_is_splitmix64():
