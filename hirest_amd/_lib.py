@@ -164,6 +164,21 @@ class JointEncoderX3(C.Structure):
                [(n, C.c_void_p) for n in ("emb_w2", "emb_b", "pos", "emb_ln_g", "emb_ln_b")] + [("layer", C.POINTER(JointLayerX3))]
 
 
+class WhisperLayerX3(C.Structure):
+    """hirest_whisper_layer_x3 (include/hirest_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("attn_ln_g", "attn_ln_b", "qkv_w2", "qkv_b", "out_w2", "out_b", "mlp_ln_g", "mlp_ln_b", "fc1_w2", "fc1_b",
+                                          "fc2_w2", "fc2_b")]
+
+
+class WhisperEncoderX3(C.Structure):
+    """hirest_whisper_encoder_x3 (include/hirest_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint64)] + [(n, C.c_int32) for n in ("layers", "heads", "width", "ffn", "ctx", "flags")] + \
+               [("ln_eps", C.c_float), ("layer", C.POINTER(WhisperLayerX3)), ("ln_post_g", C.c_void_p), ("ln_post_b", C.c_void_p)]
+
+
+WHISPER_X3_GELU_PASS, WHISPER_X3_AUTO_TILES = 1, 2     # HIREST_WHISPER_X3_*: measurement switches of the descriptor
+
+
 class ColsumItem(C.Structure):
     """hirest_colsum_item (include/hirest_hip.h)."""
     _fields_ = [("x", C.c_void_p), ("row_weight", C.c_void_p), ("row_select", C.c_void_p), ("out", C.c_void_p), ("ldx", C.c_int64),
@@ -461,6 +476,10 @@ _SIGNATURES = {
     "hirest_log_mel": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),
     "hirest_mel_to_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "hirest_whisper_encoder_x3_workspace_bytes": (C.c_size_t, [C.POINTER(WhisperEncoderX3), C.c_int32]),
+    "hirest_whisper_encoder_x3_gemm_args": (C.c_int, [C.POINTER(WhisperEncoderX3), C.c_int32, C.c_int32, C.POINTER(GemmArgs)]),
+    "hirest_whisper_encoder_x3_forward": (C.c_int, [C.POINTER(WhisperEncoderX3), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p]),
     "hirest_attention_f32_decode_inplace": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                                       C.c_float, C.c_void_p]),

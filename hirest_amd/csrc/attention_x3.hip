@@ -256,6 +256,11 @@ static int attention_x3(const float* q, int64_t ldq, const float* k, const float
     // exactly nine waves of queries (the ViT's 257 tokens): one workgroup per (frame, head) stages every K / V tile once instead of three
     // times (5.5 -> 2.2 GB read per 512-frame launch; 3.21 -> 3.07 ms at 1024 frames: the kernel is bound by instruction issue, not by bytes)
     if (waves == 9 && B * H >= 512) nw = 9;
+    // long sequences (the Whisper encoder's 1500 positions = 47 waves; nothing else reaches 32 waves): eight-wave workgroups stage a
+    // (window, head)'s keys 6 times instead of 12, at 48 wave slots either way — once they fill the 256 CUs.  small.en, 12 heads: 8 and
+    // 16 windows 0.6 % and 1.8 % of the encoder faster than with four waves; ONE window is 72 workgroups, and 144 of four waves are 3.7 %
+    // faster there (profiles/whisper_enc_x3.txt).  Same bits either way.
+    if (waves >= 32 && (int64_t)B * H * ((waves + 7) / 8) >= 256) nw = 8;
     if (g_x3_waves) nw = g_x3_waves;
     const dim3 grid((unsigned)((int64_t)B * H * ((waves + nw - 1) / nw)));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

@@ -20,7 +20,8 @@ it closer to the exact spectrogram than the fp32 ``torch.stft`` Whisper itself r
 ``hirest_gemm_f32`` products over an overlapping view of channel-last rows with one zero row around each clip (``hirest_mel_to_rows``):
 row m of the A operand starts ``stride * C`` floats after row m - 1 and is ``3 C`` long, so no im2col copy exists; the second one adds
 the positional embedding in its epilogue, after the GELU.  The blocks run on the exact-fp32 kernels of the other encoders
-(``hirest_gemm_f32`` / ``hirest_gemm_f32_ln`` / ``hirest_attention_f32`` / ``hirest_layernorm``).  There is no CPU path: ``forward`` and
+(``hirest_gemm_f32`` / ``hirest_gemm_f32_ln`` / ``hirest_attention_f32`` / ``hirest_layernorm``) or, after
+``set_precision("bf16x3")``, on split bf16 operands in one C call (``hirest_whisper_encoder_x3_forward``).  There is no CPU path: ``forward`` and
 ``log_mel_spectrogram`` raise off-GPU.  A local ``.pt`` or model directory is required: nothing is downloaded.
 
 What the two halves share is written once: the size and key tables of both checkpoint schemas (``_dims``, ``_canonical``, by side), the
@@ -283,10 +284,12 @@ class _FrozenWeights(nn.Module):
             # parameter names cannot hold dots: keep the checkpoint's name with '/'
             self.register_parameter(k.replace(".", "/"), nn.Parameter(sd[k].detach().float().clone(), requires_grad=False))
         self._cache = None
+        self._cache_kinds = {}
 
-    # nn.Module plumbing: any move / cast invalidates the fused-weight cache
+    # nn.Module plumbing: any move / cast invalidates the fused-weight cache, every kind of it together
     def _apply(self, fn, *a, **k):
         self._cache = None
+        self._cache_kinds = {}
         return super()._apply(fn, *a, **k)
 
     def _p(self, name: str) -> torch.Tensor:
@@ -305,6 +308,14 @@ class _FrozenWeights(nn.Module):
             self._require_gpu()
             self._cache = self.prepared_weights()
         return self._cache
+
+    def _w_kind(self, kind: str, prepare):
+        """The preparation of a further kernel set (``AudioEncoder``: ``'x3'``) beside the fp32 one of ``_w()``: built once by
+        ``prepare()``, kept next to it, dropped with it."""
+        if kind not in self._cache_kinds:
+            self._require_gpu()
+            self._cache_kinds[kind] = prepare()
+        return self._cache_kinds[kind]
 
 
 _LN_EPS = 1e-5                 # of every LayerNorm of both halves
@@ -347,10 +358,17 @@ class AudioEncoder(_FrozenWeights):
 
     ``dims_or_config``: OpenAI's ``ModelDimensions`` / ``dims`` dict or a Hugging Face ``config.json`` dict; ``state_dict`` in either
     schema (``encoder.blocks.i.attn.query ...`` or ``[model.]encoder.layers.i.self_attn.q_proj ...``; decoder tensors are ignored).
-    The weights are frozen parameters under OpenAI's names; the fused operands are built on first use and dropped on any move / cast."""
+    The weights are frozen parameters under OpenAI's names; the fused operands are built on first use and dropped on any move / cast.
+
+    ``set_precision("bf16x3")`` runs the blocks and ``ln_post`` on split operands (csrc/whisper_enc_x3.hip: every weight product and both
+    attention products from bf16 hi + lo splits, three bf16 MFMAs each, fp32 accumulation; residual stream, LayerNorm and softmax fp32);
+    the stem stays exact fp32 in both.  The default, ``"fp32"``, is exact fp32 throughout.  What is set is what runs, at every batch size."""
+
+    PRECISIONS = ("fp32", "bf16x3")
 
     def __init__(self, dims_or_config, state_dict: Dict[str, torch.Tensor]):
         super().__init__()
+        self._precision = "fp32"
         self.dims = _dims(dims_or_config, "audio")
         d = self.dims
         self.n_mels, self.ctx, self.width, self.heads, self.layers, self.ffn = (d[k] for k in ("n_mels", "ctx", "width", "heads", "layers", "ffn"))
@@ -392,6 +410,57 @@ class AudioEncoder(_FrozenWeights):
                 c[p + n] = f(p + n)
         return c
 
+    @property
+    def precision(self) -> str:
+        return self._precision
+
+    def set_precision(self, precision: str) -> "AudioEncoder":
+        """``"fp32"`` (default) or ``"bf16x3"``.  Prepares nothing and needs no GPU: the operands of a precision are built on its first
+        use and stay resident beside the other's."""
+        if precision not in self.PRECISIONS:
+            raise ValueError(f"precision {precision!r}: one of {', '.join(self.PRECISIONS)} expected")
+        if precision == "bf16x3" and (self.width % 32 or self.ffn % 32):
+            raise NotImplementedError(f"bf16x3: width {self.width} / ffn {self.ffn} are not multiples of 32 (the split operand's blocks)")
+        self._precision = precision
+        return self
+
+    def prepared_weights_x3(self) -> Dict[str, object]:
+        """The descriptor of csrc/whisper_enc_x3.hip (``hirest_whisper_encoder_x3``): per block the four weights split into bf16 hi | lo
+        (``ops.split2``; the fused query | key | value with a zero key bias and NO head padding — the split-operand attention takes the
+        head width as it is), the fp32 LayerNorm and bias vectors of the fp32 preparation, and ``ln_post``."""
+        c = self._w()
+        f = lambda n: self._p(n).detach().float().contiguous()
+        keep, layers = [], (_lib.WhisperLayerX3 * self.layers)()
+        no_bias = torch.zeros(self.width, device=self.device)
+        for i in range(self.layers):
+            p = f"blocks.{i}."
+            qkv_w2 = ops.split2(torch.cat([f(p + f"attn.{n}.weight") for n in ("query", "key", "value")]))
+            qkv_b = torch.cat([f(p + "attn.query.bias"), no_bias, f(p + "attn.value.bias")])
+            out_w2, fc1_w2, fc2_w2 = (ops.split2(f(p + n)) for n in ("attn.out.weight", "mlp.0.weight", "mlp.2.weight"))
+            t = {"attn_ln_g": c[p + "attn_ln.weight"], "attn_ln_b": c[p + "attn_ln.bias"], "qkv_w2": qkv_w2, "qkv_b": qkv_b,
+                 "out_w2": out_w2, "out_b": c[p + "attn.out.bias"], "mlp_ln_g": c[p + "mlp_ln.weight"], "mlp_ln_b": c[p + "mlp_ln.bias"],
+                 "fc1_w2": fc1_w2, "fc1_b": c[p + "mlp.0.bias"], "fc2_w2": fc2_w2, "fc2_b": c[p + "mlp.2.bias"]}
+            keep.append(t)                                           # (the device tensors behind the raw pointers)
+            for name, v in t.items():
+                setattr(layers[i], name, v.data_ptr())
+        desc = _lib.WhisperEncoderX3(struct_size=C.sizeof(_lib.WhisperEncoderX3), layers=self.layers, heads=self.heads, width=self.width,
+                                     ffn=self.ffn, ctx=self.ctx, flags=0, ln_eps=_LN_EPS, layer=layers,
+                                     ln_post_g=c["ln_post_w"].data_ptr(), ln_post_b=c["ln_post_b"].data_ptr())
+        return {"desc": desc, "layers": layers, "keep": keep, "fp32": c}
+
+    def _blocks_x3(self, x: torch.Tensor, B: int) -> torch.Tensor:
+        """The blocks and ln_post of ``x`` [B ctx, width] in one C call; its scratch is per stream (``ops.stream_workspace``)"""
+        lib = _lib.load()
+        desc = C.byref(self._w_kind("x3", self.prepared_weights_x3)["desc"])
+        need = lib.hirest_whisper_encoder_x3_workspace_bytes(desc, B)
+        if need == 0:
+            raise NotImplementedError(f"bf16x3: no kernel for width {self.width} / heads {self.heads} / ffn {self.ffn}")
+        ws, wsb = ops.stream_workspace(x.device, need, "whisper_encoder_x3")
+        out = torch.empty_like(x)
+        _lib.check(lib.hirest_whisper_encoder_x3_forward(desc, x.data_ptr(), B, out.data_ptr(), ws, wsb, ops.stream_ptr()),
+                   "hirest_whisper_encoder_x3_forward")
+        return out
+
     # ------------------------------------------------------------------------------------------------------------
 
     def _stem(self, mel: torch.Tensor) -> torch.Tensor:
@@ -431,6 +500,8 @@ class AudioEncoder(_FrozenWeights):
             x = self._stem(mel)
             if return_stem:
                 return x.view(B, ctx, self.width)
+            if self._precision == "bf16x3":
+                return self._blocks_x3(x, B).view(B, ctx, self.width)
             for i in range(self.layers):
                 p = f"blocks.{i}."
                 qkv = _ln_linear(x, c[p + "attn_ln.weight"], c[p + "attn_ln.bias"], c[f"qkv_w.{i}"], c[f"qkv_b.{i}"])
@@ -446,12 +517,19 @@ class AudioEncoder(_FrozenWeights):
     embed_audio = forward
 
 
-def load_encoder(path: str, device: Optional[Union[str, torch.device]] = None) -> AudioEncoder:
+def _load_precision(precision: Optional[str]) -> str:
+    """The encoder precision of a load: the keyword, else ``HIREST_WHISPER_PRECISION`` (so that an unmodified driver reaches the mode, as
+    ``HIREST_PRECISION`` does for the towers), else ``"fp32"``"""
+    return precision if precision is not None else (os.environ.get("HIREST_WHISPER_PRECISION") or "fp32")
+
+
+def load_encoder(path: str, device: Optional[Union[str, torch.device]] = None, *, precision: Optional[str] = None) -> AudioEncoder:
     """An OpenAI ``.pt`` checkpoint (a dict with ``dims`` and ``model_state_dict``) or a Hugging Face model directory (``config.json`` +
     ``model.safetensors`` / ``pytorch_model.bin``), picked by what ``path`` is.  A model name (``'small.en'``, ``'openai/whisper-small.en'``)
-    raises FileNotFoundError: nothing is downloaded."""
+    raises FileNotFoundError: nothing is downloaded.  ``precision``: ``AudioEncoder.set_precision``'s (default: the environment's
+    ``HIREST_WHISPER_PRECISION``, else ``"fp32"``); a bad name raises ValueError here."""
     dims, sd, _ = _read_checkpoint(path, " (no network access: download the model beforehand and pass its path)")
-    enc = AudioEncoder(dims, sd)
+    enc = AudioEncoder(dims, sd).set_precision(_load_precision(precision))
     return enc.to(device) if device is not None else enc
 
 
@@ -1041,7 +1119,8 @@ class DecodingOptions:
     suppress_tokens: Optional[Union[str, Iterable[int]]] = "-1"
     without_timestamps: bool = False
     max_initial_timestamp: Optional[float] = 1.0
-    fp16: bool = True                         # accepted and ignored: this path is exact fp32
+    fp16: bool = True                         # accepted and ignored: the decoder is exact fp32; the encoder's precision is the model's
+                                              # (Whisper.set_precision / load_model(precision=) / HIREST_WHISPER_PRECISION)
     seed: int = 0                             # of the counter-based generator the categorical draws come from (not Whisper's: it draws from torch's)
     monotonic_timestamps: bool = True         # current Whisper's rule that timestamps do not decrease
 
@@ -1420,6 +1499,15 @@ class Whisper(nn.Module):
     def is_multilingual(self) -> bool:
         return self.dims["n_vocab"] >= 51865
 
+    @property
+    def precision(self) -> str:
+        return self.encoder.precision
+
+    def set_precision(self, precision: str) -> "Whisper":
+        """The audio encoder's precision (``AudioEncoder.set_precision``: ``"fp32"`` | ``"bf16x3"``); the decoder is exact fp32 always"""
+        self.encoder.set_precision(precision)
+        return self
+
     def embed_audio(self, mel: torch.Tensor) -> torch.Tensor:
         return self.encoder(mel)
 
@@ -1442,13 +1530,15 @@ class Whisper(nn.Module):
         return transcribe_many(self, audios, **kw)
 
 
-def load_model(path: str, device: Optional[Union[str, torch.device]] = None, tokenizer: Optional[Union[str, Tokenizer]] = None) -> Whisper:
+def load_model(path: str, device: Optional[Union[str, torch.device]] = None, tokenizer: Optional[Union[str, Tokenizer]] = None, *,
+               precision: Optional[str] = None) -> Whisper:
     """A local OpenAI ``.pt`` checkpoint or a Hugging Face model directory -> ``Whisper``.  There are no model names and no downloads: a
     bare name (``'small.en'``) raises FileNotFoundError saying so.  ``tokenizer``: a ``Tokenizer`` or a directory with ``vocab.json`` and
-    ``merges.txt`` (default: the model directory itself when it has them; a ``.pt`` carries no vocabulary)."""
+    ``merges.txt`` (default: the model directory itself when it has them; a ``.pt`` carries no vocabulary).  ``precision``: the audio
+    encoder's (``Whisper.set_precision``; default: the environment's ``HIREST_WHISPER_PRECISION``, else ``"fp32"``)."""
     dims, sd, is_dir = _read_checkpoint(path, ": model names are not resolved and nothing is downloaded (no network access) — download "
                                               "the model beforehand and pass its path")
-    model = Whisper(dims, sd)
+    model = Whisper(dims, sd).set_precision(_load_precision(precision))
     if is_dir and tokenizer is None and os.path.isfile(os.path.join(path, "vocab.json")):
         tokenizer = path
     if isinstance(tokenizer, (str, os.PathLike)):

@@ -1266,6 +1266,41 @@ int hirest_log_mel(const float* audio, int64_t n, int64_t padding, const float* 
  * K = 3 C). */
 int hirest_mel_to_rows(const float* mel, float* rows, int32_t B, int32_t n_mels, int32_t T, void* stream);
 
+/* The encoder's blocks at the split-operand precision ("bf16x3"; csrc/whisper_enc_x3.hip, AudioEncoder.set_precision): the
+ * pre-LN blocks of whisper/model.py::AudioEncoder and ln_post with the four weight products of a block (HIREST_GEMM_X3) and both attention
+ * products (hirest_attention_x3_qkv_split2) formed from bf16 hi + lo splits of both fp32 operands, three bf16 MFMAs per product, fp32
+ * accumulation.  The residual stream, the LayerNorm statistics (eps inside the root) and the softmax are fp32; the stem stays the caller's
+ * (exact fp32).  One C call issues layers x 7 launches + ln_post.  width % 32 == 0, ffn % 32 == 0, width <= 2048, head width % 4 == 0 and
+ * <= 96 (HIREST_E_SHAPE otherwise).  A window's result does not depend on the other windows of the call: every product runs on one kernel
+ * family with one K order at every row count.  Weights are split once with hirest_split2_bf16 ([N, K] fp32 -> [N, 2K] bf16). */
+typedef struct hirest_whisper_layer_x3 {
+    const float* attn_ln_g; const float* attn_ln_b;       /* attn_ln                                                                        */
+    const hirest_bf16* qkv_w2; const float* qkv_b;        /* query | key | value rows [3 width, 2 width] split, bias [3 width] (key part: 0) */
+    const hirest_bf16* out_w2; const float* out_b;        /* attn.out [width, 2 width]                                                      */
+    const float* mlp_ln_g; const float* mlp_ln_b;         /* mlp_ln                                                                         */
+    const hirest_bf16* fc1_w2; const float* fc1_b;        /* mlp.0 [ffn, 2 width] (+ erf-GELU)                                              */
+    const hirest_bf16* fc2_w2; const float* fc2_b;        /* mlp.2 [width, 2 ffn]                                                           */
+} hirest_whisper_layer_x3;
+enum { HIREST_WHISPER_X3_GELU_PASS = 1,    /* measurement: fc1 writes fp32 and GELU + split run as a hirest_split2_bf16(act = 1) pass           */
+       HIREST_WHISPER_X3_AUTO_TILES = 2 }; /* measurement: hirest_gemm_bf16's own choice between gemm_t128x3 and gemm_pp256x3 per product
+                                            * (another K order for large products: results then depend on the number of windows)            */
+typedef struct hirest_whisper_encoder_x3 {
+    uint64_t struct_size;
+    int32_t layers, heads, width, ffn, ctx;
+    int32_t flags;                                        /* 0; HIREST_WHISPER_X3_* for A/B timing (per descriptor: no process-wide state)  */
+    float ln_eps;                                         /* 1e-5                                                                           */
+    const hirest_whisper_layer_x3* layer;                 /* HOST array [layers]                                                            */
+    const float* ln_post_g; const float* ln_post_b;
+} hirest_whisper_encoder_x3;
+size_t hirest_whisper_encoder_x3_workspace_bytes(const hirest_whisper_encoder_x3* e, int32_t B);
+/* The hirest_gemm_bf16 call the forward makes for product `which` of a block at B windows — M, N, K, strides, epilogue and flags as it
+ * passes them, the pointers NULL: what hirest_gemm_dispatch_name is asked to name the kernel of (host logic only, no GPU needed). */
+enum { HIREST_WHISPER_X3_QKV = 0, HIREST_WHISPER_X3_OUT = 1, HIREST_WHISPER_X3_FC1 = 2, HIREST_WHISPER_X3_FC2 = 3 };
+int hirest_whisper_encoder_x3_gemm_args(const hirest_whisper_encoder_x3* e, int32_t B, int32_t which, hirest_gemm_args* out);
+/* x fp32 [B * ctx, width] (the stem's output, positional embedding added; left unchanged) -> out fp32 [B * ctx, width].  Pointers 16-B aligned. */
+int hirest_whisper_encoder_x3_forward(const hirest_whisper_encoder_x3* e, const float* x, int32_t B, float* out, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Whisper text decoder (csrc/whisper_dec.hip, hirest_amd/whisper.py): a sampling step's attention kernels, its tail and
  * the step itself.  Prefill runs on hirest_gemm_f32(_ln) / hirest_attention_f32_qkv.

@@ -10,6 +10,8 @@ reference's ``extraction/whisper_ASR/extract_ASR.py``, our own code against our 
 model then detects each file's language on its first 30 seconds.  ``--task translate`` writes English subtitles for any language.
 ``--word_timestamps`` also writes ``<name>.json`` beside each ``.srt``: the segments with their words (``word``, ``start``, ``end``,
 ``probability``); the ``.srt`` is what it is without the option.
+``--precision bf16x3`` runs the audio encoder's blocks on split bf16 operands (the reference runs them at fp16); without
+it the environment's ``HIREST_WHISPER_PRECISION`` decides, else fp32.
 """
 import argparse
 import json
@@ -48,13 +50,15 @@ def main(argv=None):
     ap.add_argument("--files_in_flight", type=int, default=whisper.FILES_IN_FLIGHT,
                     help="files whose current windows are decoded together (whisper.transcribe_many); 1: one file at a time (whisper.transcribe)")
     ap.add_argument("--word_timestamps", action="store_true", help="align every window's words (whisper.timing) and write <name>.json")
+    ap.add_argument("--precision", type=str, default=None, choices=list(whisper.AudioEncoder.PRECISIONS),
+                    help="the audio encoder's precision (default: HIREST_WHISPER_PRECISION, else fp32); the decoder is exact fp32 always")
     args = ap.parse_args(argv)
     if args.files_in_flight < 1:
         ap.error("--files_in_flight must be at least 1")
     print(args)
 
-    model = whisper.load_model(args.model, args.device, tokenizer=args.tokenizer).eval()
-    print("Model loaded: ", args.model, "at device", model.device)
+    model = whisper.load_model(args.model, args.device, tokenizer=args.tokenizer, precision=args.precision).eval()
+    print("Model loaded: ", args.model, "at device", model.device, "encoder precision", model.precision)
 
     # the reference's option block.  Its first temperature is 0.15, so every window is sampled (best_of candidates) and the beam options
     # are never used: transcribe() drops them above temperature 0.

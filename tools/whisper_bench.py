@@ -11,7 +11,12 @@ that call; the step leg: the one ``hirest_whisper_decode_step_rows`` call inside
 ``hirest_whisper_alignment_matrix`` and ``hirest_dtw_f32`` for one window at small.en's shape (12 layers, 72 selected heads, 1500 keys)
 with 50 and 220 tokens, each timed on its own, beside the numpy restatement of both on the CPU (tests/_whisper_align_ref.py, fp32).
 
+``--precision fp32 bf16x3`` times the encoder leg at each named precision (``AudioEncoder.set_precision``), alternating per
+batch size; the FLOP count is the same, the fraction is of the 157-TFLOP/s fp32 peak for fp32 and of bf16 peak / 3 for bf16x3.
+``--x3-ab`` adds the bf16x3 encoder's A/B runs: GELU + split as a separate pass, the GEMMs' own tile choice, 4-wave attention workgroups.
+
     python tools/whisper_bench.py [--repeats 7] [--warmup 2] [--batches 1 8] [--legs encoder decode detect step align]
+                                  [--precision fp32] [--x3-ab]
                                   [--windows 1 2 4 8 16] [--prompt-len 0] [--detect_windows 1 16] [--align_tokens 50 220]
 """
 import argparse
@@ -27,6 +32,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hirest_amd import synth, whisper  # noqa: E402
 
 FP32_MFMA_PEAK = 157e12
+BF16_MFMA_PEAK = 2500e12                # dense bf16; a bf16x3 product is three bf16 MFMAs, so its yardstick is a third of this
+PEAKS = {"fp32": (FP32_MFMA_PEAK, "the fp32 MFMA peak"), "bf16x3": (BF16_MFMA_PEAK / 3, "bf16 MFMA peak / 3")}
 
 
 def spread(xs, scale=1e3, unit="ms"):
@@ -57,6 +64,55 @@ def timed(fn, repeats, warmup, min_window=0.25):
             fn()
         torch.cuda.synchronize()
         out.append((time.perf_counter() - t0) / inner)
+    return out
+
+
+def x3_ab(enc, mel, a):
+    """The bf16x3 encoder as shipped against each of its measurement switches (same arithmetic, other launches): GELU + split as a
+    separate pass over an fp32 hidden activation, hirest_gemm_bf16's own tile choice (gemm_pp256x3 for the large products), and the
+    attention with 4-wave workgroups instead of 8-wave ones.  Medians in ms; the shipped form is timed first and last."""
+    from hirest_amd import _lib
+    lib = _lib.load()
+    enc.set_precision("bf16x3")
+    enc(mel)
+    desc = enc._cache_kinds["x3"]["desc"]
+    out = {}
+
+    def run(name, flags=0, waves=0):
+        desc.flags = flags
+        lib.hirest_attention_x3_select_waves(waves)
+        try:
+            ts = timed(lambda: enc(mel), a.repeats, a.warmup)
+        finally:
+            desc.flags = 0
+            lib.hirest_attention_x3_select_waves(0)
+        out[name] = [round(x * 1e3, 4) for x in ts]
+        print(f"        x3 A/B B = {mel.shape[0]} {name:28s} {spread(ts)}")
+    run("shipped")
+    run("gelu_separate_pass", _lib.WHISPER_X3_GELU_PASS)
+    run("gemm_auto_tiles", _lib.WHISPER_X3_AUTO_TILES)
+    run("gemm_auto_tiles+gelu_pass", _lib.WHISPER_X3_AUTO_TILES | _lib.WHISPER_X3_GELU_PASS)
+    run("attention_4_waves", 0, 4)
+    run("attention_3_waves", 0, 3)
+    run("shipped_again")
+    # the per-kernel split of the shipped form from the library's per-launch event records (one call)
+    lib.hirest_profile_enable(1)
+    enc(mel)
+    torch.cuda.synchronize()
+    recs = (_lib.ProfRecord * 4096)()
+    n = lib.hirest_profile_collect(recs, len(recs))
+    lib.hirest_profile_enable(0)
+    groups = {}
+    for r in recs[:max(n, 0)]:
+        g = groups.setdefault((r.kind, r.tag, r.d0, r.d1, r.d2), [0, 0.0])
+        g[0] += 1
+        g[1] += r.ms
+    kernels = []
+    for (kind, tag, d0, d1, d2), (count, ms) in sorted(groups.items(), key=lambda kv: -kv[1][1]):
+        kernels.append({"kind": {0: "gemm", 1: "attention", 2: "rows"}.get(kind, kind), "tag": tag, "dims": [d0, d1, d2], "launches": count,
+                        "ms_per_call": round(ms, 5), "ms_per_launch": round(ms / count, 5)})
+        print(f"        x3 kernels B = {mel.shape[0]} {kernels[-1]}")
+    out["kernels"] = kernels
     return out
 
 
@@ -227,6 +283,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--precision", nargs="+", choices=list(whisper.AudioEncoder.PRECISIONS), default=["fp32"],
+                    help="encoder leg: the precisions to time, in this order for every batch size")
+    ap.add_argument("--x3-ab", action="store_true", help="encoder leg: also the bf16x3 encoder under each of its measurement switches")
     ap.add_argument("--legs", nargs="+", choices=["encoder", "decode", "detect", "step", "align"], default=["encoder", "decode"])
     ap.add_argument("--windows", type=int, nargs="+", default=[1, 2, 4, 8, 16], help="windows per decode_many() call of the decode leg")
     ap.add_argument("--prompt-len", type=int, default=0, help="previous tokens in every window's prompt of the decode leg (0: none, as before)")
@@ -251,21 +310,32 @@ def main():
     mel1 = whisper.log_mel_spectrogram(audio)
     for B in a.batches:
         mel = mel1[None].expand(B, -1, -1).contiguous()
-        stem = timed(lambda: enc(mel, return_stem=True), a.repeats, a.warmup)
-        whole = timed(lambda: enc(mel), a.repeats, a.warmup)
-        t_front, t_stem, t_whole = (statistics.median(x) for x in (front, stem, whole))
-        t_blocks = t_whole - t_stem
-        per_window = t_front + t_whole / B
-        print(f"B = {B}: encoder {spread(whole)}, of which stem {spread(stem)}")
-        print(f"        windows/s {1.0 / per_window:.1f} with one front-end call per window; shares: front end {t_front / per_window:.3f}, "
-              f"stem {t_stem / B / per_window:.3f}, blocks {t_blocks / B / per_window:.3f}")
-        print(f"        encoder {B * (stem_flop + block_flop) / t_whole / 1e12:.1f} TFLOP/s = {B * (stem_flop + block_flop) / t_whole / FP32_MFMA_PEAK:.3f} of the "
-              f"fp32 MFMA peak (stem {B * stem_flop / t_stem / 1e12:.1f}, blocks {B * block_flop / t_blocks / 1e12:.1f} TFLOP/s); a whole-call "
-              "rate, launches and row operations included")
-        result["batches"][str(B)] = {"encoder_ms": [round(x * 1e3, 4) for x in whole], "stem_ms": [round(x * 1e3, 4) for x in stem],
-                                     "windows_per_s": 1.0 / per_window, "front_end_share": t_front / per_window,
-                                     "encoder_tflops": B * (stem_flop + block_flop) / t_whole / 1e12,
-                                     "fraction_of_fp32_mfma_peak": B * (stem_flop + block_flop) / t_whole / FP32_MFMA_PEAK}
+        for precision in a.precision:
+            enc.set_precision(precision)
+            peak, peak_name = PEAKS[precision]
+            stem = timed(lambda: enc(mel, return_stem=True), a.repeats, a.warmup)
+            whole = timed(lambda: enc(mel), a.repeats, a.warmup)
+            t_front, t_stem, t_whole = (statistics.median(x) for x in (front, stem, whole))
+            t_blocks = t_whole - t_stem
+            per_window = t_front + t_whole / B
+            print(f"B = {B} {precision}: encoder {spread(whole)}, of which stem {spread(stem)} ({t_stem / t_whole:.3f} of it)")
+            print(f"        windows/s {1.0 / per_window:.1f} with one front-end call per window; shares: front end {t_front / per_window:.3f}, "
+                  f"stem {t_stem / B / per_window:.3f}, blocks {t_blocks / B / per_window:.3f}")
+            print(f"        encoder {B * (stem_flop + block_flop) / t_whole / 1e12:.1f} TFLOP/s = {B * (stem_flop + block_flop) / t_whole / peak:.3f} of "
+                  f"{peak_name} (stem {B * stem_flop / t_stem / 1e12:.1f}, blocks {B * block_flop / t_blocks / 1e12:.1f} TFLOP/s = "
+                  f"{B * block_flop / t_blocks / peak:.3f}); a whole-call rate, launches and row operations included")
+            entry = {"encoder_ms": [round(x * 1e3, 4) for x in whole], "stem_ms": [round(x * 1e3, 4) for x in stem],
+                     "windows_per_s": 1.0 / per_window, "front_end_share": t_front / per_window,
+                     "encoder_tflops": B * (stem_flop + block_flop) / t_whole / 1e12}
+            if precision == "fp32":                                    # (the keys this tool has always printed)
+                entry["fraction_of_fp32_mfma_peak"] = B * (stem_flop + block_flop) / t_whole / peak
+                result["batches"][str(B)] = entry
+            else:
+                entry["fraction_of_bf16_mfma_peak_over_3"] = B * (stem_flop + block_flop) / t_whole / peak
+                result.setdefault("batches_" + precision, {})[str(B)] = entry
+        if a.x3_ab:
+            result.setdefault("x3_ab", {})[str(B)] = x3_ab(enc, mel, a)
+    enc.set_precision("fp32")
     for leg, fn in (("decode", decode_leg), ("detect", detect_leg), ("step", step_leg), ("align", align_leg)):
         if leg in a.legs:
             result[leg] = fn(a, dev)
