@@ -15,11 +15,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libhirest_hip.so")
-SOURCES = ["gemm.hip", "joint_x3.hip", "attention.hip", "elementwise.hip", "score.hip", "tower.hip", "tower_f32.hip", "tower_x3.hip", "attention_x3.hip", "profile.hip", "joint.hip", "train.hip", "train_block.hip", "optim.hip", "optim_capturable.hip", "caption.hip", "preprocess.hip", "eval.hip", "cascade.hip", "jpeg.hip", "batch.hip", "bertscore.hip", "valid.hip", "audio.hip", "whisper_dec.hip", "whisper_align.hip", "whisper_prefill.hip", "whisper_enc_x3.hip"]
+SOURCES = ["gemm.hip", "joint_x3.hip", "attention.hip", "attention_long.hip","elementwise.hip", "score.hip", "tower.hip", "tower_f32.hip", "tower_x3.hip", "attention_x3.hip", "profile.hip", "joint.hip", "train.hip", "train_block.hip", "optim.hip", "optim_capturable.hip", "caption.hip", "preprocess.hip", "eval.hip", "cascade.hip", "jpeg.hip", "batch.hip", "bertscore.hip", "valid.hip", "audio.hip", "whisper_dec.hip", "whisper_align.hip", "whisper_prefill.hip", "whisper_enc_x3.hip"]
 ARCH = "gfx950"
 # attention's softmax only ever sees finite values (masked scores are -3e38, not -inf): dropping NaN handling removes
 # the canonicalising v_max the compiler otherwise puts in front of every fmaxf on an MFMA result
 EXTRA_FLAGS = {"attention.hip": ["-ffinite-math-only"],
+               "attention_long.hip": ["-ffinite-math-only"],
                # Pillow-exact weight tables (host doubles) and the reference's (x/255-mean)/std: no fused multiply-adds
                "preprocess.hip": ["-ffp-contract=off"],
                # evaluate.py's double-precision interval arithmetic, operation for operation

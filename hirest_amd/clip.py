@@ -111,7 +111,8 @@ class OpenAIVisionTower(_Tower):
                 _lib.check(lib.hirest_vision_forward(desc, x[s:s + n].data_ptr(), code, n, out[s:s + n].data_ptr(), ws.data_ptr(),
                                                      ws.numel(), 0, ops.stream_ptr()), "hirest_vision_forward")
         wsb = lib.hirest_vision_workspace_bytes_f32 if f32 else lib.hirest_vision_workspace_bytes
-        self._run_calls(B, self.max_frames_per_call, False, lambda n: wsb(desc, n), call, x.device)
+        limit = self.max_frames_per_call if f32 else self._frames_limit(self.max_frames_per_call, T)
+        self._run_calls(B, limit, False, lambda n: wsb(desc, n), call, x.device)
         if self.pip_head:
             # the pip `clip` package's head (openai/CLIP @ a9b1bf5, model.py VisionTransformer.forward: ln_post(x[:, 0, :]) @ proj):
             # LayerNorm and projection act per token, so it is row 0 of what the kernel computed for every token

@@ -73,13 +73,26 @@ int gemm(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bi
     return hirest_gemm_bf16(&a, stream);
 }
 
+// Attention of a vision block: sequences the short kernels hold on chip (T <= 272) take them, unchanged; longer ones with 64-wide heads
+// (ViT-L/14@336px: 577 tokens) take the streaming kernel of attention_long.hip.  Anything else is refused by the short entry, as before.
+// q_rows: 0 = every query row.  (tests/test_attention_long_host.py restates this rule.)
+inline bool vision_attention_long(int T, int dh) { return T > 272 && dh == 64; }
+
+int vision_attention(const hirest_bf16* qkv, hirest_bf16* out, int B, int T, int heads, int dh, int q_rows, void* stream) {
+    const float scale = 1.0f / sqrtf((float)dh);
+    if (vision_attention_long(T, dh)) return hirest_attention_bf16_long(qkv, out, B, T, heads, dh, scale, q_rows, stream);
+    if (q_rows) return hirest_attention_bf16_rows(qkv, out, B, T, heads, dh, scale, 0, q_rows, stream);
+    return hirest_attention_bf16(qkv, out, B, T, heads, dh, scale, 0, stream);
+}
+
 // one pre-LN block: x += proj(attn(LN1 x)); x += fc2(act(fc1(LN2 x)))
 int run_block(const hirest_block_weights& w, float* x, hirest_bf16* h, hirest_bf16* big, int B, int T, int D, int heads,
               int dh, int Dm, float eps, int act, int causal, void* stream) {
     const int M = B * T;
     CHECK(hirest_layernorm(x, D, nullptr, w.ln1_g, w.ln1_b, eps, h, D, 0, M, D, stream));
     CHECK(gemm(h, D, w.qkv_w, D, w.qkv_b, big, 3 * D, M, 3 * D, D, HIREST_EPI_BIAS_BF16, stream));
-    CHECK(hirest_attention_bf16(big, h, B, T, heads, dh, 1.0f / sqrtf((float)dh), causal, stream));
+    if (causal) CHECK(hirest_attention_bf16(big, h, B, T, heads, dh, 1.0f / sqrtf((float)dh), 1, stream));   // text tower: T <= 77
+    else CHECK(vision_attention(big, h, B, T, heads, dh, 0, stream));
     CHECK(gemm(h, D, w.proj_w, D, w.proj_b, x, D, M, D, D, HIREST_EPI_BIAS_RESID_F32, stream));
     CHECK(hirest_layernorm(x, D, nullptr, w.ln2_g, w.ln2_b, eps, h, D, 0, M, D, stream));
     CHECK(gemm(h, D, w.fc1_w, D, w.fc1_b, big, Dm, M, Dm, D,
@@ -99,7 +112,7 @@ int run_block_lnfold(const hirest_block_weights& w, float* x, hirest_bf16* h, hi
     const int epi_res = xl ? HIREST_EPI_BIAS_RESID2_LNSTATS : HIREST_EPI_BIAS_RESID_LNSTATS_F32;
     CHECK(gemm(xb, D, w.qkv_wf, D, w.qkv_bf, big, 3 * D, M, 3 * D, D, HIREST_EPI_LNFOLD_BF16, stream, nullptr, 0, stats,
                const_cast<float*>(w.qkv_s)));
-    CHECK(hirest_attention_bf16(big, h, B, T, heads, dh, 1.0f / sqrtf((float)dh), 0, stream));
+    CHECK(vision_attention(big, h, B, T, heads, dh, 0, stream));
     CHECK(gemm(h, D, w.proj_w, D, w.proj_b, res, D, M, D, D, epi_res, stream, nullptr, 0, xb, part));
     CHECK(hirest_ln_stats_finalize(part, G, stats, eps, M, D, guard, stream));
     CHECK(gemm(xb, D, w.fc1_wf, D, w.fc1_bf, big, Dm, M, Dm, D, HIREST_EPI_LNFOLD_GELU_BF16, stream, nullptr, 0, stats,
@@ -125,7 +138,7 @@ int run_block_lnfold_cls(const hirest_block_weights& w, float* x, hirest_bf16* h
     const int64_t TD = (int64_t)T * D;
     CHECK(gemm(xb, D, w.qkv_wf, D, w.qkv_bf, big, 3 * D, M, 3 * D, D, HIREST_EPI_LNFOLD_BF16, stream, nullptr, 0, stats,
                const_cast<float*>(w.qkv_s)));
-    CHECK(hirest_attention_bf16_rows(big, h, B, T, heads, dh, 1.0f / sqrtf((float)dh), 0, 1, stream));
+    CHECK(vision_attention(big, h, B, T, heads, dh, 1, stream));
     if (xl) {
         // two-array residual stream: the CLS rows' hi / lo move into compact [B, D] arrays (the epilogue indexes its hi array by output
         // row), and the block updates those — the same arithmetic per row as run_block_lnfold's, so the result equals the unpruned block's

@@ -244,6 +244,17 @@ class _Tower(nn.Module):
         limit = max(1, int(limit))
         return -(-B // -(-B // limit)) if near_equal else min(B, limit)
 
+    @staticmethod
+    def _frames_limit(limit, tokens: int) -> int:
+        """Frames per bf16 tower call at ``tokens`` tokens per frame.  Up to 272 tokens: ``limit``, as ever.  Longer sequences (the
+        streaming attention; ViT-L/14@336px has 577) keep a call's rows B * T at what 2048 frames of 257 tokens have, the largest call
+        the short sequences make: 2048 frames of 577 tokens would be 1.18 M rows of up to 4 D columns, past 2^32 elements in the
+        widest workspace region.  At least 64 frames, the boundary where the tower switches kernels."""
+        limit = max(1, int(limit))
+        if tokens <= 272:
+            return limit
+        return min(limit, max(64, 2048 * 257 // int(tokens)))
+
     def _run_calls(self, B: int, limit, near_equal: bool, ws_bytes, call, device):
         """Run ``call(start, rows, workspace)`` over a batch of B rows in micro-batches (``_call_size``), all in one workspace that
         ``ws_bytes(rows)`` sizes for the largest of them.  Returns the (start, rows) of the calls."""
@@ -366,7 +377,8 @@ class VisionTower(_Tower):
         # Near-equal micro-batches instead of full ones + a remainder: with max_frames_per_call = 1024, 1030 frames run as
         # 515 + 515, not 1024 + 6, so a small tail never drops below the 64-frame boundary where the tower switches
         # kernels (folded LayerNorm / persistent attention) — every frame of a >= 64-frame call takes the same path.
-        step = self._call_size(B, self.max_frames_per_call, True)
+        limit = self._frames_limit(self.max_frames_per_call, self.num_tokens)
+        step = self._call_size(B, limit, True)
         code = ops._IN_DTYPES[image.dtype]
         self.last_fold_ratio = 0.0
         flags = (0 if self.prune_last_block else _lib.TOWER_NO_PRUNE) | (_lib.TOWER_F32_RESIDUAL if self.f32_residual else 0)
@@ -387,7 +399,7 @@ class VisionTower(_Tower):
                 g = lib.hirest_vision_guard_offset(desc, n)
                 if g != _NO_GUARD:
                     guards[s // step:s // step + 1].copy_(ws[g:g + 4].view(torch.float32))
-        spans = self._run_calls(B, self.max_frames_per_call, True, lambda n: lib.hirest_vision_workspace_bytes(desc, n), guarded, image.device)
+        spans = self._run_calls(B, limit, True, lambda n: lib.hirest_vision_workspace_bytes(desc, n), guarded, image.device)
         if guards is not None:
             ratios = guards.cpu().tolist()
             self.last_fold_ratio = max(ratios)

@@ -170,6 +170,16 @@ int hirest_attention_bf16(const hirest_bf16* qkv, hirest_bf16* out,
 int hirest_attention_bf16_rows(const hirest_bf16* qkv, hirest_bf16* out,
                                int32_t B, int32_t N, int32_t H, int32_t dh,
                                float scale, int32_t causal, int32_t q_rows, void* stream);
+/* softmax(scale * q k^T) v on a packed bf16 QKV activation, as hirest_attention_bf16 (same layout: qkv [B*N, 3*H*dh], out [B*N, H*dh]),
+ * for sequences the short kernels do not hold on chip.  1 <= N <= 4096, dh == 64, no mask.  q_rows: 0 = every query row; else only
+ * the output rows of queries [0, q_rows) of every frame are written and the rest of `out` is left untouched (all keys are still read).
+ * A streaming kernel (csrc/attention_long.hip): K and V pass through LDS in 64-key tiles under an online softmax; scores and softmax
+ * in fp32, P rounded to bf16 for the P.V MFMA, fp32 accumulation, bf16 store: the short kernels' contract, but not their bits (the
+ * running rescale rounds differently).  A frame's bits do not depend on B, on the other frames or on the run; they do not depend on
+ * q_rows either.  Null pointers, B <= 0, H <= 0, q_rows < 0: HIREST_E_BADARG; N outside [1, 4096] or dh != 64: HIREST_E_SHAPE; both
+ * before any launch.  qkv and out must be 16-byte aligned.  The vision tower takes this entry when T > 272 and head_dim == 64. */
+int hirest_attention_bf16_long(const hirest_bf16* qkv, hirest_bf16* out, int32_t B, int32_t N, int32_t H, int32_t dh,
+                               float scale, int32_t q_rows, void* stream);
 /* 1 = register-staged kernel with a transposed V image, 2 = LDS-DMA staging + hardware transpose reads, one workgroup
  * per (frame, head), 3 = 2's arithmetic in one persistent workgroup per frame (nine waves; used for 80 < N <= 272 tokens
  * and >= 64 frames; other shapes fall back to 2), 4 = 3 with twelve waves, 7 (default) = 3 with a tenth wave that issues all
@@ -1025,7 +1035,7 @@ int hirest_cascade_trim_gather(const float* vis, const float* asr, const int32_t
 enum hirest_prof_kind { HIREST_PROF_GEMM = 0, HIREST_PROF_ATTENTION = 1, HIREST_PROF_LAYERNORM = 2 };
 typedef struct hirest_prof_record {
     int32_t kind;        /* enum hirest_prof_kind */
-    int32_t tag;         /* GEMM: epilogue id; attention: causal flag; LN: 0 */
+    int32_t tag;         /* GEMM: epilogue id; attention: causal flag, or 2 = hirest_attention_bf16_long; LN: 0 */
     int64_t d0, d1, d2;  /* GEMM: M,N,K; attention: B*H, N, dh; LN: rows, D, 0 */
     float ms;            /* elapsed device time of this launch */
 } hirest_prof_record;
