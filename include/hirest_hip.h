@@ -477,10 +477,14 @@ int hirest_layernorm_split2(const float* x, int64_t ldx, const float* gamma, con
                             int32_t rows, int32_t D, void* stream);
 /* softmax(q k^T * scale) v for fp32 q / k / v rows (row strides ldq / ldkv, head h at column h * dh; out [B * Tq, H * dh]) with both products
  * formed from bf16 hi + lo splits (three bf16 MFMAs per product, fp32 accumulation), softmax in fp32: the attention of the bf16x3 tower
- * (vit_model.py:127-147; no mask).  dh % 4 == 0, dh <= 96; pointers 16-B aligned. */
+ * (vit_model.py:127-147; no mask).  Frame b's queries start at row b * Tq of q (and of out), its keys and values at row b * Tk of k and v;
+ * Tq and Tk are independent, and q, k and v may live in one packed allocation or in separate ones.  dh % 4 == 0, 4 <= dh <= 96; ldq and
+ * ldkv multiples of 4; q, k, v and out 16-B aligned (HIREST_E_SHAPE otherwise).  NULL pointers, B, Tq, Tk or H <= 0: HIREST_E_BADARG.
+ * Nothing is launched or written on a refusal.  Tested per element in tests/test_gpu_attention_x3_exact.py. */
 int hirest_attention_x3_qkv(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, float* out, int32_t B, int32_t Tq,
                             int32_t Tk, int32_t H, int32_t dh, float scale, void* stream);
-/* the same with the output stored as the split operand [B * Tq, 2 * H * dh] bf16 of the GEMM that follows ((H * dh) % 32 == 0) */
+/* the same with the output stored as the split operand [B * Tq, 2 * H * dh] bf16 of the GEMM that follows: (H * dh) % 32 == 0 and out2
+ * 8-B aligned (HIREST_E_SHAPE otherwise); bit-equal to hirest_split2_bf16 of the fp32 output */
 int hirest_attention_x3_qkv_split2(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, hirest_bf16* out2, int32_t B,
                                    int32_t Tq, int32_t Tk, int32_t H, int32_t dh, float scale, void* stream);
 /* Waves (32 queries each) per workgroup of the split-operand attention: 0 = automatic, 3 / 4 / 8 / 9 force.  Every workgroup stages all
@@ -488,7 +492,8 @@ int hirest_attention_x3_qkv_split2(const float* q, int64_t ldq, const float* k, 
 int hirest_attention_x3_select_waves(int32_t waves);
 /* Timing tool: workgroup 0 of every following launch stamps the shader clock at six points of every 32-key tile into device_buffer
  * ([tile < 16][wave < 16][8] int64: 0 top, 1 after the barrier, 6 the next tile's loads landed, 7 split + LDS stores done, 2 next fetch issued,
- * 3 scores issued, 4 softmax done, 5 P.V issued); NULL switches it off (default).  tools/attn_x3_trace.py. */
+ * 3 scores issued, 4 softmax done, 5 P.V issued); NULL switches it off (default).  The buffer covers 16 key tiles and the kernel does not
+ * clamp the tile index: it must not be armed for a call with Tk > 512.  tools/attn_x3_trace.py. */
 int hirest_attention_x3_debug_trace(int64_t* device_buffer);
 /* A/B and tests: bit 0 = the tower's attention is the exact-fp32 hirest_attention_f32_qkv instead of hirest_attention_x3_qkv; bit 1 = fc1 writes fp32
  * and GELU + split run as a separate pass (hirest_split2_bf16) instead of in its epilogue (HIREST_EPI_BIAS_GELU_SPLIT2).  Default 0. */

@@ -1,5 +1,5 @@
 """Inputs whose results are known without a tolerance, and the fp64 references that go with them, for tests/test_gpu_gemm_exact.py,
-tests/test_gpu_attention_edges.py and tests/test_gpu_gemm_f32_exact.py.  tests/test_exact_inputs_host.py checks every precondition stated here on the CPU, so a wrong
+tests/test_gpu_attention_edges.py, tests/test_gpu_attention_x3_exact.py and tests/test_gpu_gemm_f32_exact.py.  tests/test_exact_inputs_host.py checks every precondition stated here on the CPU, so a wrong
 generator cannot make a GPU test pass vacuously.  Not a test module.
 
 "Exact inputs" for the bf16 GEMM: operands are small integers (or integers times a power of two), so every product and every
@@ -315,6 +315,217 @@ def attention_launchers_all():
             out.add(("launch3", dh, 17, False, False, variant))
             out.add(("launch3", dh, 17, False, True, variant))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# split-operand attention (csrc/attention_x3.hip): tests/test_gpu_attention_x3_exact.py
+#   fp32 q [B, Tq, H, dh], k and v [B, Tk, H, dh]; head scale dh ** -0.5; both products from bf16 hi + lo parts of both operands
+# ------------------------------------------------------------------------------------------------------------------------------
+# (Tq, Tk) in query waves x key tiles: 1 x 1; 1 x 1 full; 2 x 1; 1 x 2; 2 x 3 (the first fetch at k0 + 64); 4 x 2; 5 x 4 (workgroups of
+# 3 + 2 waves, or of 4 + 1); 10 x 2 (more than one nine-wave workgroup); 2 x 10
+X3A_SHAPES = [(1, 1), (32, 32), (33, 31), (31, 33), (64, 65), (97, 64), (129, 97), (289, 33), (33, 289)]
+X3A_DH = [4, 32, 36, 64, 68, 88, 96]          # 4: the dh - 4 clamp is 0; 36, 68: one group of four columns into the next DHP
+X3A_B, X3A_H = [1, 3], [2, 3]
+X3A_GAP = 110.0                               # exp(-110) = 2^-158.7 is below the smallest fp32 denormal (2^-149)
+X3A_FRAC = 2.0 ** -10
+
+
+def x3a_cases(dhs=None, passes=2):
+    """A rotating subset of X3A_SHAPES x dhs x X3A_B x X3A_H: every shape `passes` times, with dh, B and H stepping at different rates so
+    that every value of every axis occurs (asserted in tests/test_exact_inputs_host.py).  [(B, Tq, Tk, H, dh)]."""
+    dhs = X3A_DH if dhs is None else dhs
+    out = []
+    for p in range(passes):
+        for i, (Tq, Tk) in enumerate(X3A_SHAPES):
+            n = p * len(X3A_SHAPES) + i
+            out.append((X3A_B[n % 2], Tq, Tk, X3A_H[(n // 2) % 2], dhs[(n + 2 * p) % len(dhs)]))
+    return out
+
+
+def x3a_id(case):
+    return "B{}-Tq{}-Tk{}-H{}-dh{}".format(*case)
+
+
+def hi_lo(x):
+    """The two bf16 parts the kernels form from an fp32 tensor, as fp32: hi = bf16(x), lo = bf16(x - hi)."""
+    hi = x.to(torch.bfloat16).float()
+    return hi, (x - hi).to(torch.bfloat16).float()
+
+
+def _heads(t):
+    return t.permute(0, 2, 1, 3)                  # [B, T, H, dh] <-> [B, H, T, dh]
+
+
+def attention_x3_ref(q, k, v):
+    """softmax(dh^-0.5 q k^T) v in fp64, [B, Tq, H, dh]."""
+    q, k, v = (_heads(t.double()) for t in (q, k, v))
+    s = q @ k.transpose(-1, -2) * q.shape[-1] ** -0.5
+    return _heads(torch.softmax(s, -1) @ v)
+
+
+def attention_x3_restated(q, k, v):
+    """The same in fp64 from the bf16 hi + lo parts of q, k, p = exp(s - row max) and v, each product hi lo + lo hi + hi hi, normalised at
+    the end (_whisper_enc_ref.attention_heads): what the operand format alone costs.  The yardstick of the random family."""
+    import _whisper_enc_ref as W
+    return _heads(W.attention_heads(*(_heads(t.double()) for t in (q, k, v)), True))
+
+
+def attention_x3_logits(q, k):
+    """Natural-unit logits in fp64, [B, H, Tq, Tk]."""
+    return _heads(q.double()) @ _heads(k.double()).transpose(-1, -2) * q.shape[-1] ** -0.5
+
+
+def attention_x3_emulated(q, k, v, drop=()):
+    """The kernel's arithmetic in fp32 torch: 32-key tiles, the three score products added small terms first (k_hi q_lo, k_lo q_hi, k_hi
+    q_hi), fp32 scale, running max with the exp(m_old - m_new) rescale, p split into hi + lo, v_hi p_lo + v_lo p_hi + v_hi p_hi, one
+    division at the end.  The order of the additions inside a product is torch's, not the MFMA's.  `drop` names terms to leave out
+    ("khql", "klqh", "vlph", ...): the host tests use it to show that a family notices a missing term."""
+    B, Tq, H, dh = q.shape
+    Tk = k.shape[1]
+    scale = torch.tensor(dh ** -0.5, dtype=torch.float32)
+    (qh, ql), (kh, kl), (vh, vl) = (tuple(_heads(p) for p in hi_lo(t.float())) for t in (q, k, v))
+    term = lambda name, a, b: 0.0 if name in drop else a @ b
+    o = torch.zeros((B, H, Tq, dh), dtype=torch.float32)
+    mrun = torch.full((B, H, Tq, 1), -3.0e38, dtype=torch.float32)
+    lrun = torch.zeros((B, H, Tq, 1), dtype=torch.float32)
+    for k0 in range(0, Tk, 32):
+        sl = slice(k0, min(k0 + 32, Tk))
+        kht, klt = kh[:, :, sl].transpose(-1, -2), kl[:, :, sl].transpose(-1, -2)
+        st = torch.zeros((B, H, Tq, sl.stop - k0), dtype=torch.float32)
+        st = st + term("khql", ql, kht)
+        st = st + term("klqh", qh, klt)
+        st = (st + term("khqh", qh, kht)) * scale
+        mnew = torch.maximum(mrun, st.amax(-1, keepdim=True))
+        alpha = torch.exp(mrun - mnew)
+        p = torch.exp(st - mnew)
+        lrun = lrun * alpha + p.sum(-1, keepdim=True)
+        mrun = mnew
+        ph, pl = hi_lo(p)
+        o = o * alpha
+        o = o + term("vhpl", pl, vh[:, :, sl])
+        o = o + term("vlph", ph, vl[:, :, sl])
+        o = o + term("vhph", ph, vh[:, :, sl])
+    return _heads(o * (1.0 / lrun))
+
+
+def x3_column_max(v):
+    """max over the keys of |v[b, j, h, d]|, [B, 1, H, dh] fp64: the scale of the per-element error of the random family."""
+    return v.double().abs().amax(dim=1, keepdim=True)
+
+
+def _balanced(rng, B, T, H, dh):
+    """[B, T, H, dh] of +-1 with dh / 2 of each per vector, the T vectors of one (frame, head) pairwise distinct."""
+    base = np.repeat(np.array([1.0, -1.0], dtype=np.float32), dh // 2)
+    s = rng.permuted(np.broadcast_to(base, (B, T, H, dh)), axis=-1)
+    for b in range(B):
+        for h in range(H):
+            while True:
+                _, first = np.unique(s[b, :, h], axis=0, return_index=True)
+                dup = np.setdiff1d(np.arange(T), first)
+                if dup.size == 0:
+                    break
+                s[b, dup, h] = rng.permuted(np.broadcast_to(base, (dup.size, dh)), axis=-1)
+    return torch.from_numpy(s)
+
+
+def _x3_pi(rng, B, Tq, Tk, H):
+    """pi [B, H, Tq] -> keys: every key when Tq >= Tk; always key Tk - 1 and one key of every 32-key tile; the rest random; shuffled."""
+    tiles = (Tk + 31) // 32
+    assert Tq >= min(Tk, tiles)
+    pi = np.empty((B, H, Tq), dtype=np.int64)
+    for b in range(B):
+        for h in range(H):
+            if Tq >= Tk:
+                must = rng.permutation(Tk)
+            else:
+                must = np.array([rng.integers(32 * t, min(32 * t + 32, Tk)) for t in range(tiles - 1)] + [Tk - 1], dtype=np.int64)
+            row = np.concatenate([must, rng.integers(0, Tk, size=Tq - must.size)])
+            pi[b, h] = rng.permutation(row)
+    return torch.from_numpy(pi)
+
+
+def _v16(rng, shape):
+    """fp32 values with random sign, exponent in {-1, 0, 1} and a random 16-bit significand (the low 8 fraction bits are 0): v == hi + lo
+    exactly, and lo != 0 for all but one value in 256, so an output is right only with both V parts."""
+    bits = (rng.integers(0, 2, size=shape) << 31) | (rng.integers(126, 129, size=shape) << 23) | (rng.integers(0, 1 << 15, size=shape) << 8)
+    return torch.from_numpy(bits.astype(np.uint32).view(np.float32))
+
+
+def _x3_selector(B, Tq, Tk, H, dh, seed, frac_in_k):
+    assert dh >= 32 and dh % 2 == 0
+    rng = _rng(31, B, Tq, Tk, H, dh, seed, int(frac_in_k))
+    s = _balanced(rng, B, Tk, H, dh)
+    pi = _x3_pi(rng, B, Tq, Tk, H)
+    idx = pi.permute(0, 2, 1)[..., None].expand(B, Tq, H, dh)                         # gather along the key axis
+    sel = torch.gather(s, 1, idx)
+    if frac_in_k:
+        q, k = sel, 1.0 + X3A_FRAC * s
+    else:
+        q, k = 1.0 + X3A_FRAC * sel, s
+    # gap at c = 1 in fp64; the logits are linear in c
+    c = 1.0 if Tk == 1 else 2.0 ** math.ceil(math.log2(X3A_GAP / x3_selector_gap({"q": q, "k": k, "pi": pi})))
+    v = _v16(rng, (B, Tk, H, dh))
+    return {"q": q * c, "k": k, "v": v, "pi": pi, "c": c, "s": s, "want": torch.gather(v, 1, idx)}
+
+
+def x3_selector_klo(B, Tq, Tk, H, dh, seed=0):
+    """k_j = u + 2^-10 s_j, q_i = c s_pi(i), with u all ones and s_j pairwise distinct balanced +-1 vectors (s . u = 0): bf16(k) = u and the
+    lo part of k is 2^-10 s_j, both exactly, and q has no lo part, so the logits differ only through q_hi k_lo: c 2^-10 dh^-0.5 (s_pi(i) .
+    s_j).  c is the smallest power of two that puts the selected logit at least X3A_GAP = 110 natural units above every other on every
+    row (fp64): every other p and every rescale factor is 0 in fp32, the selected p and the normaliser are 1.  Every partial sum of either
+    product is a multiple of c 2^-10 below 2^24 of it, hence exact in fp32 in any order; v has 16-bit significands (v == hi + lo).
+    Guarantee: out[b, i, h] == v[b, pi(i), h] ("want") bit for bit."""
+    return _x3_selector(B, Tq, Tk, H, dh, seed, True)
+
+
+def x3_selector_qlo(B, Tq, Tk, H, dh, seed=0):
+    """The mirror image: q_i = c (u + 2^-10 s_pi(i)), k_j = s_j.  bf16(q) = c u, the lo part of q is c 2^-10 s_pi(i), k has no lo part: the
+    selection rides on q_lo k_hi alone.  Same guarantee."""
+    return _x3_selector(B, Tq, Tk, H, dh, seed, False)
+
+
+def x3_selector_gap(d):
+    """Smallest (selected logit - largest other logit) over all rows, natural units, fp64."""
+    lg = attention_x3_logits(d["q"], d["k"])
+    top = torch.gather(lg, 3, d["pi"][..., None])
+    rest = lg.scatter(3, d["pi"][..., None], float("-inf")).amax(-1, keepdim=True)
+    return (top - rest).min().item() if lg.shape[-1] > 1 else float("inf")
+
+
+def x3_uniform(B, Tq, Tk, H, dh, seed=0):
+    """q = 0 (every p is exactly 1; k is random) and V[j, d] = 1 if j % dh == d else 0: out[i, d] = count_d / Tk with count_d the keys j <
+    Tk with j % dh == d.  One key too many or too few moves a column by at least 1 / count of its value.
+    bound = 2^-22 count_d / Tk: the sums are exact, the kernel rounds twice in fp32 (1 / Tk, then count_d times it), 2^-24 relative each,
+    and the bound leaves a factor 2 on top of their sum."""
+    rng = _rng(32, B, Tq, Tk, H, dh, seed)
+    k = torch.from_numpy(rng.standard_normal((B, Tk, H, dh)).astype(np.float32))
+    q = torch.zeros((B, Tq, H, dh))
+    ind = ((torch.arange(Tk)[:, None] % dh) == torch.arange(dh)[None, :])
+    ref = (ind.double().sum(0) / Tk)[None, None, None, :].expand(B, Tq, H, dh)
+    return {"q": q, "k": k, "v": ind.float()[None, :, None, :].expand(B, Tk, H, dh).contiguous(), "ref": ref, "bound": ref * 2.0 ** -22}
+
+
+def x3_isolation(B, Tq, Tk, H, dh, seed=0):
+    """attn_isolation in fp32: q = -c s_b u and k = s_b (u + small) with u a +-1 vector per head, c = 200 / sqrt(dh) and s_b = +1 / -1 in
+    even / odd frames.  Real logits are about -200; a key of the neighbouring frame meets q with the other sign (+200, 400 above), and
+    the 3e38 the tests put after the keys would overflow the score."""
+    rng = _rng(33, B, Tq, Tk, H, dh, seed)
+    u = torch.from_numpy(rng.integers(0, 2, size=(1, 1, H, dh)).astype(np.float32) * 2 - 1)
+    sgn = torch.tensor([1.0, -1.0]).repeat((B + 1) // 2)[:B].reshape(B, 1, 1, 1)
+    small = torch.from_numpy(rng.standard_normal((B, Tk, H, dh)).astype(np.float32)) * 2.0 ** -4
+    q = (-200.0 / math.sqrt(dh) * sgn * u).expand(B, Tq, H, dh).contiguous()
+    v = torch.from_numpy(rng.standard_normal((B, Tk, H, dh)).astype(np.float32))
+    return {"q": q, "k": sgn * (u + small), "v": v}
+
+
+def x3_random(B, Tq, Tk, H, dh, qscale):
+    """Standard normal q, k, v (fp32: every lo part is alive), q times qscale (1, 3, 6), V column 1 of every head times 64 and column 2
+    times 1 / 64, so that an error bar relative to the tensor's maximum would be blind to column 2."""
+    rng = _rng(34, B, Tq, Tk, H, dh, int(qscale))
+    q, k, v = (torch.from_numpy(rng.standard_normal((B, T, H, dh)).astype(np.float32)) for T in (Tq, Tk, Tk))
+    v[..., 1] *= 64.0
+    v[..., 2] /= 64.0
+    return {"q": q * qscale, "k": k, "v": v}
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

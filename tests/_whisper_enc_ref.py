@@ -45,17 +45,21 @@ def stem(cfg, sd, mel):
     return x.permute(0, 2, 1) + sd["embed_positions.weight"].double()
 
 
+def attention_heads(q, k, v, split):
+    """q [B, H, Tq, dh], k, v [B, H, Tk, dh] -> [B, H, Tq, dh]: softmax(q k^T dh^-0.5) v.  ``split``: the score product on the split of q
+    and k, scaled afterwards; the second product on the split of exp(score - row max) and v, divided by the fp64 row sum afterwards (the
+    flash kernel normalises at the end too).  Also the yardstick of tests/test_gpu_attention_x3_exact.py (_exact_inputs.attention_x3_restated)."""
+    s = product(q, k.transpose(-1, -2), split) * q.shape[-1] ** -0.5
+    p = torch.exp(s - s.amax(dim=-1, keepdim=True))
+    return product(p, v, split) / p.sum(dim=-1, keepdim=True)
+
+
 def attention(q, k, v, heads, split):
-    """q, k, v [B, T, D] -> [B, T, D]: softmax(q k^T dh^-0.5) v per head.  ``split``: the score product on the split of q and k, scaled
-    afterwards; the second product on the split of exp(score - row max) and v, divided by the fp64 row sum afterwards (the flash kernel
-    normalises at the end too)."""
+    """q, k, v [B, T, D] -> [B, T, D]: attention_heads per head."""
     B, T, D = q.shape
     dh = D // heads
     q, k, v = (t.reshape(B, T, heads, dh).permute(0, 2, 1, 3) for t in (q, k, v))
-    s = product(q, k.transpose(-1, -2), split) * dh ** -0.5
-    p = torch.exp(s - s.amax(dim=-1, keepdim=True))
-    o = product(p, v, split) / p.sum(dim=-1, keepdim=True)
-    return o.permute(0, 2, 1, 3).reshape(B, T, D)
+    return attention_heads(q, k, v, split).permute(0, 2, 1, 3).reshape(B, T, D)
 
 
 def encoder(cfg, sd, mel, split=False, split_attention=True):

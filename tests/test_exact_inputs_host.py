@@ -1,6 +1,8 @@
 """The preconditions of tests/_exact_inputs.py, checked on the CPU: the GPU tests that use these generators (test_gpu_gemm_exact.py,
-test_gpu_attention_edges.py, test_gpu_gemm_f32_exact.py) assert bit equality or derived bounds that only mean something while these hold."""
+test_gpu_attention_edges.py, test_gpu_attention_x3_exact.py, test_gpu_gemm_f32_exact.py) assert bit equality or derived bounds that only mean
+something while these hold."""
 import ctypes
+import math
 
 import pytest
 import torch
@@ -358,3 +360,133 @@ def test_f32_gemm_rejects_strides_its_epilogue_cannot_use(lib):
         assert lib.hirest_gemm_f32_ln(P, K, None, None, None, P, P, 1e-5, P, ldl, P, K, None, None, 0, P, N, 16, N, K, 0, None) == SHAPE, ldl
     for ldo in (8197, 8198, 8192):
         assert lib.hirest_gemm_f32_ln_colmax(P, 768, P, P, 1e-5, P, 768, None, P, ldo, P, 16, 8196, 768, None) == SHAPE, ldo
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# split-operand attention: tests/test_gpu_attention_x3_exact.py
+# ------------------------------------------------------------------------------------------------------------------------------
+X3A_SEL_DH = [dh for dh in X.X3A_DH if dh >= 32]
+# the generators are the same code for every shape: the host side takes two tiles with a ragged end, the first fetch at k0 + 64, Tq < Tk
+# with ten tiles and Tq > Tk, over the narrowest, the widest and the two padded head widths
+X3A_HOST = [(3, 31, 33, 2, 32), (1, 64, 65, 3, 36), (3, 129, 97, 2, 68), (1, 33, 289, 3, 88), (3, 289, 33, 2, 96), (1, 97, 64, 2, 64)]
+x3a_host = pytest.mark.parametrize("B,Tq,Tk,H,dh", X3A_HOST, ids=[X.x3a_id(c) for c in X3A_HOST])
+
+
+def test_x3a_cases_cover_every_axis_value():
+    for dhs in (X.X3A_DH, X3A_SEL_DH):
+        cases = X.x3a_cases(dhs)
+        assert {(Tq, Tk) for _, Tq, Tk, _, _ in cases} == set(X.X3A_SHAPES) and len(cases) == 2 * len(X.X3A_SHAPES)
+        assert {c[4] for c in cases} == set(dhs) and {c[0] for c in cases} == set(X.X3A_B) and {c[3] for c in cases} == set(X.X3A_H)
+        for axis, values in ((0, X.X3A_B), (3, X.X3A_H)):                  # both B and both H against more than one head width and shape
+            for val in values:
+                assert len({c[4] for c in cases if c[axis] == val}) >= 3 and len({c[1:3] for c in cases if c[axis] == val}) >= 4
+        for shape in X.X3A_SHAPES:                                         # every shape with both batch sizes and two head widths
+            mine = [c for c in cases if c[1:3] == shape]
+            assert {c[0] for c in mine} == set(X.X3A_B) and len({c[4] for c in mine}) == 2
+    assert any(Tq == Tk for Tq, Tk in X.X3A_SHAPES)                     # the packed layout has cases
+
+
+@pytest.mark.parametrize("frac_in_k", [True, False], ids=["klo", "qlo"])
+@x3a_host
+def test_x3_selector_preconditions(B, Tq, Tk, H, dh, frac_in_k):
+    d = (X.x3_selector_klo if frac_in_k else X.x3_selector_qlo)(B, Tq, Tk, H, dh)
+    q, k, v, pi, c, s = d["q"], d["k"], d["v"], d["pi"], d["c"], d["s"]
+    assert q.shape == (B, Tq, H, dh) and k.shape == v.shape == (B, Tk, H, dh) and q.dtype == k.dtype == v.dtype == torch.float32
+    gap = X.x3_selector_gap(d)
+    print(f"c = 2^{math.log2(c):.0f}, gap {gap:.1f}")
+    assert gap >= X.X3A_GAP and c == 2.0 ** round(math.log2(c)) and X.x3_selector_gap(dict(d, q=q / 2)) < X.X3A_GAP   # the smallest such c
+    # s: balanced +-1, pairwise distinct within a (frame, head)
+    assert set(s.unique().tolist()) == {-1.0, 1.0} and (s.sum(-1) == 0).all()
+    for b in range(B):
+        for h in range(H):
+            assert torch.unique(s[b, :, h], dim=0).shape[0] == Tk
+    # pi: every key when Tq >= Tk; key Tk - 1 and one key of every 32-key tile always
+    assert pi.shape == (B, H, Tq) and pi.min() >= 0 and pi.max() < Tk
+    for row in pi.reshape(B * H, Tq):
+        hit = set(row.tolist())
+        assert Tk - 1 in hit and {j // 32 for j in hit} == set(range((Tk + 31) // 32)) and (Tq < Tk or len(hit) == Tk)
+    # hi and lo parts exactly as stated
+    sel = torch.gather(s, 1, pi.permute(0, 2, 1)[..., None].expand(B, Tq, H, dh))
+    (qh, ql), (kh, kl) = X.hi_lo(q), X.hi_lo(k)
+    if frac_in_k:
+        assert torch.equal(kh, torch.ones_like(k)) and torch.equal(kl, X.X3A_FRAC * s) and torch.equal(qh, c * sel) and (ql == 0).all()
+    else:
+        assert torch.equal(qh, torch.full_like(q, c)) and torch.equal(ql, c * X.X3A_FRAC * sel) and torch.equal(kh, s) and (kl == 0).all()
+    assert torch.equal(qh + ql, q) and torch.equal(kh + kl, k)
+    # every partial sum is a multiple of c 2^-10 below 2^24 of it: the sum of the magnitudes of all three products' terms
+    unit = c * X.X3A_FRAC
+    assert torch.equal(q / unit, (q / unit).round()) and dh * (1 + 2 * X.X3A_FRAC) / X.X3A_FRAC < X.F32_EXACT
+    # V: 16-bit significands, exponent in {-1, 0, 1}, v == hi + lo with the lo part alive; no two rows agree
+    vh, vl = X.hi_lo(v)
+    assert torch.equal(vh + vl, v) and (v.view(torch.int32) & 0xFF == 0).all() and (vl != 0).float().mean().item() > 0.9
+    assert v.abs().min().item() >= 0.5 and v.abs().max().item() < 4.0
+    assert torch.unique(v.reshape(-1, dh), dim=0).shape[0] == B * Tk * H
+    # the fp64 reference puts everything on pi(i)
+    assert torch.equal(X.attention_x3_ref(q, k, v).float(), d["want"])
+
+
+@pytest.mark.parametrize("frac_in_k", [True, False], ids=["klo", "qlo"])
+@x3a_host
+def test_x3_selector_emulation_needs_its_cross_term(B, Tq, Tk, H, dh, frac_in_k):
+    """The fp32 emulation of the kernel returns the selected V rows bit for bit, and does not once the score term that carries the selection
+    (k_lo q_hi for klo, k_hi q_lo for qlo) or the v_lo p_hi term is left out; the other cross term is zero in that family."""
+    d = (X.x3_selector_klo if frac_in_k else X.x3_selector_qlo)(B, Tq, Tk, H, dh)
+    q, k, v, want = d["q"], d["k"], d["v"], d["want"]
+    assert torch.equal(X.attention_x3_emulated(q, k, v).view(torch.int32), want.view(torch.int32))
+    carrying, idle = ("klqh", "khql") if frac_in_k else ("khql", "klqh")
+    assert not torch.equal(X.attention_x3_emulated(q, k, v, drop=(carrying,)), want)
+    assert torch.equal(X.attention_x3_emulated(q, k, v, drop=(idle,)), want)
+    assert not torch.equal(X.attention_x3_emulated(q, k, v, drop=("vlph",)), want)
+    assert torch.equal(X.attention_x3_emulated(q, k, v, drop=("vhpl",)), want)               # (p is 0 or 1: no lo part)
+
+
+@pytest.mark.parametrize("B,Tq,Tk,H,dh", X3A_HOST + [(1, 1, 1, 2, 4), (3, 33, 31, 3, 4)])
+def test_x3_uniform_bound_under_the_emulation(B, Tq, Tk, H, dh):
+    d = X.x3_uniform(B, Tq, Tk, H, dh)
+    assert d["q"].abs().max().item() == 0 and set(d["v"].unique().tolist()) <= {0.0, 1.0}
+    ref = d["ref"]
+    assert (X.attention_x3_ref(d["q"], d["k"], d["v"]) - ref).abs().max().item() < 1e-15
+    count = ref[0, 0, 0] * Tk
+    assert torch.equal(count.round(), torch.tensor([len(range(c, Tk, dh)) for c in range(dh)], dtype=torch.float64)) and count.sum().round() == Tk
+    err = (X.attention_x3_emulated(d["q"], d["k"], d["v"]).double() - ref).abs()
+    assert (err <= d["bound"]).all()
+    # one key too many (the clamped copy of key Tk - 1 left unmasked) or too few (key Tk - 1 masked away)
+    have = ref[0, 0, 0, (Tk - 1) % dh]
+    for wrong in ((have * Tk + 1) / (Tk + 1), (have * Tk - 1) / max(Tk - 1, 1)):
+        assert abs(wrong - have) > 1000 * have * 2.0 ** -22 or Tk == 1
+
+
+def test_x3_isolation_logits():
+    B, Tq, Tk, H, dh = 3, 33, 65, 2, 36
+    d = X.x3_isolation(B, Tq, Tk, H, dh)
+    s = X.attention_x3_logits(d["q"], d["k"])
+    assert s.max().item() < -150 and s.min().item() > -250
+    for qa, kb in ((d["q"][:-1], d["k"][1:]), (d["q"][1:], d["k"][:-1])):          # a key of the neighbouring frame: about +200
+        assert X.attention_x3_logits(qa, kb).min().item() > 150
+
+
+@pytest.mark.parametrize("qscale", [1, 3, 6])
+def test_x3_random_family_and_the_restatement(qscale):
+    """The restatement is the reference when every lo part is zero: bit for bit with one key (p = 1), and with many keys up to the lo x lo
+    term of p's split alone (bf16-valued q, k, v do not make p bf16-valued), far below the family's own Y.  The fp32 emulation stays within
+    the factor 2 of Y that the GPU test allows the kernel."""
+    B, Tq, Tk, H, dh = 3, 33, 97, 2, 36
+    d = X.x3_random(B, Tq, Tk, H, dh, qscale)
+    q, k, v = d["q"], d["k"], d["v"]
+    cm = X.x3_column_max(v)
+    assert cm[:, :, :, 1].min().item() > 64 and cm[:, :, :, 2].max().item() < 0.1 and (X.hi_lo(k)[1] != 0).float().mean().item() > 0.9
+    import _whisper_enc_ref as W
+    heads = lambda t: t.double().permute(0, 2, 1, 3)
+    unsplit = W.attention_heads(heads(q), heads(k), heads(v), False).permute(0, 2, 1, 3)            # (exp / sum against torch.softmax)
+    assert ((unsplit - X.attention_x3_ref(q, k, v)).abs() / cm).max().item() < 1e-14
+    # lo parts zero: one-key softmax (p = 1, no lo part either) makes the restatement the reference bit for bit
+    q1, k1, v1 = (t.to(torch.bfloat16).float() for t in (q, k[:, :1], v[:, :1]))
+    assert torch.equal(X.attention_x3_restated(q1, k1, v1), X.attention_x3_ref(q1, k1, v1))
+    # and with many keys only p's lo x lo term (2^-18 relative) separates them
+    qb, kb, vb = (t.to(torch.bfloat16).float() for t in (q, k, v))
+    e0 = ((X.attention_x3_restated(qb, kb, vb) - X.attention_x3_ref(qb, kb, vb)).abs() / cm).max().item()
+    Y = ((X.attention_x3_restated(q, k, v) - X.attention_x3_ref(q, k, v)).abs() / cm).max().item()
+    E = ((X.attention_x3_emulated(q, k, v).double() - X.attention_x3_ref(q, k, v)).abs() / cm).max().item()
+    R = ((X.attention_x3_emulated(q, k, v).double() - X.attention_x3_restated(q, k, v)).abs() / cm).max().item()
+    print(f"qscale {qscale}: lo-free restatement {e0:.2e}, Y {Y:.2e}, emulation / Y {E / Y:.2f}, emulation - restatement {R:.2e}")
+    assert e0 < 2.0 ** -17 and e0 < Y / 2 and E <= 2 * Y
