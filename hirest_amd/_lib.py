@@ -500,6 +500,9 @@ _SIGNATURES = {
                                                            C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "hirest_whisper_step_tail_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(WhisperTailParams),
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hirest_whisper_step_tail_rows_counted": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                                        C.POINTER(WhisperTailParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p]),
     "hirest_whisper_step_rows_workspace_bytes": (C.c_size_t, [C.POINTER(WhisperDecoder), C.c_int32, C.c_int32]),
     "hirest_whisper_decode_step_rows": (C.c_int, [C.POINTER(WhisperDecoder), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                                   C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p,

@@ -333,6 +333,20 @@ __global__ __launch_bounds__(64) void whisper_stamp_rows_kernel(const hirest_whi
     if (threadIdx.x == 0) *done_host = ((call + 1) << 1) | (none ? 1 : 0);
 }
 
+// the counted form: the call's number is a device word, read and advanced by this one lane — nothing of the launch
+// changes from call to call, so a captured sequence of tails stamps 2, 4, 6, ... as it is replayed
+__global__ __launch_bounds__(64) void whisper_stamp_rows_counted_kernel(const hirest_whisper_row_ctl* __restrict__ ctl, int R,
+                                                                       int32_t* __restrict__ count, int32_t* __restrict__ done_host) {
+    int none = 1;
+    for (int r = threadIdx.x; r < R; r += 64) none &= ctl[r].position < 0;
+    none = __all(none);
+    if (threadIdx.x == 0) {
+        const int call = *count;
+        if (done_host) *done_host = ((call + 1) << 1) | (none ? 1 : 0);
+        *count = call + 1;
+    }
+}
+
 // Language detection: the softmax of a row of logits over the L <= 128 language columns alone, and its argmax.  One
 // wave per row; lane l holds table entries l and l + 64.  The maximum is the tail's pick (strict > over ascending ids, then the xor
 // tree with the lower id on ties), the sum a lane's two terms in ascending order and then wave_sum's xor tree in double: fixed orders, so a row
@@ -488,10 +502,10 @@ extern "C" int hirest_whisper_step_tail(const float* logits, int64_t ldx, int32_
     return hirest_launch_status();
 }
 
-extern "C" int hirest_whisper_step_tail_rows(const float* logits, int64_t ldx, int32_t R, int32_t V, int32_t call, int64_t ld_tokens,
-                                             const hirest_whisper_tail_params* params, hirest_whisper_row_ctl* ctl,
-                                             hirest_whisper_row_state* state, int32_t* next_ids, int32_t* tokens, float* logprobs,
-                                             int32_t* done_host, void* stream) {
+// call >= 0: the stamp carries `call`; count != null: it carries *count, which the stamp's launch advances.  One tail launch either way.
+static int step_tail_rows(const float* logits, int64_t ldx, int32_t R, int32_t V, int32_t call, int32_t* count, int64_t ld_tokens,
+                          const hirest_whisper_tail_params* params, hirest_whisper_row_ctl* ctl, hirest_whisper_row_state* state,
+                          int32_t* next_ids, int32_t* tokens, float* logprobs, int32_t* done_host, void* stream) {
     if (!logits || !params || !ctl || !state || !next_ids || !tokens || !params->suppress_mask || R <= 0 || V <= 0 || call < 0 || ld_tokens <= 0)
         return HIREST_E_BADARG;
     const hirest_whisper_tail_params& c = *params;                // temperature, seed, serial and sample_begin: the rows' records replace them
@@ -502,8 +516,24 @@ extern "C" int hirest_whisper_step_tail_rows(const float* logits, int64_t ldx, i
         return HIREST_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(whisper_tail_rows_kernel, dim3(R), dim3(1024), 0, s, logits, ldx, (int)V, ld_tokens, c, ctl, state, next_ids, tokens, logprobs);
-    if (done_host) hipLaunchKernelGGL(whisper_stamp_rows_kernel, dim3(1), dim3(64), 0, s, ctl, (int)R, (int)call, done_host);
+    if (count) hipLaunchKernelGGL(whisper_stamp_rows_counted_kernel, dim3(1), dim3(64), 0, s, ctl, (int)R, count, done_host);
+    else if (done_host) hipLaunchKernelGGL(whisper_stamp_rows_kernel, dim3(1), dim3(64), 0, s, ctl, (int)R, (int)call, done_host);
     return hirest_launch_status();
+}
+
+extern "C" int hirest_whisper_step_tail_rows(const float* logits, int64_t ldx, int32_t R, int32_t V, int32_t call, int64_t ld_tokens,
+                                             const hirest_whisper_tail_params* params, hirest_whisper_row_ctl* ctl,
+                                             hirest_whisper_row_state* state, int32_t* next_ids, int32_t* tokens, float* logprobs,
+                                             int32_t* done_host, void* stream) {
+    return step_tail_rows(logits, ldx, R, V, call, nullptr, ld_tokens, params, ctl, state, next_ids, tokens, logprobs, done_host, stream);
+}
+
+extern "C" int hirest_whisper_step_tail_rows_counted(const float* logits, int64_t ldx, int32_t R, int32_t V, int32_t* count, int64_t ld_tokens,
+                                                     const hirest_whisper_tail_params* params, hirest_whisper_row_ctl* ctl,
+                                                     hirest_whisper_row_state* state, int32_t* next_ids, int32_t* tokens, float* logprobs,
+                                                     int32_t* done_host, void* stream) {
+    if (!count) return HIREST_E_BADARG;
+    return step_tail_rows(logits, ldx, R, V, 0, count, ld_tokens, params, ctl, state, next_ids, tokens, logprobs, done_host, stream);
 }
 
 extern "C" int hirest_whisper_language_tail(const float* logits, int64_t ldx, int32_t R, int32_t V, const int32_t* language_ids, int32_t L,

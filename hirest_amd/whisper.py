@@ -32,6 +32,7 @@ Whisper's ``decoder(tokens, xa, kv_cache)`` surface; the lock-step loop over the
 """
 from __future__ import annotations
 
+import collections
 import copy
 import ctypes as C
 import dataclasses
@@ -654,6 +655,7 @@ class TextDecoder(_FrozenWeights):
         if self.ffn % 16:
             raise NotImplementedError(f"ffn {self.ffn}: a multiple of 16 expected")
         self.vocab_padded = (self.vocab + 3) // 4 * 4
+        self.graph_stats = {"captures": 0, "replays": 0, "eager_steps": 0}          # Whisper.graph_stats()
         D, I = self.width, self.ffn
         want = {"token_embedding.weight": (self.vocab, D), "positional_embedding": (self.ctx, D), "ln.weight": (D,), "ln.bias": (D,)}
         for i in range(self.layers):
@@ -1301,7 +1303,8 @@ def detect_language(model: "Whisper", mel: torch.Tensor, tokenizer: Optional[Tok
 
 
 @torch.no_grad()
-def decode(model: "Whisper", mel: torch.Tensor, options: DecodingOptions = DecodingOptions(), *, return_candidates: bool = False):
+def decode(model: "Whisper", mel: torch.Tensor, options: DecodingOptions = DecodingOptions(), *, return_candidates: bool = False,
+           graph: Optional[bool] = None):
     """``whisper.decode``: one 30-second window ``[n_mels, 3000]`` (or encoder states ``[Tk, D]``) or a batch of them -> a
     ``DecodingResult`` (a list for a batch).  Greedy at temperature 0; at temperature > 0 ``best_of`` candidates per window are sampled
     and the one with the highest ``sum_logprobs / length`` is returned.  A window is one run of the decoding loop (``_decode_rows``) over
@@ -1311,11 +1314,13 @@ def decode(model: "Whisper", mel: torch.Tensor, options: DecodingOptions = Decod
     yields to the task the tokenizer was made with, so a ``with_language(.., "translate")`` tokenizer translates whatever
     ``options.task`` says — see ``_initial_tokens``); an English-only one ignores both.  Where neither names a language, the windows' languages are detected first, in one ``detect_language``
     pass, and ``result.language`` / ``result.language_probs`` say what was found.  ``task="lang_id"`` is not built: call
-    ``detect_language``.  ``return_candidates``: also every candidate's (tokens, sum_logprobs) per window (tests)."""
+    ``detect_language``.  ``return_candidates``: also every candidate's (tokens, sum_logprobs) per window (tests).  ``graph``: replay the
+    loop's iterations from a captured hipGraph (``None``: the environment's ``HIREST_WHISPER_GRAPH``, else off) — the same
+    values bit for bit, fewer launches on the host."""
     single = mel.ndim == 2
     if single:
         mel = mel[None]
-    results, everything = _decode_windows(model, mel, [options] * int(mel.shape[0]), 0)          # 0 rows fit beside a window: one per loop
+    results, everything = _decode_windows(model, mel, [options] * int(mel.shape[0]), 0, **_graph_kw(graph))      # 0 rows fit beside a window: one per loop
     if return_candidates:
         return (results[0], everything[0]) if single else (results, everything)
     return results[0] if single else results
@@ -1323,13 +1328,13 @@ def decode(model: "Whisper", mel: torch.Tensor, options: DecodingOptions = Decod
 
 @torch.no_grad()
 def decode_many(model: "Whisper", mels, options: Union[DecodingOptions, Sequence[DecodingOptions]] = DecodingOptions(), *,
-                return_candidates: bool = False):
+                return_candidates: bool = False, graph: Optional[bool] = None):
     """``decode`` for W windows that need not share their options — the current windows of W files — in ONE run of the decoding loop:
     ``mels`` W spectrograms ``[n_mels, 3000]`` or encoder states ``[Tk, D]`` (a tensor or a sequence of them), ``options`` one
     ``DecodingOptions`` or W of them.  ``prompt``, ``temperature``, ``best_of``, ``seed`` and ``language`` may differ between windows; any other field
     that does raises ValueError.  Returns a list of W ``DecodingResult`` with the values ``decode`` gives window by window, bit for bit
     (the same loop, whose rows do not depend on their neighbours); ``return_candidates`` as ``decode``'s.  More than 256 candidate rows
-    are split into consecutive loops."""
+    are split into consecutive loops.  ``graph`` as ``decode``'s."""
     mel = mels if torch.is_tensor(mels) else torch.stack([m.to(model.device) for m in mels])
     if mel.ndim != 3:
         raise ValueError(f"decode_many takes W windows [W, n_mels, frames] or [W, Tk, D], not a tensor of shape {tuple(mel.shape)}")
@@ -1340,15 +1345,17 @@ def decode_many(model: "Whisper", mels, options: Union[DecodingOptions, Sequence
     for f in dataclasses.fields(DecodingOptions):
         if f.name not in _PER_WINDOW_OPTIONS and any(getattr(o, f.name) != getattr(opts[0], f.name) for o in opts):
             raise ValueError(f"decode_many: {f.name} differs between the windows of one call (only {', '.join(_PER_WINDOW_OPTIONS)} may)")
-    results, everything = _decode_windows(model, mel, opts, _ROWS_PER_CALL)
+    results, everything = _decode_windows(model, mel, opts, _ROWS_PER_CALL, **_graph_kw(graph))
     return (results, everything) if return_candidates else results
 
 
-def _decode_windows(model, mel, opts, rows_per_loop):
+def _decode_windows(model, mel, opts, rows_per_loop, graph=False):
     """What ``decode`` and ``decode_many`` share: the plan of every window (initial tokens, sot index, step budget cut by the context,
     candidate rows), one encoder call for all of them, and consecutive windows — as many as fit ``rows_per_loop`` candidate rows, at
     least one — through ``_decode_rows``.  -> (results, candidates), one entry per window."""
     tokenizer, dec, dev = model.tokenizer, model.decoder, model.device
+    if graph:
+        dec._require_gpu()                                            # (before anything of the option is looked at: no CPU form of it either)
     if tokenizer is None:
         raise ValueError("the model has no tokenizer: load_model(path, tokenizer=...) or set model.tokenizer")
     codes = tokenizer.all_language_codes if tokenizer.multilingual else ()
@@ -1377,18 +1384,158 @@ def _decode_windows(model, mel, opts, rows_per_loop):
             while w1 < len(plans) and rows + plans[w1][3] <= rows_per_loop:
                 rows += plans[w1][3]
                 w1 += 1
-            res, cands = _decode_rows(model, xa[w0:w1], opts[w0:w1], plans[w0:w1], langs[w0:w1])
+            res, cands = _decode_rows(model, xa[w0:w1], opts[w0:w1], plans[w0:w1], langs[w0:w1], **_graph_kw(graph))
             results += res
             everything += cands
             w0 = w1
     return results, everything
 
 
-def _decode_rows(model, xa, opts, plans, langs):
+# The loop replayed from a hipGraph.  Every per-step quantity is on the device (the rows' records, and the call's number
+# in the counted tail), so ONE captured run of DECODE_GRAPH_CHUNK x {tail, step} serves every token of every window whose loop has the
+# arena's shape: the buffers of a loop live in an arena with stable addresses, keyed by (device, stream, R, n_windows, Tk).
+DECODE_GRAPH_CHUNK = 8         # iterations per captured graph (as CAPTION_GRAPH_CHUNK; profiles/whisper_graph.txt has 4 and 16 beside it)
+DECODE_ARENAS = 4              # arenas kept per decoder, least recently used first out
+
+
+def resolve_graph(graph: Optional[bool]) -> bool:
+    """The ``graph=`` keyword of ``decode`` / ``decode_many`` / ``transcribe`` / ``transcribe_many``: the keyword where it is given, else
+    the environment's ``HIREST_WHISPER_GRAPH`` (set and not ``0``), else off."""
+    if graph is not None:
+        return bool(graph)
+    return os.environ.get("HIREST_WHISPER_GRAPH", "").strip() not in ("", "0")
+
+
+def _graph_kw(graph: Optional[bool]) -> Dict[str, bool]:
+    """what a caller hands on: ``graph=True`` where the option resolves to on, nothing where it is off — the calls of before"""
+    return {"graph": True} if resolve_graph(graph) else {}
+
+
+def graph_throttle(issued: int, stamp: int, chunk: int, max_steps: int) -> str:
+    """What the replaying loop does next, a pure function of the chunks it has issued and the pinned stamp it has just read: ``"stop"``,
+    ``"wait"`` (poll the stamp again) or ``"issue"`` (replay one more chunk).  The stamp is ``(tails landed << 1) | no row is active``;
+    iteration 0 ran eagerly, so after ``issued`` chunks ``1 + issued * chunk`` tails are enqueued.  Stop when no row is active, when
+    ``max_steps`` tails have landed, or when every tail a row can need is enqueued (the caller then synchronises).  Otherwise at most
+    two chunks are in flight: the next is issued only once the chunk before the last has landed."""
+    if issued < 0 or chunk < 1 or max_steps < 1 or stamp < 0:
+        raise ValueError(f"graph_throttle({issued}, {stamp}, {chunk}, {max_steps})")
+    landed = stamp >> 1
+    if (stamp & 1) or landed >= max_steps or 1 + issued * chunk >= max_steps:
+        return "stop"
+    if issued >= 2 and landed < 1 + (issued - 1) * chunk:
+        return "wait"
+    return "issue"
+
+
+class _DecodeArena:
+    """Everything a decoding loop of one shape reads and writes between its prefill and its read-back, at addresses that do not change
+    from loop to loop: what ``KVCache`` holds (same attribute names: ``prefill_many`` and the step take either), with the self caches
+    ``[R, n_text_ctx, D]`` whatever the prompts' lengths, and the rows' records, states, ids, tokens ``[R, n_text_ctx // 2]``, the
+    suppress mask, the tail's call counter and the pinned stamp.  ``graph`` is the captured chunk, ``graph_key`` what it was captured
+    with (the tail's constants and the chunk length): another key captures again."""
+
+    def __init__(self, decoder: "TextDecoder", R: int, n_windows: int, Tk: int):
+        dev, D, L = decoder.device, decoder.width, decoder.layers
+        self.R, self.T_max, self.length, self.n_windows, self.Tk = R, decoder.ctx, 0, n_windows, Tk
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        self.row_window = i32(R)
+        self.self_k, self.self_v = [f32(R, self.T_max, D) for _ in range(L)], [f32(R, self.T_max, D) for _ in range(L)]
+        self.cross_kv = [f32(n_windows, Tk, 2 * D) for _ in range(L)]
+        P = C.c_void_p * L
+        self.k_ptrs, self.v_ptrs = P(*(t.data_ptr() for t in self.self_k)), P(*(t.data_ptr() for t in self.self_v))
+        self.x_ptrs = P(*(t.data_ptr() for t in self.cross_kv))
+        self.logits = f32(R, decoder.vocab_padded)
+        need = _lib.load().hirest_whisper_step_rows_workspace_bytes(C.byref(decoder._w()["desc"]), R, Tk)
+        self.ws = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=dev)
+        self.ctl, self.state = i32(R, _lib.WHISPER_ROW_CTL_WORDS), i32(R, _lib.WHISPER_ROW_STATE_WORDS)
+        self.ids, self.tokens = i32(R), i32(R, max(decoder.ctx // 2, 1))
+        self.mask, self.count = i32((decoder.vocab_padded + 31) // 32), i32(1)
+        self.stamp = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self.stamp_host = self.stamp.numpy()                          # the same word, read without a tensor per poll
+        self.graph, self.graph_key = None, None
+
+    def load(self, decoder: "TextDecoder", xa: torch.Tensor, row_window: torch.Tensor) -> None:
+        """a loop's windows: ``row_window`` and every layer's cross key | value rows, computed into the arena's own buffers"""
+        c, dev, D = decoder._w(), decoder.device, decoder.width
+        self.row_window.copy_(row_window)
+        rows = xa.to(dev, torch.float32).contiguous().view(self.n_windows * self.Tk, D)
+        for i, out in enumerate(self.cross_kv):
+            _gemm(rows.data_ptr(), D, c[f"ckv_w.{i}"], c[f"ckv_b.{i}"], out.data_ptr(), 2 * D, rows.shape[0], dev)
+
+
+def _decode_arena(decoder: "TextDecoder", R: int, n_windows: int, Tk: int) -> _DecodeArena:
+    """The arena of (device, current stream, R, n_windows, Tk), made on first use.  The arenas live in the decoder's weight
+    preparation — their graphs hold its addresses — so any move or cast drops them all; of more than ``DECODE_ARENAS`` the least
+    recently used goes."""
+    arenas = decoder._w().setdefault("decode_arenas", collections.OrderedDict())
+    dev = decoder.device
+    with torch.cuda.device(dev):
+        key = (dev.index, ops.stream_ptr(), R, n_windows, Tk)
+        if key not in arenas:
+            while len(arenas) >= DECODE_ARENAS:
+                arenas.popitem(last=False)
+            arenas[key] = _DecodeArena(decoder, R, n_windows, Tk)
+    arenas.move_to_end(key)
+    return arenas[key]
+
+
+def _replay_loop(dec, arena: _DecodeArena, params, max_steps: int) -> None:
+    """The loop's iterations on an arena whose ``logits`` hold the prefill's: iteration 0 eagerly (also the warm-up of a capture), then
+    the captured chunk of ``DECODE_GRAPH_CHUNK`` x {counted tail, step} replayed as ``graph_throttle`` says.  The only thing the host
+    reads is the pinned stamp; nothing here synchronises with the device but a capture."""
+    lib, a, Vp, R = _lib.load(), arena, dec.vocab_padded, arena.R
+    desc, ld_tokens = C.byref(dec._w()["desc"]), int(a.tokens.shape[1])
+    stats = dec.graph_stats
+
+    def iteration(stream):
+        _lib.check(lib.hirest_whisper_step_tail_rows_counted(a.logits.data_ptr(), Vp, R, Vp, a.count.data_ptr(), ld_tokens, C.byref(params),
+                                                             a.ctl.data_ptr(), a.state.data_ptr(), a.ids.data_ptr(), a.tokens.data_ptr(), None,
+                                                             a.stamp.data_ptr(), stream), "hirest_whisper_step_tail_rows_counted")
+        _lib.check(lib.hirest_whisper_decode_step_rows(desc, R, a.ctl.data_ptr(), a.ids.data_ptr(), a.k_ptrs, a.v_ptrs, a.T_max, a.x_ptrs,
+                                                       a.n_windows, a.Tk, a.row_window.data_ptr(), a.logits.data_ptr(), a.ws.data_ptr(),
+                                                       a.ws.numel(), stream), "hirest_whisper_decode_step_rows")
+    # what a capture bakes in beside the arena's addresses: the tail's constants (not the four fields the rows' records replace)
+    baked = type(params).from_buffer_copy(params)
+    baked.temperature, baked.seed, baked.serial, baked.sample_begin = 0.0, 0, 0, 0
+    key = (bytes(baked), ld_tokens, max(1, int(DECODE_GRAPH_CHUNK)))
+    a.stamp_host[0] = 0                                               # (the loop before this one ended with a synchronisation)
+    a.count.zero_()
+    iteration(ops.stream_ptr())
+    stats["eager_steps"] += 1
+    chunk = key[2]
+    issued, stream, polls = 0, torch.cuda.current_stream(), 0
+    while True:
+        seen = int(a.stamp_host[0])
+        act = graph_throttle(issued, seen, chunk, max_steps)
+        if act == "stop":
+            return
+        if act == "wait":
+            polls += 1
+            if polls % 4096 == 0 and stream.query() and int(a.stamp_host[0]) == seen:      # an idle stream and no new stamp: no tail will land
+                raise RuntimeError(f"{_NAME}: the replayed decoding loop stopped at stamp {seen} with {issued} chunks issued")
+            continue
+        if a.graph is None or a.graph_key != key:
+            a.graph = a.graph_key = None
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                st = ops.stream_ptr()
+                for _ in range(chunk):
+                    iteration(st)
+            a.graph, a.graph_key = g, key
+            stats["captures"] += 1
+        a.graph.replay()
+        stats["replays"] += 1
+        issued, polls = issued + 1, 0
+
+
+def _decode_rows(model, xa, opts, plans, langs, graph: bool = False):
     """THE decoding loop, over the candidate rows of ``xa``'s windows: one cross key / value projection for all windows, one cache of
     all rows, one ragged prefill of all windows' prompts (``prefill_many``), then per token ``hirest_whisper_step_tail_rows`` + ``hirest_whisper_decode_step_rows`` over
     all rows — each at its own position, with its own temperature, seed and remaining room, kept in a device record per row — until
-    no row is active.  Nothing is read back in the loop but the pinned stamp; tokens and sums are read once at the end."""
+    no row is active.  Nothing is read back in the loop but the pinned stamp; tokens and sums are read once at the end.
+    ``graph``: the same calls on the buffers of a ``_DecodeArena`` (a cache of the decoder's whole context per row), the iterations after
+    the first replayed from the arena's captured chunk (``_replay_loop``) — the same bits."""
     tokenizer, dec, dev, lib = model.tokenizer, model.decoder, model.device, _lib.load()
     Vp = dec.vocab_padded
     first_row = np.cumsum([0] + [p[3] for p in plans]).tolist()
@@ -1396,9 +1543,17 @@ def _decode_rows(model, xa, opts, plans, langs):
     T_max = max(len(initial) + steps for initial, _, steps, _ in plans)
     max_steps = max(steps for _, _, steps, _ in plans)
     row_window = torch.tensor([w for w, p in enumerate(plans) for _ in range(p[3])], dtype=torch.int32)
-    kc = KVCache(dec, xa, row_window, T_max, per_row=True)
     # the constants every window shares; temperature, seed, serial and sample_begin are the rows' own (hirest_whisper_row_ctl)
     params, mask = tail_params(tokenizer, opts[0], dec.vocab, Vp, model.dims["n_audio_ctx"], 0, dev)
+    if graph:
+        if max_steps > dec.ctx // 2:
+            raise ValueError(f"graph=True: {max_steps} steps to sample, the arena's tokens hold n_text_ctx // 2 = {dec.ctx // 2}")
+        kc = _decode_arena(dec, R, int(xa.shape[0]), int(xa.shape[1]))
+        kc.load(dec, xa, row_window)
+        kc.mask.copy_(mask)
+        params.suppress_mask = kc.mask.data_ptr()
+    else:
+        kc = KVCache(dec, xa, row_window, T_max, per_row=True)
     # every window's prompt in one ragged pass: the caches, the logits of the last position and, where it is another one, of sot's
     groups = [p[3] for p in plans]
     want_sot = tokenizer.no_speech is not None
@@ -1416,13 +1571,23 @@ def _decode_rows(model, xa, opts, plans, langs):
                                                     None, None, ops.stream_ptr()), "hirest_whisper_step_tail")
         no_speech.append(scratch)
         ctl_rows += [(T - 1, 0, steps, g, opts[w].seed, opts[w].temperature) for g in range(group)]
-    ctl = new_row_ctl(ctl_rows, dev)
-    state = new_row_state(R, dev)
-    tokens = torch.full((R, max_steps), tokenizer.eot, dtype=torch.int32, device=dev)
-    ids = torch.zeros((R,), dtype=torch.int32, device=dev)
-    stamp = torch.zeros(1, dtype=torch.int32).pin_memory()
+    if graph:
+        kc.ctl.copy_(new_row_ctl(ctl_rows, "cpu"))
+        kc.state.copy_(new_row_state(R, "cpu"))
+        kc.tokens.fill_(tokenizer.eot)
+        kc.ids.zero_()
+        kc.logits.copy_(first)                                        # every iteration reads its logits at the same address
+        state, tokens = kc.state, kc.tokens
+        _replay_loop(dec, kc, params, max_steps)
+    else:
+        ctl = new_row_ctl(ctl_rows, dev)
+        state = new_row_state(R, dev)
+        tokens = torch.full((R, max_steps), tokenizer.eot, dtype=torch.int32, device=dev)
+        ids = torch.zeros((R,), dtype=torch.int32, device=dev)
+        stamp = torch.zeros(1, dtype=torch.int32).pin_memory()
     desc, logits = C.byref(dec._w()["desc"]), first
-    for call in range(max_steps):
+    for call in range(0 if graph else max_steps):                   # (a replayed loop has made its calls)
+        dec.graph_stats["eager_steps"] += 1
         _lib.check(lib.hirest_whisper_step_tail_rows(logits.data_ptr(), Vp, R, Vp, call, max_steps, C.byref(params), ctl.data_ptr(), state.data_ptr(),
                                                      ids.data_ptr(), tokens.data_ptr(), None, stamp.data_ptr(), ops.stream_ptr()),
                    "hirest_whisper_step_tail_rows")
@@ -1517,8 +1682,13 @@ class Whisper(nn.Module):
     def forward(self, mel: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
         return self.decoder(tokens, self.encoder(mel))
 
-    def decode(self, mel, options: DecodingOptions = DecodingOptions()):
-        return decode(self, mel, options)
+    def decode(self, mel, options: DecodingOptions = DecodingOptions(), *, graph: Optional[bool] = None):
+        return decode(self, mel, options, **_graph_kw(graph))
+
+    def graph_stats(self) -> Dict[str, int]:
+        """Counts since the model was made: ``captures`` (hipGraphs captured by the replayed decoding loop), ``replays`` (chunks
+        replayed) and ``eager_steps`` (loop iterations issued launch by launch, those of loops without ``graph`` included)"""
+        return dict(self.decoder.graph_stats)
 
     def detect_language(self, mel, tokenizer: Optional[Tokenizer] = None):
         return detect_language(self, mel, tokenizer)
@@ -1693,7 +1863,7 @@ def _detect_file_languages(model, walks) -> None:
         w.language = tokenizer.all_language_codes[tokenizer.all_language_tokens.index(token)]
 
 
-def transcribe(model, audio, **kw):
+def transcribe(model, audio, *, graph: Optional[bool] = None, **kw):
     """``whisper.transcribe``: a ``.wav`` path, a waveform or a ready spectrogram ``[n_mels, frames]`` (with its 30 s of padding) ->
     ``{"text", "segments", "language"}``.  One spectrogram per file; 3000-frame windows from ``seek``; per window the temperature
     fallback (the next temperature when the compression ratio or the average log-probability crosses its threshold), the no-speech
@@ -1707,16 +1877,18 @@ def transcribe(model, audio, **kw):
     option — Whisper moves ``seek`` to the last word's end, which is deliberately not done here.
     With a multilingual model ``language`` is a code, name or alias, or None: the language detected on the file's first 30 seconds
     (``detect_language``, once per file) — every window decodes in it and the result's ``"language"`` is its code; ``task`` is
-    "transcribe" or "translate".  An English-only model ignores both: ``"language"`` is "en"."""
+    "transcribe" or "translate".  An English-only model ignores both: ``"language"`` is "en".  ``graph`` as ``decode``'s: every window's
+    loop is replayed from a captured hipGraph."""
+    graph = _graph_kw(graph)
     walk = _FileWalk(model, audio, **kw)
     while True:
         request = walk.next_request()
         if request is None:
             return walk.result()
-        walk.accept(decode(model, *request))
+        walk.accept(decode(model, *request, **graph))
 
 
-def transcribe_many(model, audios, *, files_in_flight: int = FILES_IN_FLIGHT, **kw):
+def transcribe_many(model, audios, *, files_in_flight: int = FILES_IN_FLIGHT, graph: Optional[bool] = None, **kw):
     """``transcribe()`` of every item of ``audios`` (keywords as ``transcribe``'s, the same for all), with the current windows of up
     to ``files_in_flight`` files decoded together by ``decode_many``: a file's windows stay in order, files are independent.  After a
     round every file takes its result (a fallback is simply its request of the next round); a file that ends hands its slot to the
@@ -1725,6 +1897,7 @@ def transcribe_many(model, audios, *, files_in_flight: int = FILES_IN_FLIGHT, **
     call of its own when its result is taken).  Returns the files' dicts in input order, each equal to ``transcribe()``'s."""
     if files_in_flight < 1:
         raise ValueError(f"files_in_flight = {files_in_flight}: at least one file")
+    graph = _graph_kw(graph)
     audios = list(audios)
     out: List[Optional[Dict[str, object]]] = [None] * len(audios)
     waiting = iter(range(len(audios)))
@@ -1751,7 +1924,7 @@ def transcribe_many(model, audios, *, files_in_flight: int = FILES_IN_FLIGHT, **
     while any(s is not None for s in slots):
         live = [s for s in slots if s is not None]
         requests = [walk.next_request() for _, walk in live]
-        results = decode_many(model, [r[0] for r in requests], [r[1] for r in requests])
+        results = decode_many(model, [r[0] for r in requests], [r[1] for r in requests], **graph)
         for (_, walk), result in zip(live, results):
             walk.accept(result)
         slots = seat_all(slots)

@@ -1405,6 +1405,14 @@ typedef struct hirest_whisper_row_ctl {
 int hirest_whisper_step_tail_rows(const float* logits, int64_t ldx, int32_t R, int32_t V, int32_t call, int64_t ld_tokens,
                                   const hirest_whisper_tail_params* params, hirest_whisper_row_ctl* ctl, hirest_whisper_row_state* state,
                                   int32_t* next_ids, int32_t* tokens, float* logprobs, int32_t* done_host, void* stream);
+/* hirest_whisper_step_tail_rows with the call's number on the device: `count` is one device int32 (not NULL); the launch
+ * that writes the stamp reads it, writes *done_host = ((*count + 1) << 1) | (no row is active) (done_host optional, pinned host) and
+ * stores *count + 1.  No argument changes from call to call, so a captured sequence of calls can be replayed.  The tail launch is the
+ * same one: picks, tokens, state and ctl have hirest_whisper_step_tail_rows' bits. */
+int hirest_whisper_step_tail_rows_counted(const float* logits, int64_t ldx, int32_t R, int32_t V, int32_t* count, int64_t ld_tokens,
+                                          const hirest_whisper_tail_params* params, hirest_whisper_row_ctl* ctl,
+                                          hirest_whisper_row_state* state, int32_t* next_ids, int32_t* tokens, float* logprobs,
+                                          int32_t* done_host, void* stream);
 /* Language detection: for R rows of logits [R, V] (row stride ldx >= V), the softmax over the L language columns alone.
  * language_ids: L device ints, ascending, 1 <= L <= 128 (the tokenizer's language tokens).  lang_token[r] = the id with the largest
  * logit (the lower id on ties); probs[r * L + j] = exp(x[ids[j]] - max) / sum_j exp(x[ids[j]] - max).  One wave per row; the sum runs

@@ -12,6 +12,8 @@ model then detects each file's language on its first 30 seconds.  ``--task trans
 ``probability``); the ``.srt`` is what it is without the option.
 ``--precision bf16x3`` runs the audio encoder's blocks on split bf16 operands (the reference runs them at fp16); without
 it the environment's ``HIREST_WHISPER_PRECISION`` decides, else fp32.
+``--graph`` replays every decoding loop's iterations from a captured hipGraph: the same subtitles, fewer launches on
+the host; without it the environment's ``HIREST_WHISPER_GRAPH`` decides, else off.
 """
 import argparse
 import json
@@ -52,6 +54,8 @@ def main(argv=None):
     ap.add_argument("--word_timestamps", action="store_true", help="align every window's words (whisper.timing) and write <name>.json")
     ap.add_argument("--precision", type=str, default=None, choices=list(whisper.AudioEncoder.PRECISIONS),
                     help="the audio encoder's precision (default: HIREST_WHISPER_PRECISION, else fp32); the decoder is exact fp32 always")
+    ap.add_argument("--graph", action="store_true",
+                    help="replay the decoding loop from a captured hipGraph (default: HIREST_WHISPER_GRAPH, else off); the same output")
     args = ap.parse_args(argv)
     if args.files_in_flight < 1:
         ap.error("--files_in_flight must be at least 1")
@@ -67,6 +71,8 @@ def main(argv=None):
                    initial_prompt=None, condition_on_previous_text=True, fp16=True, compression_ratio_threshold=2.4, logprob_threshold=-1.0,
                    no_speech_threshold=0.6, seed=args.seed, word_timestamps=args.word_timestamps)
     temperatures = tuple(np.arange(temperature, 1.0 + 1e-6, temperature_increment_on_fallback))
+    if args.graph:
+        options["graph"] = True
 
     out_dir = Path(args.asr_dir)
     out_dir.mkdir(parents=True, exist_ok=True)

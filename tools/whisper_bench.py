@@ -6,7 +6,9 @@ encoder's rate as a fraction of the 157-TFLOP/s fp32 MFMA peak DESIGN.md uses fo
 shapes.  Each figure is the median with the min .. max spread over the repeats.  The decode leg: W windows through one
 run of the decoding loop (``decode_many``) against W one-window runs of the same loop (W sequential ``decode`` calls) at small.en's
 decoder shape; ``--prompt-len N`` gives every window N previous tokens as its prompt (``transcribe()`` with
-``condition_on_previous_text`` carries up to 223), so that the prefill has a prompt to run.  The detect leg: ``detect_language`` of W windows at multilingual small's decoder shape and the pieces of
+``condition_on_previous_text`` carries up to 223), so that the prefill has a prompt to run; ``--graph`` adds, per
+window count and per ``--graph-chunks`` value, ``decode_many(graph=True)`` against the eager ``decode_many``, the two
+alternating call by call in the same process.  The detect leg: ``detect_language`` of W windows at multilingual small's decoder shape and the pieces of
 that call; the step leg: the one ``hirest_whisper_decode_step_rows`` call inside it, alone.  The align leg:
 ``hirest_whisper_alignment_matrix`` and ``hirest_dtw_f32`` for one window at small.en's shape (12 layers, 72 selected heads, 1500 keys)
 with 50 and 220 tokens, each timed on its own, beside the numpy restatement of both on the CPU (tests/_whisper_align_ref.py, fp32).
@@ -17,7 +19,8 @@ batch size; the FLOP count is the same, the fraction is of the 157-TFLOP/s fp32 
 
     python tools/whisper_bench.py [--repeats 7] [--warmup 2] [--batches 1 8] [--legs encoder decode detect step align]
                                   [--precision fp32] [--x3-ab]
-                                  [--windows 1 2 4 8 16] [--prompt-len 0] [--detect_windows 1 16] [--align_tokens 50 220]
+                                  [--windows 1 2 4 8 16] [--prompt-len 0] [--graph] [--graph-chunks 8]
+                                  [--detect_windows 1 16] [--align_tokens 50 220]
 """
 import argparse
 import json
@@ -121,7 +124,9 @@ def decode_leg(a, dev):
     biased so far down that no row ends — through one decode_many() loop against W sequential decode() calls, which are W one-window
     runs of the same loop, in the same process; and the same two with one step, which is the prefill and everything else a window
     costs before its loop: that call's time is the "prefill ms" column.  ``--prompt-len N``: every window's prompt is <|startofprev|>,
-    N seeded text tokens (cut to the 223 the context admits) and <|startoftranscript|>; 0: <|startoftranscript|> alone."""
+    N seeded text tokens (cut to the 223 the context admits) and <|startoftranscript|>; 0: <|startoftranscript|> alone.
+    ``--graph``: after a window count's row, the same decode_many() with ``graph=True`` at every ``--graph-chunks`` length against the
+    eager call — eager and replayed calls alternate, one of each per repeat — with the spread of both."""
     cfg = synth._dec_config(768, 12, 12, 1500, 51864, 448)
     eot, steps = 50256, 64
     sd = synth.whisper_decoder_state_dict(cfg, 83, eot, -8.0)
@@ -156,7 +161,46 @@ def decode_leg(a, dev):
         print(f"  {W:2d} | {row['many_windows_per_s']:22.2f}  {row['many_ms_per_step']:7.3f}  {row['many_prefill_ms']:10.3f}  "
               f"{row['many_prefill_share']:13.3f} | {row['sequential_windows_per_s']:21.2f}  {row['sequential_ms_per_step']:7.3f}  "
               f"{row['sequential_prefill_ms']:10.3f}  {row['sequential_prefill_share']:13.3f} | {seq / many:5.2f}")
+        if a.graph:
+            row["graph"] = {str(chunk): graph_rows(a, model, xa, full, one, steps, chunk, [r.tokens for r in res]) for chunk in a.graph_chunks}
     return table
+
+
+def graph_rows(a, model, xa, full, one, steps, chunk, want_tokens):
+    """decode_many eager and with graph=True at one chunk length, alternating call by call: windows/s, ms per step and the prefill share
+    of each, medians with min .. max"""
+    W = int(xa.shape[0])
+    whisper.DECODE_GRAPH_CHUNK = chunk
+    before = model.graph_stats()
+    assert [r.tokens for r in whisper.decode_many(model, xa, full, graph=True)] == want_tokens, "the replayed loop differs from the eager one"
+    replays = model.graph_stats()["replays"] - before["replays"]
+
+    def once(options, graph):
+        t0 = time.perf_counter()
+        whisper.decode_many(model, xa, options, graph=graph)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    t = {(g, k): [] for g in (False, True) for k in ("full", "one")}
+    for i in range(a.warmup + a.repeats):
+        for g in (False, True):
+            for k, options in (("full", full), ("one", one)):
+                dt = once(options, g)
+                if i >= a.warmup:
+                    t[(g, k)].append(dt)
+    med = statistics.median
+    out = {"replays_per_call": replays}
+    for g, name in ((False, "eager"), (True, "graph")):
+        f, o = t[(g, "full")], t[(g, "one")]
+        out[name] = {"windows_per_s": W / med(f), "windows_per_s_min": W / max(f), "windows_per_s_max": W / min(f),
+                     "ms_per_step": (med(f) - med(o)) / (steps - 1) * 1e3, "prefill_ms": med(o) * 1e3, "prefill_share": med(o) / med(f),
+                     "call_ms": [round(x * 1e3, 4) for x in f]}
+        r = out[name]
+        print(f"     | W {W:2d} chunk {chunk:2d} {name}: windows/s {r['windows_per_s']:8.2f} ({r['windows_per_s_min']:.2f} .. {r['windows_per_s_max']:.2f})  "
+              f"ms/step {r['ms_per_step']:.3f}  prefill ms {r['prefill_ms']:.3f}  prefill share {r['prefill_share']:.3f}"
+              + (f"  replays per call {replays}" if g else ""))
+    out["graph_over_eager"] = out["graph"]["windows_per_s"] / out["eager"]["windows_per_s"]
+    print(f"     | W {W:2d} chunk {chunk:2d} graph / eager windows/s {out['graph_over_eager']:.3f}")
+    return out
 
 
 def step_rows_setup(model, xa, sot):
@@ -289,6 +333,9 @@ def main():
     ap.add_argument("--legs", nargs="+", choices=["encoder", "decode", "detect", "step", "align"], default=["encoder", "decode"])
     ap.add_argument("--windows", type=int, nargs="+", default=[1, 2, 4, 8, 16], help="windows per decode_many() call of the decode leg")
     ap.add_argument("--prompt-len", type=int, default=0, help="previous tokens in every window's prompt of the decode leg (0: none, as before)")
+    ap.add_argument("--graph", action="store_true", help="decode leg: also decode_many(graph=True), alternating with the eager call")
+    ap.add_argument("--graph-chunks", type=int, nargs="+", default=[whisper.DECODE_GRAPH_CHUNK],
+                    help="decode leg with --graph: iterations per captured graph (whisper.DECODE_GRAPH_CHUNK) to time")
     ap.add_argument("--detect_windows", type=int, nargs="+", default=[1, 16], help="windows per detect_language() call of the detect leg")
     ap.add_argument("--align_tokens", type=int, nargs="+", default=[50, 220], help="tokens of the teacher-forced pass of the align leg")
     a = ap.parse_args()
