@@ -614,25 +614,73 @@ def _seq_table(seqs):
 class KVCache:
     """What a decoding loop keeps between steps: per layer the preallocated self-attention cache ``[R, T_max, D]`` (key, value), the
     cross-attention ``key(xa) | value(xa)`` rows ``[n_windows, Tk, 2 D]``, ``row_window [R]`` and the number of filled positions.
-    ``per_row``: the rows sit at positions of their own (the decoding loop of ``decode`` and ``decode_many``): the workspace is
-    ``hirest_whisper_decode_step_rows``'s and ``length`` is not used."""
+    ``per_row``: the rows sit at positions of their own (``TextDecoder.step_rows``: ``detect_language``, and the decoding loop's
+    ``DecodeState``): the workspace is ``hirest_whisper_decode_step_rows``'s and ``length`` is not used."""
 
     def __init__(self, decoder: "TextDecoder", xa: torch.Tensor, row_window: torch.Tensor, T_max: Optional[int] = None, per_row: bool = False):
-        dev, D = xa.device, decoder.width
-        self.R, self.T_max, self.length = int(row_window.numel()), int(T_max or decoder.ctx), 0
-        self.n_windows, self.Tk = int(xa.shape[0]), int(xa.shape[1])
-        self.row_window = row_window.to(dev, torch.int32).contiguous()
-        self.self_k = [torch.empty((self.R, self.T_max, D), dtype=torch.float32, device=dev) for _ in range(decoder.layers)]
-        self.self_v = [torch.empty((self.R, self.T_max, D), dtype=torch.float32, device=dev) for _ in range(decoder.layers)]
-        self.cross_kv = decoder.cross_kv(xa)
-        P = C.c_void_p * decoder.layers
+        self._allocate(decoder, int(row_window.numel()), int(xa.shape[0]), int(xa.shape[1]), int(T_max or decoder.ctx), per_row)
+        self.load(decoder, xa, row_window)
+
+    def _allocate(self, decoder: "TextDecoder", R: int, n_windows: int, Tk: int, T_max: int, per_row: bool) -> None:
+        dev, D, L = decoder.device, decoder.width, decoder.layers
+        self.R, self.T_max, self.length, self.n_windows, self.Tk = R, T_max, 0, n_windows, Tk
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        self.row_window = torch.empty((R,), dtype=torch.int32, device=dev)
+        self.self_k, self.self_v = [f32(R, T_max, D) for _ in range(L)], [f32(R, T_max, D) for _ in range(L)]
+        self.cross_kv = [f32(n_windows, Tk, 2 * D) for _ in range(L)]
+        P = C.c_void_p * L
         self.k_ptrs, self.v_ptrs = P(*(t.data_ptr() for t in self.self_k)), P(*(t.data_ptr() for t in self.self_v))
         self.x_ptrs = P(*(t.data_ptr() for t in self.cross_kv))
-        self.logits = torch.empty((self.R, decoder.vocab_padded), dtype=torch.float32, device=dev)
+        self.logits = f32(R, decoder.vocab_padded)
         lib = _lib.load()
         need = (lib.hirest_whisper_step_rows_workspace_bytes if per_row else lib.hirest_whisper_step_workspace_bytes)(
-            C.byref(decoder._w()["desc"]), self.R, self.Tk)
+            C.byref(decoder._w()["desc"]), R, Tk)
         self.ws = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=dev)
+
+    def load(self, decoder: "TextDecoder", xa: torch.Tensor, row_window: torch.Tensor) -> None:
+        """a loop's windows: ``row_window`` and every layer's cross key | value rows, computed into the cache's own buffers"""
+        self.row_window.copy_(row_window)
+        decoder.cross_kv(xa, self.cross_kv)
+
+
+class DecodeState(KVCache):
+    """Everything a per-row decoding loop reads and writes between its prefill and its read-back: a per-row ``KVCache`` of ``T_max``
+    positions, and the rows' records (``ctl``), states, next ids, tokens ``[R, slots]``, the suppress mask, the counted tail's call
+    counter and the pinned stamp.  The eager loop makes one per loop, as large as its prompts and step budgets need; the replayed loop
+    keeps one per shape at the decoder's whole context (``_decode_arena``: addresses that do not change from loop to loop), whose
+    ``graph`` is the captured chunk and ``graph_key`` what it was captured with: another key captures again."""
+
+    def __init__(self, decoder: "TextDecoder", R: int, n_windows: int, Tk: int, T_max: int, slots: int):
+        self._allocate(decoder, R, n_windows, Tk, T_max, per_row=True)
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=decoder.device)
+        self.ctl, self.state = i32(R, _lib.WHISPER_ROW_CTL_WORDS), i32(R, _lib.WHISPER_ROW_STATE_WORDS)
+        self.ids, self.tokens = i32(R), i32(R, slots)
+        self.mask, self.count = i32((decoder.vocab_padded + 31) // 32), i32(1)
+        self.stamp = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self.stamp_host = self.stamp.numpy()                          # the same word, read without a tensor per poll
+        self.graph, self.graph_key = None, None
+
+    def reset(self, ctl_rows, eot: int, last: torch.Tensor) -> None:
+        """a loop's rows: their records from ``(position, step, max_steps, draw_row, seed, temperature)`` per row, a fresh state, no
+        token yet, and as first logits the last prompt position's of each row's window (``last [n_windows, vocab_padded]``)"""
+        self.ctl.copy_(new_row_ctl(ctl_rows, "cpu"))
+        self.state.copy_(new_row_state(self.R, "cpu"))
+        self.tokens.fill_(eot)
+        self.ids.zero_()
+        torch.index_select(last, 0, self.row_window, out=self.logits)      # every iteration reads its logits at the same address
+        self.stamp_host[0] = 0                                        # (the loop before this one ended with a synchronisation)
+
+    def tail(self, params, call: Optional[int] = None, stream=None) -> None:
+        """The rows' next tokens from ``logits``: with ``call``, the loop's call number, ``hirest_whisper_step_tail_rows``; without, the
+        counted entry, which keeps that number on the device (``count``) so that a captured launch serves every call."""
+        lib, Vp = _lib.load(), int(self.logits.shape[1])
+        rest = (int(self.tokens.shape[1]), C.byref(params), self.ctl.data_ptr(), self.state.data_ptr(), self.ids.data_ptr(),
+                self.tokens.data_ptr(), None, self.stamp.data_ptr(), ops.stream_ptr() if stream is None else stream)
+        if call is None:
+            _lib.check(lib.hirest_whisper_step_tail_rows_counted(self.logits.data_ptr(), Vp, self.R, Vp, self.count.data_ptr(), *rest),
+                       "hirest_whisper_step_tail_rows_counted")
+        else:
+            _lib.check(lib.hirest_whisper_step_tail_rows(self.logits.data_ptr(), Vp, self.R, Vp, call, *rest), "hirest_whisper_step_tail_rows")
 
 
 class TextDecoder(_FrozenWeights):
@@ -708,13 +756,18 @@ class TextDecoder(_FrozenWeights):
         return c
 
     @torch.no_grad()
-    def cross_kv(self, xa: torch.Tensor):
-        """``xa [n_windows, Tk, D]`` -> per layer ``[n_windows, Tk, 2 D]``: the layer's ``key(xa) | value(xa)``, computed once per window"""
-        c = self._w()
+    def cross_kv(self, xa: torch.Tensor, out: Optional[List[torch.Tensor]] = None):
+        """``xa [n_windows, Tk, D]`` -> per layer ``[n_windows, Tk, 2 D]``: the layer's ``key(xa) | value(xa)``, computed once per window;
+        into ``out``'s tensors where they are given"""
+        c, dev = self._w(), self.device
         W, Tk, D = xa.shape
-        rows = xa.to(self.device, torch.float32).contiguous().view(W * Tk, D)
-        with torch.cuda.device(self.device):
-            return [_linear(rows, c[f"ckv_w.{i}"], c[f"ckv_b.{i}"]).view(W, Tk, 2 * D) for i in range(self.layers)]
+        rows = xa.to(dev, torch.float32).contiguous().view(W * Tk, D)
+        with torch.cuda.device(dev):
+            if out is None:
+                out = [torch.empty((W, Tk, 2 * D), dtype=torch.float32, device=dev) for _ in range(self.layers)]
+            for i, kv in enumerate(out):
+                _gemm(rows.data_ptr(), D, c[f"ckv_w.{i}"], c[f"ckv_b.{i}"], kv.data_ptr(), 2 * D, W * Tk, dev)
+        return out
 
     def _sequences(self, tokens: torch.Tensor, cross_kv, Tk: int, keep=None, keep_cross_q=None):
         """[B, T] tokens (sequence b against window b of cross_kv) -> [B * T, D] states before ``ln``; ``keep(i, qkv)`` sees every layer's
@@ -861,6 +914,15 @@ class TextDecoder(_FrozenWeights):
                                                           kc.x_ptrs, kc.n_windows, kc.Tk, kc.row_window.data_ptr(), kc.logits.data_ptr(),
                                                           kc.ws.data_ptr(), kc.ws.numel(), ops.stream_ptr()), "hirest_whisper_decode_step")
         kc.length += 1
+        return kc.logits
+
+    def step_rows(self, ctl: torch.Tensor, ids: torch.Tensor, kc: KVCache, stream=None) -> torch.Tensor:
+        """one position for every row of a per-row cache that its record ``ctl [R, 8]`` has at a position (a row at -1 is left alone):
+        ``ids`` int32 ``[R]`` on the device -> ``kc.logits [R, vocab_padded]``; on ``stream`` (a raw handle) or the current one"""
+        _lib.check(_lib.load().hirest_whisper_decode_step_rows(C.byref(self._w()["desc"]), kc.R, ctl.data_ptr(), ids.data_ptr(), kc.k_ptrs, kc.v_ptrs,
+                                                               kc.T_max, kc.x_ptrs, kc.n_windows, kc.Tk, kc.row_window.data_ptr(),
+                                                               kc.logits.data_ptr(), kc.ws.data_ptr(), kc.ws.numel(),
+                                                               ops.stream_ptr() if stream is None else stream), "hirest_whisper_decode_step_rows")
         return kc.logits
 
 
@@ -1290,10 +1352,7 @@ def detect_language(model: "Whisper", mel: torch.Tensor, tokenizer: Optional[Tok
             kc = KVCache(dec, xa[r0:r0 + R], torch.arange(R, dtype=torch.int32), 1, per_row=True)
             ctl = new_row_ctl([(0, 0, 1, 0, 0, 0.0)] * R, dev)                   # every row at position 0
             ids = torch.full((R,), tokenizer.sot, dtype=torch.int32, device=dev)
-            _lib.check(lib.hirest_whisper_decode_step_rows(C.byref(dec._w()["desc"]), R, ctl.data_ptr(), ids.data_ptr(), kc.k_ptrs, kc.v_ptrs,
-                                                           kc.T_max, kc.x_ptrs, kc.n_windows, kc.Tk, kc.row_window.data_ptr(),
-                                                           kc.logits.data_ptr(), kc.ws.data_ptr(), kc.ws.numel(), ops.stream_ptr()),
-                       "hirest_whisper_decode_step_rows")
+            dec.step_rows(ctl, ids, kc)
             _lib.check(lib.hirest_whisper_language_tail(kc.logits.data_ptr(), dec.vocab_padded, R, dec.vocab, ids_table.data_ptr(), L,
                                                         found[r0:].data_ptr(), probs[r0:].data_ptr(), ops.stream_ptr()),
                        "hirest_whisper_language_tail")
@@ -1320,7 +1379,8 @@ def decode(model: "Whisper", mel: torch.Tensor, options: DecodingOptions = Decod
     single = mel.ndim == 2
     if single:
         mel = mel[None]
-    results, everything = _decode_windows(model, mel, [options] * int(mel.shape[0]), 0, **_graph_kw(graph))      # 0 rows fit beside a window: one per loop
+    results, everything = _decode_windows(model, mel, [options] * int(mel.shape[0]), 0,         # 0 rows fit beside a window: one per loop
+                                          **({"graph": True} if resolve_graph(graph) else {}))
     if return_candidates:
         return (results[0], everything[0]) if single else (results, everything)
     return results[0] if single else results
@@ -1345,7 +1405,7 @@ def decode_many(model: "Whisper", mels, options: Union[DecodingOptions, Sequence
     for f in dataclasses.fields(DecodingOptions):
         if f.name not in _PER_WINDOW_OPTIONS and any(getattr(o, f.name) != getattr(opts[0], f.name) for o in opts):
             raise ValueError(f"decode_many: {f.name} differs between the windows of one call (only {', '.join(_PER_WINDOW_OPTIONS)} may)")
-    results, everything = _decode_windows(model, mel, opts, _ROWS_PER_CALL, **_graph_kw(graph))
+    results, everything = _decode_windows(model, mel, opts, _ROWS_PER_CALL, **({"graph": True} if resolve_graph(graph) else {}))
     return (results, everything) if return_candidates else results
 
 
@@ -1384,7 +1444,7 @@ def _decode_windows(model, mel, opts, rows_per_loop, graph=False):
             while w1 < len(plans) and rows + plans[w1][3] <= rows_per_loop:
                 rows += plans[w1][3]
                 w1 += 1
-            res, cands = _decode_rows(model, xa[w0:w1], opts[w0:w1], plans[w0:w1], langs[w0:w1], **_graph_kw(graph))
+            res, cands = _decode_rows(model, xa[w0:w1], opts[w0:w1], plans[w0:w1], langs[w0:w1], graph)
             results += res
             everything += cands
             w0 = w1
@@ -1393,22 +1453,19 @@ def _decode_windows(model, mel, opts, rows_per_loop, graph=False):
 
 # The loop replayed from a hipGraph.  Every per-step quantity is on the device (the rows' records, and the call's number
 # in the counted tail), so ONE captured run of DECODE_GRAPH_CHUNK x {tail, step} serves every token of every window whose loop has the
-# arena's shape: the buffers of a loop live in an arena with stable addresses, keyed by (device, stream, R, n_windows, Tk).
+# arena's shape: the eager loop's ``DecodeState`` at the decoder's whole context, kept for its stable addresses under (device, stream,
+# R, n_windows, Tk).  The loops differ in who issues the iterations (``_eager_loop`` / ``_replay_loop``) and in the tail's entry only.
 DECODE_GRAPH_CHUNK = 8         # iterations per captured graph (as CAPTION_GRAPH_CHUNK; profiles/whisper_graph.txt has 4 and 16 beside it)
 DECODE_ARENAS = 4              # arenas kept per decoder, least recently used first out
 
 
 def resolve_graph(graph: Optional[bool]) -> bool:
     """The ``graph=`` keyword of ``decode`` / ``decode_many`` / ``transcribe`` / ``transcribe_many``: the keyword where it is given, else
-    the environment's ``HIREST_WHISPER_GRAPH`` (set and not ``0``), else off."""
+    the environment's ``HIREST_WHISPER_GRAPH`` (set and not ``0``), else off.  Each of the four hands ``graph=True`` on where it is on
+    and nothing where it is off (the calls of before, which the host tests' stand-ins take); ``_decode_windows`` hands on a plain bool."""
     if graph is not None:
         return bool(graph)
     return os.environ.get("HIREST_WHISPER_GRAPH", "").strip() not in ("", "0")
-
-
-def _graph_kw(graph: Optional[bool]) -> Dict[str, bool]:
-    """what a caller hands on: ``graph=True`` where the option resolves to on, nothing where it is off — the calls of before"""
-    return {"graph": True} if resolve_graph(graph) else {}
 
 
 def graph_throttle(issued: int, stamp: int, chunk: int, max_steps: int) -> str:
@@ -1427,47 +1484,10 @@ def graph_throttle(issued: int, stamp: int, chunk: int, max_steps: int) -> str:
     return "issue"
 
 
-class _DecodeArena:
-    """Everything a decoding loop of one shape reads and writes between its prefill and its read-back, at addresses that do not change
-    from loop to loop: what ``KVCache`` holds (same attribute names: ``prefill_many`` and the step take either), with the self caches
-    ``[R, n_text_ctx, D]`` whatever the prompts' lengths, and the rows' records, states, ids, tokens ``[R, n_text_ctx // 2]``, the
-    suppress mask, the tail's call counter and the pinned stamp.  ``graph`` is the captured chunk, ``graph_key`` what it was captured
-    with (the tail's constants and the chunk length): another key captures again."""
-
-    def __init__(self, decoder: "TextDecoder", R: int, n_windows: int, Tk: int):
-        dev, D, L = decoder.device, decoder.width, decoder.layers
-        self.R, self.T_max, self.length, self.n_windows, self.Tk = R, decoder.ctx, 0, n_windows, Tk
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
-        self.row_window = i32(R)
-        self.self_k, self.self_v = [f32(R, self.T_max, D) for _ in range(L)], [f32(R, self.T_max, D) for _ in range(L)]
-        self.cross_kv = [f32(n_windows, Tk, 2 * D) for _ in range(L)]
-        P = C.c_void_p * L
-        self.k_ptrs, self.v_ptrs = P(*(t.data_ptr() for t in self.self_k)), P(*(t.data_ptr() for t in self.self_v))
-        self.x_ptrs = P(*(t.data_ptr() for t in self.cross_kv))
-        self.logits = f32(R, decoder.vocab_padded)
-        need = _lib.load().hirest_whisper_step_rows_workspace_bytes(C.byref(decoder._w()["desc"]), R, Tk)
-        self.ws = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=dev)
-        self.ctl, self.state = i32(R, _lib.WHISPER_ROW_CTL_WORDS), i32(R, _lib.WHISPER_ROW_STATE_WORDS)
-        self.ids, self.tokens = i32(R), i32(R, max(decoder.ctx // 2, 1))
-        self.mask, self.count = i32((decoder.vocab_padded + 31) // 32), i32(1)
-        self.stamp = torch.zeros(1, dtype=torch.int32).pin_memory()
-        self.stamp_host = self.stamp.numpy()                          # the same word, read without a tensor per poll
-        self.graph, self.graph_key = None, None
-
-    def load(self, decoder: "TextDecoder", xa: torch.Tensor, row_window: torch.Tensor) -> None:
-        """a loop's windows: ``row_window`` and every layer's cross key | value rows, computed into the arena's own buffers"""
-        c, dev, D = decoder._w(), decoder.device, decoder.width
-        self.row_window.copy_(row_window)
-        rows = xa.to(dev, torch.float32).contiguous().view(self.n_windows * self.Tk, D)
-        for i, out in enumerate(self.cross_kv):
-            _gemm(rows.data_ptr(), D, c[f"ckv_w.{i}"], c[f"ckv_b.{i}"], out.data_ptr(), 2 * D, rows.shape[0], dev)
-
-
-def _decode_arena(decoder: "TextDecoder", R: int, n_windows: int, Tk: int) -> _DecodeArena:
-    """The arena of (device, current stream, R, n_windows, Tk), made on first use.  The arenas live in the decoder's weight
-    preparation — their graphs hold its addresses — so any move or cast drops them all; of more than ``DECODE_ARENAS`` the least
-    recently used goes."""
+def _decode_arena(decoder: "TextDecoder", R: int, n_windows: int, Tk: int) -> DecodeState:
+    """The arena of (device, current stream, R, n_windows, Tk), made on first use: a ``DecodeState`` of the decoder's whole context
+    per row and ``n_text_ctx // 2`` tokens.  The arenas live in the decoder's weight preparation — their graphs hold its addresses —
+    so any move or cast drops them all; of more than ``DECODE_ARENAS`` the least recently used goes."""
     arenas = decoder._w().setdefault("decode_arenas", collections.OrderedDict())
     dev = decoder.device
     with torch.cuda.device(dev):
@@ -1475,91 +1495,94 @@ def _decode_arena(decoder: "TextDecoder", R: int, n_windows: int, Tk: int) -> _D
         if key not in arenas:
             while len(arenas) >= DECODE_ARENAS:
                 arenas.popitem(last=False)
-            arenas[key] = _DecodeArena(decoder, R, n_windows, Tk)
+            arenas[key] = DecodeState(decoder, R, n_windows, Tk, decoder.ctx, decoder.ctx // 2)
     arenas.move_to_end(key)
     return arenas[key]
 
 
-def _replay_loop(dec, arena: _DecodeArena, params, max_steps: int) -> None:
-    """The loop's iterations on an arena whose ``logits`` hold the prefill's: iteration 0 eagerly (also the warm-up of a capture), then
-    the captured chunk of ``DECODE_GRAPH_CHUNK`` x {counted tail, step} replayed as ``graph_throttle`` says.  The only thing the host
-    reads is the pinned stamp; nothing here synchronises with the device but a capture."""
-    lib, a, Vp, R = _lib.load(), arena, dec.vocab_padded, arena.R
-    desc, ld_tokens = C.byref(dec._w()["desc"]), int(a.tokens.shape[1])
+def _eager_loop(dec: "TextDecoder", kc: DecodeState, params, max_steps: int) -> None:
+    """The loop's iterations launch by launch: tail, then step, until the pinned stamp says that no row is active; no step after the last tail."""
+    for call in range(max_steps):
+        dec.graph_stats["eager_steps"] += 1
+        kc.tail(params, call)
+        if (int(kc.stamp_host[0]) & 1) or call == max_steps - 1:      # whatever call has landed by now: no wait
+            break
+        dec.step_rows(kc.ctl, kc.ids, kc)
+
+
+def _replay_loop(dec: "TextDecoder", kc: DecodeState, params, max_steps: int) -> None:
+    """The same iterations on an arena: iteration 0 eagerly (also the warm-up of a capture), then the captured chunk of
+    ``DECODE_GRAPH_CHUNK`` x {counted tail, step} replayed as ``graph_throttle`` says.  The only thing the host reads is the pinned
+    stamp; nothing here synchronises with the device but a capture."""
     stats = dec.graph_stats
 
     def iteration(stream):
-        _lib.check(lib.hirest_whisper_step_tail_rows_counted(a.logits.data_ptr(), Vp, R, Vp, a.count.data_ptr(), ld_tokens, C.byref(params),
-                                                             a.ctl.data_ptr(), a.state.data_ptr(), a.ids.data_ptr(), a.tokens.data_ptr(), None,
-                                                             a.stamp.data_ptr(), stream), "hirest_whisper_step_tail_rows_counted")
-        _lib.check(lib.hirest_whisper_decode_step_rows(desc, R, a.ctl.data_ptr(), a.ids.data_ptr(), a.k_ptrs, a.v_ptrs, a.T_max, a.x_ptrs,
-                                                       a.n_windows, a.Tk, a.row_window.data_ptr(), a.logits.data_ptr(), a.ws.data_ptr(),
-                                                       a.ws.numel(), stream), "hirest_whisper_decode_step_rows")
+        kc.tail(params, stream=stream)
+        dec.step_rows(kc.ctl, kc.ids, kc, stream)
     # what a capture bakes in beside the arena's addresses: the tail's constants (not the four fields the rows' records replace)
     baked = type(params).from_buffer_copy(params)
     baked.temperature, baked.seed, baked.serial, baked.sample_begin = 0.0, 0, 0, 0
-    key = (bytes(baked), ld_tokens, max(1, int(DECODE_GRAPH_CHUNK)))
-    a.stamp_host[0] = 0                                               # (the loop before this one ended with a synchronisation)
-    a.count.zero_()
+    key = (bytes(baked), int(kc.tokens.shape[1]), max(1, int(DECODE_GRAPH_CHUNK)))
+    kc.count.zero_()
     iteration(ops.stream_ptr())
     stats["eager_steps"] += 1
     chunk = key[2]
     issued, stream, polls = 0, torch.cuda.current_stream(), 0
     while True:
-        seen = int(a.stamp_host[0])
+        seen = int(kc.stamp_host[0])
         act = graph_throttle(issued, seen, chunk, max_steps)
         if act == "stop":
             return
         if act == "wait":
             polls += 1
-            if polls % 4096 == 0 and stream.query() and int(a.stamp_host[0]) == seen:      # an idle stream and no new stamp: no tail will land
+            if polls % 4096 == 0 and stream.query() and int(kc.stamp_host[0]) == seen:      # an idle stream and no new stamp: no tail will land
                 raise RuntimeError(f"{_NAME}: the replayed decoding loop stopped at stamp {seen} with {issued} chunks issued")
             continue
-        if a.graph is None or a.graph_key != key:
-            a.graph = a.graph_key = None
+        if kc.graph is None or kc.graph_key != key:
+            kc.graph = kc.graph_key = None
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 st = ops.stream_ptr()
                 for _ in range(chunk):
                     iteration(st)
-            a.graph, a.graph_key = g, key
+            kc.graph, kc.graph_key = g, key
             stats["captures"] += 1
-        a.graph.replay()
+        kc.graph.replay()
         stats["replays"] += 1
         issued, polls = issued + 1, 0
 
 
 def _decode_rows(model, xa, opts, plans, langs, graph: bool = False):
-    """THE decoding loop, over the candidate rows of ``xa``'s windows: one cross key / value projection for all windows, one cache of
-    all rows, one ragged prefill of all windows' prompts (``prefill_many``), then per token ``hirest_whisper_step_tail_rows`` + ``hirest_whisper_decode_step_rows`` over
-    all rows — each at its own position, with its own temperature, seed and remaining room, kept in a device record per row — until
-    no row is active.  Nothing is read back in the loop but the pinned stamp; tokens and sums are read once at the end.
-    ``graph``: the same calls on the buffers of a ``_DecodeArena`` (a cache of the decoder's whole context per row), the iterations after
-    the first replayed from the arena's captured chunk (``_replay_loop``) — the same bits."""
+    """THE decoding loop, over the candidate rows of ``xa``'s windows: one ``DecodeState`` for all rows, one cross key / value
+    projection for all windows into it (``load``), one ragged prefill of all windows' prompts (``prefill_many``), the rows' records
+    and first logits (``reset``), then per token a tail (``DecodeState.tail``) and a step (``TextDecoder.step_rows``) over all rows —
+    each at its own position, with its own temperature, seed and remaining room, kept in a device record per row — until no row is
+    active.  Nothing is read back in the loop but the pinned stamp; tokens and sums are read once at the end.
+    ``graph`` chooses the state and who issues the iterations, nothing else: off, a state sized for this loop and ``_eager_loop``; on,
+    the arena of the loop's shape and ``_replay_loop``, which replays the iterations after the first — the same bits."""
     tokenizer, dec, dev, lib = model.tokenizer, model.decoder, model.device, _lib.load()
     Vp = dec.vocab_padded
     first_row = np.cumsum([0] + [p[3] for p in plans]).tolist()
     R = first_row[-1]
-    T_max = max(len(initial) + steps for initial, _, steps, _ in plans)
     max_steps = max(steps for _, _, steps, _ in plans)
     row_window = torch.tensor([w for w, p in enumerate(plans) for _ in range(p[3])], dtype=torch.int32)
-    # the constants every window shares; temperature, seed, serial and sample_begin are the rows' own (hirest_whisper_row_ctl)
-    params, mask = tail_params(tokenizer, opts[0], dec.vocab, Vp, model.dims["n_audio_ctx"], 0, dev)
     if graph:
         if max_steps > dec.ctx // 2:
             raise ValueError(f"graph=True: {max_steps} steps to sample, the arena's tokens hold n_text_ctx // 2 = {dec.ctx // 2}")
-        kc = _decode_arena(dec, R, int(xa.shape[0]), int(xa.shape[1]))
-        kc.load(dec, xa, row_window)
-        kc.mask.copy_(mask)
-        params.suppress_mask = kc.mask.data_ptr()
+        kc, run = _decode_arena(dec, R, int(xa.shape[0]), int(xa.shape[1])), _replay_loop
     else:
-        kc = KVCache(dec, xa, row_window, T_max, per_row=True)
+        T_max = max(len(initial) + steps for initial, _, steps, _ in plans)
+        kc, run = DecodeState(dec, R, int(xa.shape[0]), int(xa.shape[1]), T_max, max_steps), _eager_loop
+    kc.load(dec, xa, row_window)
+    # the constants every window shares; temperature, seed, serial and sample_begin are the rows' own (hirest_whisper_row_ctl)
+    params, mask = tail_params(tokenizer, opts[0], dec.vocab, Vp, model.dims["n_audio_ctx"], 0, "cpu")
+    kc.mask.copy_(mask)
+    params.suppress_mask = kc.mask.data_ptr()
     # every window's prompt in one ragged pass: the caches, the logits of the last position and, where it is another one, of sot's
     groups = [p[3] for p in plans]
     want_sot = tokenizer.no_speech is not None
     last, at_sot = dec.prefill_many([p[0] for p in plans], kc, first_row[:-1], groups, range(len(plans)),
                                     [p[1] for p in plans] if want_sot else None)
-    first = last.index_select(0, kc.row_window) if R != len(plans) else last          # a window's candidate rows start from the same logits
     no_speech, ctl_rows = [], []
     for w, (initial, sot_index, steps, group) in enumerate(plans):
         T = len(initial)
@@ -1571,35 +1594,10 @@ def _decode_rows(model, xa, opts, plans, langs, graph: bool = False):
                                                     None, None, ops.stream_ptr()), "hirest_whisper_step_tail")
         no_speech.append(scratch)
         ctl_rows += [(T - 1, 0, steps, g, opts[w].seed, opts[w].temperature) for g in range(group)]
-    if graph:
-        kc.ctl.copy_(new_row_ctl(ctl_rows, "cpu"))
-        kc.state.copy_(new_row_state(R, "cpu"))
-        kc.tokens.fill_(tokenizer.eot)
-        kc.ids.zero_()
-        kc.logits.copy_(first)                                        # every iteration reads its logits at the same address
-        state, tokens = kc.state, kc.tokens
-        _replay_loop(dec, kc, params, max_steps)
-    else:
-        ctl = new_row_ctl(ctl_rows, dev)
-        state = new_row_state(R, dev)
-        tokens = torch.full((R, max_steps), tokenizer.eot, dtype=torch.int32, device=dev)
-        ids = torch.zeros((R,), dtype=torch.int32, device=dev)
-        stamp = torch.zeros(1, dtype=torch.int32).pin_memory()
-    desc, logits = C.byref(dec._w()["desc"]), first
-    for call in range(0 if graph else max_steps):                   # (a replayed loop has made its calls)
-        dec.graph_stats["eager_steps"] += 1
-        _lib.check(lib.hirest_whisper_step_tail_rows(logits.data_ptr(), Vp, R, Vp, call, max_steps, C.byref(params), ctl.data_ptr(), state.data_ptr(),
-                                                     ids.data_ptr(), tokens.data_ptr(), None, stamp.data_ptr(), ops.stream_ptr()),
-                   "hirest_whisper_step_tail_rows")
-        s = int(stamp[0])                                             # whatever call has landed by now: no wait
-        if (s & 1) or call == max_steps - 1:
-            break
-        _lib.check(lib.hirest_whisper_decode_step_rows(desc, R, ctl.data_ptr(), ids.data_ptr(), kc.k_ptrs, kc.v_ptrs, kc.T_max, kc.x_ptrs,
-                                                       kc.n_windows, kc.Tk, kc.row_window.data_ptr(), kc.logits.data_ptr(), kc.ws.data_ptr(),
-                                                       kc.ws.numel(), ops.stream_ptr()), "hirest_whisper_decode_step_rows")
-        logits = kc.logits
+    kc.reset(ctl_rows, tokenizer.eot, last)
+    run(dec, kc, params, max_steps)
     torch.cuda.current_stream().synchronize()
-    toks, st = tokens.cpu().numpy(), state.cpu()
+    toks, st = kc.tokens.cpu().numpy(), kc.state.cpu()
     sums = st[:, 5].view(torch.float32).tolist()
     results, everything = [], []
     for w, (initial, sot_index, steps, group) in enumerate(plans):
@@ -1683,7 +1681,7 @@ class Whisper(nn.Module):
         return self.decoder(tokens, self.encoder(mel))
 
     def decode(self, mel, options: DecodingOptions = DecodingOptions(), *, graph: Optional[bool] = None):
-        return decode(self, mel, options, **_graph_kw(graph))
+        return decode(self, mel, options, graph=graph)
 
     def graph_stats(self) -> Dict[str, int]:
         """Counts since the model was made: ``captures`` (hipGraphs captured by the replayed decoding loop), ``replays`` (chunks
@@ -1879,7 +1877,7 @@ def transcribe(model, audio, *, graph: Optional[bool] = None, **kw):
     (``detect_language``, once per file) — every window decodes in it and the result's ``"language"`` is its code; ``task`` is
     "transcribe" or "translate".  An English-only model ignores both: ``"language"`` is "en".  ``graph`` as ``decode``'s: every window's
     loop is replayed from a captured hipGraph."""
-    graph = _graph_kw(graph)
+    graph = {"graph": True} if resolve_graph(graph) else {}
     walk = _FileWalk(model, audio, **kw)
     while True:
         request = walk.next_request()
@@ -1897,7 +1895,7 @@ def transcribe_many(model, audios, *, files_in_flight: int = FILES_IN_FLIGHT, gr
     call of its own when its result is taken).  Returns the files' dicts in input order, each equal to ``transcribe()``'s."""
     if files_in_flight < 1:
         raise ValueError(f"files_in_flight = {files_in_flight}: at least one file")
-    graph = _graph_kw(graph)
+    graph = {"graph": True} if resolve_graph(graph) else {}
     audios = list(audios)
     out: List[Optional[Dict[str, object]]] = [None] * len(audios)
     waiting = iter(range(len(audios)))

@@ -308,6 +308,83 @@ def test_graph_refuses_more_steps_than_its_tokens_hold(dev):
         whisper.decode(m, xa[0], O(temperature=0.0, sample_len=30), graph=True)
 
 
+# ---------------------------------------------------------------------------------------------------------------- the loop state
+def eager_loop_state(dev, monkeypatch):
+    """``_decode_rows`` without the option over two windows of case p whose prompts differ in length, one greedy row and two sampled
+    ones, three steps each -> (model, xa [2, 33, 128], the state the loop made, the prompts' lengths, what graph_stats moved by)"""
+    m, _, _ = model("p", dev)
+    m.float()                                                          # (whatever arenas the tests before left: gone)
+    cfg, _, seed, _ = synth.WHISPER_DEC_CASES["p"]
+    xa = synth.whisper_audio_states(cfg, 2, seed + 100).to(dev)
+    opts = [O(temperature=0.0, sample_len=3), O(temperature=0.4, best_of=2, seed=3, sample_len=3, prompt=[5, 6, 7, 8, 9])]
+    plans = []
+    for o in opts:
+        initial, sot_index = whisper._initial_tokens(m.tokenizer, o, m.decoder.ctx)
+        plans.append((initial, sot_index, 3, (o.best_of or 1) if o.temperature > 0 else 1))
+    made, init = [], whisper.DecodeState.__init__
+
+    def spy(self, *a, **k):
+        made.append(self)
+        init(self, *a, **k)
+    monkeypatch.setattr(whisper.DecodeState, "__init__", spy)
+    before = m.graph_stats()
+    results, cands = whisper._decode_rows(m, xa, opts, plans, [(None, None)] * 2)
+    assert len(made) == 1 and [len(c) for c in cands] == [1, 2] and all(len(r.tokens) <= 3 for r in results)
+    return m, xa, made[0], [len(p[0]) for p in plans], delta(m, before)
+
+
+def test_eager_state_is_sized_by_its_loop(dev, monkeypatch):
+    m, xa, state, lengths, d = eager_loop_state(dev, monkeypatch)
+    dec = m.decoder
+    assert lengths[1] - lengths[0] == 6 and max(lengths) + 3 < dec.ctx          # <|startofprev|> + 5 previous tokens
+    assert state.R == 3 and state.T_max == max(lengths) + 3
+    for t in state.self_k + state.self_v:
+        assert t.shape == (3, max(lengths) + 3, dec.width)
+    assert state.tokens.shape == (3, 3) and state.row_window.tolist() == [0, 1, 1]
+    assert not dec._w().get("decode_arenas")                           # absent, or empty
+    assert d["captures"] == d["replays"] == 0 and 1 <= d["eager_steps"] <= 3, d
+
+
+def test_both_loops_run_on_one_state_class(dev, monkeypatch):
+    m, xa, state, _, _ = eager_loop_state(dev, monkeypatch)
+    dec = m.decoder
+    arena = whisper._decode_arena(dec, 3, 2, int(xa.shape[1]))
+    assert type(arena) is type(state) and isinstance(arena, whisper.KVCache)
+    assert arena.T_max == dec.ctx and arena.tokens.shape == (3, dec.ctx // 2)
+    for t in arena.self_k + arena.self_v:
+        assert t.shape == (3, dec.ctx, dec.width)
+    assert dec._w()["decode_arenas"] and whisper._decode_arena(dec, 3, 2, int(xa.shape[1])) is arena
+
+
+def test_step_rows_method_equals_the_entry(dev):
+    m, _, _ = model("p", dev)
+    dec = m.decoder
+    cfg, _, seed, _ = synth.WHISPER_DEC_CASES["p"]
+    xa = synth.whisper_audio_states(cfg, 2, seed + 100).to(dev)
+    T, positions = 4, (0, 2, -1)
+    ctl = whisper.new_row_ctl([(p, 0, T, 0, 0, 0.0) for p in positions], dev)
+    ids = torch.tensor([3, 17, 42], dtype=torch.int32, device=dev)
+
+    def prepared():
+        kc = whisper.KVCache(dec, xa, torch.tensor([0, 1, 1], dtype=torch.int32), T, per_row=True)
+        for t in kc.self_k + kc.self_v + [kc.logits]:
+            t.fill_(CANARY)
+        return kc
+    a, b = prepared(), prepared()
+    assert dec.step_rows(ctl, ids, a) is a.logits
+    _lib.check(_lib.load().hirest_whisper_decode_step_rows(C.byref(dec._w()["desc"]), 3, ctl.data_ptr(), ids.data_ptr(), b.k_ptrs, b.v_ptrs, b.T_max,
+                                                           b.x_ptrs, b.n_windows, b.Tk, b.row_window.data_ptr(), b.logits.data_ptr(),
+                                                           b.ws.data_ptr(), b.ws.numel(), ops.stream_ptr()), "hirest_whisper_decode_step_rows")
+    torch.cuda.synchronize()
+    assert torch.equal(a.logits, b.logits) and not bool((a.logits[:2] == CANARY).any())
+    for x, y in zip(a.self_k + a.self_v, b.self_k + b.self_v):
+        assert torch.equal(x, y)
+        assert bool((x[2] == CANARY).all())                            # the inactive row's cache
+        for r, p in enumerate(positions[:2]):                          # an active row wrote its own position and no other
+            assert not bool((x[r, p] == CANARY).any())
+            assert bool((x[r, :p] == CANARY).all()) and bool((x[r, p + 1:] == CANARY).all())
+
+
 # ---------------------------------------------------------------------------------------------------------------- transcribe
 def test_transcribe_equals_eager(dev):
     """31 s of synthetic audio — two windows — through the case-p decoder behind the 1500-position encoder, with the temperature

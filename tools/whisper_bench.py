@@ -205,21 +205,12 @@ def graph_rows(a, model, xa, full, one, steps, chunk, want_tokens):
 
 def step_rows_setup(model, xa, sot):
     """what one ``hirest_whisper_decode_step_rows`` call of <|startoftranscript|> at position 0 needs, row w against window w: the work
-    inside ``detect_language``, set up outside the timed call.  Uses nothing that ``detect_language`` brought, so the same function times
-    the step on a commit without it."""
-    import ctypes as C
-    from hirest_amd import _lib, ops
+    inside ``detect_language`` (``TextDecoder.step_rows``), set up outside the timed call."""
     dec, dev, R = model.decoder, model.device, int(xa.shape[0])
     kc = whisper.KVCache(dec, xa, torch.arange(R, dtype=torch.int32), 1, per_row=True)
     ctl = whisper.new_row_ctl([(0, 0, 1, 0, 0, 0.0)] * R, dev)
     ids = torch.full((R,), sot, dtype=torch.int32, device=dev)
-    lib, desc = _lib.load(), C.byref(dec._w()["desc"])
-
-    def step():
-        _lib.check(lib.hirest_whisper_decode_step_rows(desc, R, ctl.data_ptr(), ids.data_ptr(), kc.k_ptrs, kc.v_ptrs, kc.T_max, kc.x_ptrs,
-                                                       kc.n_windows, kc.Tk, kc.row_window.data_ptr(), kc.logits.data_ptr(), kc.ws.data_ptr(),
-                                                       kc.ws.numel(), ops.stream_ptr()), "hirest_whisper_decode_step_rows")
-    return step, (kc, ctl, ids)
+    return (lambda: dec.step_rows(ctl, ids, kc)), (kc, ctl, ids)
 
 
 def small_decoder_model(dev, languages):
@@ -274,7 +265,7 @@ def detect_leg(a, dev):
 
 
 def step_leg(a, dev):
-    """one ``hirest_whisper_decode_step_rows`` call at R = W alone (``step_rows_setup``): runs on a commit without ``detect_language``"""
+    """one ``hirest_whisper_decode_step_rows`` call at R = W alone (``step_rows_setup``)"""
     model, cfg = small_decoder_model(dev, 0)
     xa_all = synth.whisper_audio_states(cfg, max(a.detect_windows), 7).to(dev)
     table = {}
